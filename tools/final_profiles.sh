@@ -7,17 +7,17 @@ cd $R
 python __graft_entry__.py > $O/build.log 2>&1
 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; echo "smoke rc=$?" >> $O/smoke.log
 timeout 1500 python -m pytest tests -q -m gpu -s -p no:cacheprovider > $O/pytest_gpu.log 2>&1; echo "rc=$?" >> $O/pytest_gpu.log
-timeout 400 python bench.py > $O/bench.json 2> $O/bench.err
-GO2_GEMM_SPLIT=0 timeout 200 python bench.py --no-cpu-baseline > $O/bench_fp32_mfma_gemms.json 2> /dev/null
-GO2_FUSED_MLP=0 timeout 200 python bench.py --steps 30 --no-cpu-baseline > $O/bench_reference_formulation.json 2> /dev/null
-timeout 200 python bench.py --task go2 --no-cpu-baseline > $O/bench_go2.json 2> /dev/null
-timeout 200 python bench.py --task go2_cts --steps 50 --no-cpu-baseline > $O/bench_go2_cts.json 2> /dev/null
-GO2_GEMM_SPLIT=0 timeout 200 python bench.py --task go2_cts --steps 30 --no-cpu-baseline > $O/bench_go2_cts_fp32_mfma_gemms.json 2> /dev/null
-GO2_WGRAD_BELOW=0 timeout 200 python bench.py --no-cpu-baseline > $O/bench_wgrad_below0.json 2> /dev/null
-timeout 200 python bench.py --task go2 --num-envs 32768 --steps 20 --warmup 8 --no-cpu-baseline > $O/bench_go2_32768.json 2> /dev/null
-timeout 200 python bench.py --num-envs 8192 --steps 40 --warmup 10 --no-cpu-baseline > $O/bench_go2_flat_8192.json 2> /dev/null
-timeout 200 python bench.py --task go2_moe_cts --num-envs 8192 --steps 20 --warmup 8 --no-cpu-baseline > $O/bench_go2_moe_cts_8192.json 2> /dev/null
-timeout 200 python bench.py --task go2_moe_cts --num-envs 1024 --steps 30 --warmup 8 --no-cpu-baseline > $O/bench_go2_moe_cts_1024.json 2> /dev/null
+timeout 400 python bench.py --full > $O/bench.json 2> $O/bench.err
+GO2_GEMM_SPLIT=0 timeout 200 python bench.py --full --no-cpu-baseline > $O/bench_fp32_mfma_gemms.json 2> /dev/null
+GO2_FUSED_MLP=0 timeout 200 python bench.py --full --steps 30 --no-cpu-baseline > $O/bench_reference_formulation.json 2> /dev/null
+timeout 200 python bench.py --full --task go2 --no-cpu-baseline > $O/bench_go2.json 2> /dev/null
+timeout 200 python bench.py --full --task go2_cts --steps 50 --no-cpu-baseline > $O/bench_go2_cts.json 2> /dev/null
+GO2_GEMM_SPLIT=0 timeout 200 python bench.py --full --task go2_cts --steps 30 --no-cpu-baseline > $O/bench_go2_cts_fp32_mfma_gemms.json 2> /dev/null
+GO2_WGRAD_BELOW=0 timeout 200 python bench.py --full --no-cpu-baseline > $O/bench_wgrad_below0.json 2> /dev/null
+timeout 200 python bench.py --full --task go2 --num-envs 32768 --steps 20 --warmup 8 --no-cpu-baseline > $O/bench_go2_32768.json 2> /dev/null
+timeout 200 python bench.py --full --num-envs 8192 --steps 40 --warmup 10 --no-cpu-baseline > $O/bench_go2_flat_8192.json 2> /dev/null
+timeout 200 python bench.py --full --task go2_moe_cts --num-envs 8192 --steps 20 --warmup 8 --no-cpu-baseline > $O/bench_go2_moe_cts_8192.json 2> /dev/null
+timeout 200 python bench.py --full --task go2_moe_cts --num-envs 1024 --steps 30 --warmup 8 --no-cpu-baseline > $O/bench_go2_moe_cts_1024.json 2> /dev/null
 if [ -z "$SKIP_STEP_KERNEL" ]; then          # (SKIP_STEP_KERNEL=1: libgo2sim_hip.so is unchanged since the last full set — its kbench / PMC / SQ files stay valid, keyed by the library's hash)
 timeout 150 python tools/kbench.py 4096 > $O/kbench.txt 2>&1
 timeout 150 python tools/kbench.py 4096 rough > $O/kbench_rough.txt 2>&1
@@ -47,7 +47,7 @@ for spec in "go2_flat 4096 30 20" "go2_cts 4096 12 8" "go2_moe_cts 8192 8 8" "go
   set -- $spec; task=$1; n=$2; steps=$3; warm=$4
   rm -rf /tmp/prof_$task
   sfx=""; [ "$n" != "4096" ] && [ "$task" != "go2_moe_cts" -o "$n" != "8192" ] && sfx="_$n"
-  timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$task -o b -- python $R/bench.py --task $task --num-envs $n --steps $steps --warmup $warm --no-cpu-baseline > $O/bench_${task}${sfx}_under_rocprof.json 2> /dev/null
+  timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$task -o b -- python $R/bench.py --full --task $task --num-envs $n --steps $steps --warmup $warm --no-cpu-baseline > $O/bench_${task}${sfx}_under_rocprof.json 2> /dev/null
   find /tmp/prof_$task -name "*kernel_stats.csv" -exec cp {} $O/bench_${task}${sfx}_kernel_stats.csv \;
   python $R/tools/trace_timeline.py $(find /tmp/prof_$task -name "*kernel_trace.csv" | head -1) > $O/${task}${sfx}_timeline.txt 2>&1
 done

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Timeline of one rollout step and one mini-batch update out of a rocprofv3 kernel trace of bench.py.
-On the GPU box:  cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --output-format csv -d /tmp/kt -o kt -- python $GRAFT_REPO_ROOT/bench.py --steps 4 --warmup 6 --no-cpu-baseline
+On an MI355X:    export TMPDIR=/tmp && rocprofv3 --kernel-trace --output-format csv -d /tmp/kt -o kt -- python bench.py --full --steps 4 --warmup 6 --no-cpu-baseline
                  python tools/trace_timeline.py /tmp/kt/kt_kernel_trace.csv > gpurun_out/timeline.txt"""
 import csv, sys
 rows = list(csv.DictReader(open(sys.argv[1])))
