@@ -10,7 +10,8 @@ import torch.nn as nn
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 NN_LIB = os.path.join(_HERE, "libgo2nn_hip.so")
-GO2NN_MAX_LAYERS, GO2NN_MAX_WIDTH, GO2NN_ABI_VERSION, GO2NN_MAX_GROUP = 6, 512, 6, 2
+GO2NN_MAX_LAYERS, GO2NN_MAX_WIDTH, GO2NN_ABI_VERSION, GO2NN_MAX_GROUP = 6, 512, 7, 2
+GO2NN_RNN_LSTM, GO2NN_RNN_GRU, GO2NN_RNN_MAX_STATES = 0, 1, 4
 _cached = None
 
 
@@ -51,6 +52,16 @@ class Go2nnMlpIO(C.Structure):
 class Go2nnMlp(C.Structure):
     _fields_ = [("num_layers", C.c_int32), ("dims", C.c_int32 * (GO2NN_MAX_LAYERS + 1)),
                 ("weight", C.c_void_p * GO2NN_MAX_LAYERS), ("bias", C.c_void_p * GO2NN_MAX_LAYERS)]
+
+
+class Go2nnRnnCellJob(C.Structure):          # ABI 7
+    _fields_ = [(k, C.c_void_p) for k in ("gi", "gh", "h_prev", "c_prev", "h", "c", "gates", "save_h", "save_c", "done", "sub_h", "sub_c", "next_h", "next_c")] + \
+               [(k, C.c_int32) for k in ("B", "H", "type", "pad_")]
+
+
+class Go2nnRnnCellBwdJob(C.Structure):       # ABI 7
+    _fields_ = [(k, C.c_void_p) for k in ("gates", "c", "c_prev", "h_prev", "dy", "dh_rec", "dh_carry", "dc", "done", "dgi", "dgh")] + \
+               [(k, C.c_int32) for k in ("B", "H", "type", "pad_")]
 
 
 def bind(path):
@@ -94,6 +105,9 @@ def bind(path):
     lib.go2nn_moe_usage.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
     lib.go2nn_moe_mix_loss.argtypes = [C.c_void_p] * 7 + [C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.go2nn_moe_mix_forward.argtypes = [C.c_void_p] * 5 + [C.c_int32] * 5 + [C.c_void_p]
+    lib.go2nn_rnn_cell_forward.argtypes = [C.POINTER(Go2nnRnnCellJob), C.c_int32, C.c_void_p]
+    lib.go2nn_rnn_cell_backward.argtypes = [C.POINTER(Go2nnRnnCellBwdJob), C.c_int32, C.c_void_p]
+    lib.go2nn_rnn_reset.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
     if lib.go2nn_abi_version() != GO2NN_ABI_VERSION:
         raise RuntimeError("%s: ABI version %d, expected %d" % (path, lib.go2nn_abi_version(), GO2NN_ABI_VERSION))
     return lib

@@ -1224,3 +1224,5 @@ int go2nn_moe_mix_forward(const float* logits, const float* outs, const float* b
 }
 
 }  // extern "C"
+
+#include "go2nn_rnn.h"          // ABI 7: the recurrent memory's cell steps

@@ -155,6 +155,19 @@ class GO2FlatCfgPPO(GO2CfgPPO):
         experiment_name = "go2_flat_ppo"
 
 
+class GO2FlatCfgRnnPPO(GO2FlatCfgPPO):
+    """task=go2_flat_rnn: go2_flat with the recurrent actor-critic (the switch legged_robot_config.py:269-272 documents): an LSTM memory of 256 units, one layer,
+    in front of each MLP head"""
+    class policy(GO2FlatCfgPPO.policy):
+        rnn_type = "lstm"
+        rnn_hidden_size = 256
+        rnn_num_layers = 1
+
+    class runner(GO2FlatCfgPPO.runner):
+        policy_class_name = "ActorCriticRecurrent"
+        experiment_name = "go2_flat_rnn"
+
+
 class GO2CfgCTS(LeggedRobotCfgCTS):                 # go2_config.py:219-229
     class runner(LeggedRobotCfgCTS.runner):
         num_steps_per_env = 24

@@ -108,7 +108,7 @@ class _RolloutHeads:
 
     def _actor_critic(self, ac, obs, cobs):
         """-> (ac.actor(obs), ac.evaluate(cobs)) under autograd: one node per network (modules/fused.py:_FusedMLP)"""
-        return ac.actor(obs), ac.evaluate(cobs)
+        return ac.actor(obs), (ac.critic(cobs) if getattr(self, "_rnn", False) else ac.evaluate(cobs))
 
     # The two per-step element-wise heads of the rollout as library kernels (go2sim_act_head, go2sim_store_transition): sampling +
     # log-prob + the storage rows in one launch, reward bootstrap + done copy in another, instead of ~23 small launches.
@@ -236,6 +236,10 @@ class PPO(_RolloutHeads):
             from ..modules import fused
             fused.set_library(lib)         # Linear->ELU pairs: activation + bias gradients in one HBM pass (go2sim_elu_backward_bias), ELU in place
                                            # (+6 % whole-job, measured; GO2_FUSED_MLP=0 restores plain autograd)
+        # a recurrent policy (modules/actor_critic_recurrent.py): the is_recurrent branches of the reference (ppo.py:90-93,123-126) -> the _rnn_* methods below
+        self._rnn, self._rm = bool(getattr(actor_critic, "is_recurrent", False)), None
+        if self._rnn and _world() > 1:
+            raise NotImplementedError("recurrent policies (ActorCriticRecurrent) train on one rank only: multi-rank recurrent PPO is not implemented")
         if _world() > 1:   # identical initial replicas
             for p in self.actor_critic.parameters():
                 dist.broadcast(p.data, src=0)
@@ -252,6 +256,11 @@ class PPO(_RolloutHeads):
 
     def init_storage(self, num_envs, num_transitions_per_env, actor_obs_shape, critic_obs_shape, action_shape):
         self.storage = RolloutStorage(num_envs, num_transitions_per_env, actor_obs_shape, critic_obs_shape, action_shape, self.device, lib=self.lib)
+        if self._rnn:
+            ac = self.actor_critic
+            ac.init_hidden_states(num_envs, self.device)
+            self.storage.init_hidden_states(len(ac.memory_a.states()), len(ac.memory_c.states()), ac.memory_a.rnn.num_layers, ac.memory_a.rnn.hidden_size)
+            self._rnn_memory()          # (on the library's kernels: checks the memory's shape now, not at the first step)
 
     def test_mode(self):
         self.actor_critic.eval()
@@ -261,6 +270,8 @@ class PPO(_RolloutHeads):
 
     # ------------------------------------------------------------------ rollout half (ppo.py:90-118)
     def act(self, obs, critic_obs):
+        if self._rnn:
+            return self._rnn_act(obs, critic_obs)
         st, t, ac = self.storage, self.transition, self.actor_critic
         s = st.step
         if s >= st.num_transitions_per_env:
@@ -313,7 +324,7 @@ class PPO(_RolloutHeads):
         ok = False
         if lib is not None:
             from ... import _nn
-            ok = _nn.PolicyKernel.supports(self.actor_critic) and self.storage is not None and self.storage.privileged_observations is not None
+            ok = _nn.PolicyKernel.supports(self.actor_critic) and self.storage is not None and (self.storage.privileged_observations is not None or self._rnn)
         self._pk = _nn.PolicyKernel(lib, self.actor_critic) if ok else False
         return self._pk if self._pk is not False else None
 
@@ -324,7 +335,7 @@ class PPO(_RolloutHeads):
             self._store_transition(rewards, dones, infos, s)
             st.step += 1
             t.clear()
-            self.actor_critic.reset(dones)
+            self._reset_memory(dones, s)
             return
         r = rewards.clone()
         if "time_outs" in infos:   # bootstrap on time-outs (ppo.py:107-108)
@@ -333,9 +344,18 @@ class PPO(_RolloutHeads):
         st.dones[s].copy_(dones.view(-1, 1))
         st.step += 1
         t.clear()
-        self.actor_critic.reset(dones)
+        self._reset_memory(dones, s)
+
+    def _reset_memory(self, dones, s):
+        rm = self._rnn_memory() if self._rnn else None
+        if rm is not None:
+            rm.reset(self.storage.dones[s].view(-1))          # (uint8 done row of the step: written by the env kernel or the store above)
+        else:
+            self.actor_critic.reset(dones)
 
     def compute_returns(self, last_critic_obs):
+        if self._rnn:
+            return self._rnn_compute_returns(last_critic_obs)
         pk = self._pk if self._pk not in (None, False) else None
         if pk is not None and self._pk_packed and last_critic_obs.is_contiguous() and last_critic_obs.dtype == torch.float32:
             last_values = pk.critic.forward(last_critic_obs)          # the bootstrap value as ONE launch on the weights packed for this rollout (they have not changed since)
@@ -352,7 +372,7 @@ class PPO(_RolloutHeads):
             return loss, stats[1], stats[0], stats[2]
         ac.update_distribution(obs_b)     # the reference calls act() here and discards the sample (ppo.py:131)
         lp_b = ac.get_actions_log_prob(act_b)
-        val_b = ac.evaluate(cobs_b)
+        val_b = ac.critic(cobs_b) if self._rnn else ac.evaluate(cobs_b)          # (recurrent: cobs_b is the critic memory's output)
         mu_b, sig_b, ent_b = ac.action_mean, ac.action_std, ac.entropy
         with torch.no_grad():
             kl = torch.sum(torch.log(sig_b / old_sig_b + 1.0e-5) + (torch.square(old_sig_b) + torch.square(old_mu_b - mu_b)) / (2.0 * torch.square(sig_b)) - 0.5, axis=-1)
@@ -379,8 +399,9 @@ class PPO(_RolloutHeads):
         mean_value_loss, mean_surrogate_loss = 0.0, 0.0
         world = _world()
         adaptive = self.desired_kl is not None and self.schedule == "adaptive"
-        for batch in self.storage.mini_batch_generator(self.num_mini_batches, self.num_learning_epochs):
-            loss, value_loss, surrogate_loss, kl_mean = self._losses(*batch[:9])
+        batches = self._rnn_batches() if self._rnn else self.storage.mini_batch_generator(self.num_mini_batches, self.num_learning_epochs)
+        for batch in batches:
+            loss, value_loss, surrogate_loss, kl_mean = self._rnn_losses(batch) if self._rnn else self._losses(*batch[:9])
             self.optimizer.zero_grad()
             loss.backward()
             if _collectives_on():
@@ -556,9 +577,137 @@ class PPO(_RolloutHeads):
 
     def update(self):
         self._pk_packed = False          # the optimizer steps below change the parameters: the next rollout re-packs
-        if self.use_graphs:
+        if self._rnn and self.use_graphs and self._rnn_memory() is not None:
+            out = self._rnn_update_graphs()
+        elif self.use_graphs and not self._rnn:
             out = self._update_graphs()
         else:
             out = self._update_eager()
         self.storage.clear()
         return out
+
+    # ------------------------------------------------------------------ recurrent policies (the reference's is_recurrent branches)
+    # Rollout: the memories' step (the state before it into storage slot s), then the heads as for a feed-forward policy (go2nn_policy_act on the memories' h);
+    # process_env_step zeroes the done rows; compute_returns advances the critic memory one more step on the last observations, as the reference's evaluate() does.
+    # Update: contiguous env slices, all T steps, no shuffling, the same order every epoch (rollout_storage.py:186-234).  On the library's kernels the memory runs at
+    # fixed shapes (modules/fused_rnn.py) and the whole update is one HIP graph; the reference formulation (GO2_FUSED_MLP=0, the CPU) is nn.LSTM / nn.GRU over the
+    # padded episode segments of storage.reccurent_mini_batch_generator.
+    def _rnn_memory(self):
+        """-> modules/fused_rnn.py:RolloutMemory when the library's kernels are in use, else None (the torch formulation)"""
+        from ..modules import fused_rnn
+        if not fused_rnn.available():
+            return None
+        if self._rm is None:
+            self._rm = fused_rnn.RolloutMemory(self.actor_critic)
+        return self._rm
+
+    def _rnn_act(self, obs, critic_obs):
+        st, t, ac = self.storage, self.transition, self.actor_critic
+        s = st.step
+        if s >= st.num_transitions_per_env:
+            raise AssertionError("Rollout buffer overflow")
+        if obs.data_ptr() != st.observations[s].data_ptr():
+            st.observations[s].copy_(obs)
+        if st.privileged_observations is not None and critic_obs.data_ptr() != st.privileged_observations[s].data_ptr():
+            st.privileged_observations[s].copy_(critic_obs)
+        t.observations, t.critic_observations = obs, critic_obs
+        rm = self._rnn_memory()
+        if rm is not None:
+            if s == 0:
+                rm.images()            # the split weight images: once per rollout (inside the captured rollout too)
+            h_a, h_c = rm.step([obs.contiguous(), critic_obs.contiguous()], slots=[(st.saved_hidden_states_a, s), (st.saved_hidden_states_c, s)])
+        else:
+            for mem, saved in ((ac.memory_a, st.saved_hidden_states_a), (ac.memory_c, st.saved_hidden_states_c)):
+                for dst, src in zip(saved, mem.states()):
+                    dst[s].copy_(src)
+            h_a, h_c = ac.memory_a(obs).squeeze(0), ac.memory_c(critic_obs).squeeze(0)
+        if self.fused_rollout:
+            pk = self._policy_kernel()
+            if pk is not None:
+                if s == 0 or not self._pk_packed:
+                    pk.pack()
+                    self._pk_packed = True
+                    self._pk_recorded = self._pk_recorded or s == 0
+                actions = pk.act(h_a, h_c, self._rollout_noise(ac, st, s), st.actions[s], st.mu[s], st.sigma[s], st.actions_log_prob[s].view(-1), st.values[s].view(-1))
+                t.actions, t.values, t.actions_log_prob = actions, st.values[s], st.actions_log_prob[s].view(-1)
+                t.action_mean, t.action_sigma = st.mu[s], st.sigma[s]
+                return actions
+            if s == 0:
+                self._pk_recorded = False
+            return self._act_head(ac.actor(h_a), ac.std, self._rollout_noise(ac, st, s), ac.critic(h_c), s)
+        t.actions = _AC.act(ac, h_a).detach()
+        t.values = _AC.evaluate(ac, h_c).detach()
+        t.actions_log_prob = ac.get_actions_log_prob(t.actions).detach()
+        t.action_mean, t.action_sigma = ac.action_mean.detach(), ac.action_std.detach()
+        st.actions[s].copy_(t.actions)
+        st.values[s].copy_(t.values)
+        st.actions_log_prob[s].copy_(t.actions_log_prob.view(-1, 1))
+        st.mu[s].copy_(t.action_mean)
+        st.sigma[s].copy_(t.action_sigma)
+        return t.actions
+
+    def _rnn_compute_returns(self, last_critic_obs):
+        rm = self._rnn_memory()
+        if rm is not None:
+            h_c = rm.step([last_critic_obs.contiguous()], which=(1,))[0]          # the critic memory's extra step (the reference's evaluate(): its state carries on)
+            pk = self._pk if self._pk not in (None, False) else None
+            last_values = pk.critic.forward(h_c) if (pk is not None and self._pk_packed) else self.actor_critic.critic(h_c).detach()
+        else:
+            last_values = self.actor_critic.evaluate(last_critic_obs).detach()
+        self.storage.compute_returns(last_values, self.gamma, self.lam)
+
+    def _rnn_batches(self):
+        if self._rnn_memory() is not None:
+            fixed = self.storage.recurrent_fixed_batches(self.num_mini_batches)
+            return (b for _ in range(self.num_learning_epochs) for b in fixed)
+        return self.storage.reccurent_mini_batch_generator(self.num_mini_batches, self.num_learning_epochs)
+
+    def _rnn_heads_inputs(self, batch):
+        """-> (actor memory output, critic memory output) [T * B, H] of a mini-batch of either generator"""
+        ac = self.actor_critic
+        obs, cobs, (hid_a, hid_c), masks = batch[0], batch[1], batch[9], batch[10]
+        if self._rnn_memory() is not None:
+            from ..modules import fused_rnn
+            ya, yc = fused_rnn.memory_sequence(ac.memory_a, obs, hid_a, masks), fused_rnn.memory_sequence(ac.memory_c, cobs, hid_c, masks)
+        else:
+            ya, yc = ac.memory_a(obs, masks, hid_a), ac.memory_c(cobs, masks, hid_c)
+        return ya.reshape(-1, ya.shape[-1]), yc.reshape(-1, yc.shape[-1])
+
+    def _rnn_losses(self, batch):
+        ya, yc = self._rnn_heads_inputs(batch)
+        flat = lambda t: t.reshape(-1, t.shape[-1])
+        return self._losses(ya, yc, *[flat(t) for t in batch[2:9]])
+
+    def _rnn_graph_step(self, i):
+        batch = self._rnn_fixed[i]
+        ac = self.actor_critic
+        ya, yc = self._rnn_heads_inputs(batch)
+        rest = [t.reshape(-1, t.shape[-1]) for t in batch[2:9]]
+        self.optimizer.zero_grad(set_to_none=True)
+        if self.fused_loss:
+            mu_b, val_b = ac.actor(ya), ac.critic(yc)
+            stats, gmu, gstd, gval = _FusedPPOLoss.kernel(self, mu_b, ac.std, val_b, *rest)
+            self._acc.add_(stats[:2])
+            torch.autograd.backward([mu_b, ac.std, val_b], [gmu, gstd.view_as(ac.std), gval])
+            self._kl = stats[2]
+        else:
+            loss, value_loss, surrogate_loss, kl_mean = self._losses(ya, yc, *rest)
+            loss.backward()
+            self._acc.add_(torch.stack([surrogate_loss.detach(), value_loss.detach()]))
+            self._kl = kl_mean
+        self._graph_back()
+
+    def _rnn_update_graphs(self):
+        """the whole update (every epoch's mini-batch steps on fixed env slices of the rollout) as ONE HIP graph after one eager update; the learning-rate decision
+        on the device (FusedClipAdam), one host read per update"""
+        nmb, ne = self.num_mini_batches, self.num_learning_epochs
+        if self._graph is None:
+            self._rnn_fixed = self.storage.recurrent_fixed_batches(nmb)
+            self._acc = torch.zeros(2, device=self.device)
+            self._graph = [CapturedStep((lambda: [self._rnn_graph_step(i) for _ in range(ne) for i in range(nmb)] and None), enabled=self._capture, warmup=1,
+                                        name="recurrent PPO update (%d epochs x %d mini-batch steps)" % (ne, nmb))]
+        self._acc.zero_()
+        self._graph[0]()
+        out = torch.cat([self._acc / (ne * nmb), self._lr_t.reshape(1)]).tolist()
+        self.learning_rate = float(out[2])
+        return out[1], out[0]

@@ -22,9 +22,9 @@ from ...utils.helpers import class_to_dict
 from ..algorithms import PPO
 from ..algorithms._graph import load_optimizer_state, no_gc, strict_graphs
 from ..env import missing_members
-from ..modules import ActorCritic
+from ..modules import ActorCritic, ActorCriticRecurrent
 
-_POLICIES = {"ActorCritic": ActorCritic}
+_POLICIES = {"ActorCritic": ActorCritic, "ActorCriticRecurrent": ActorCriticRecurrent}
 _ALGS = {"PPO": PPO}
 
 for _t, _f in ((np.float32, float), (np.float64, float), (np.int32, int), (np.int64, int)):

@@ -42,7 +42,15 @@ class RolloutStorage:
         self.mu, self.sigma = z(*actions_shape), z(*actions_shape)
         self._partials = torch.zeros(3, dtype=torch.float64, device=device)
         self.num_transitions_per_env, self.num_envs = T, N
+        self.saved_hidden_states_a = self.saved_hidden_states_c = None          # recurrent policies: init_hidden_states
         self.step = 0
+
+    def init_hidden_states(self, n_a, n_c, num_layers, hidden_size):
+        """the recurrent policy's saved states (rollout_storage.py:103-117 of the reference): n_a (n_c) tensors [T, num_layers, N, H] — [h] for a GRU, [h, c] for an
+        LSTM; slot t holds the state BEFORE step t (PPO.act writes it)"""
+        z = lambda: torch.zeros(self.num_transitions_per_env, num_layers, self.num_envs, hidden_size, device=self.device)
+        self.saved_hidden_states_a = [z() for _ in range(n_a)]
+        self.saved_hidden_states_c = [z() for _ in range(n_c)]
 
     def add_transitions(self, transition):
         if self.step >= self.num_transitions_per_env:
@@ -106,3 +114,45 @@ class RolloutStorage:
             for i in range(num_mini_batches):
                 b = indices[i * mini_batch_size:(i + 1) * mini_batch_size]
                 yield obs[b], cobs[b], acts[b], vals[b], adv[b], rets[b], logp[b], mu[b], sig[b], (None, None), None
+
+    # ---- recurrent policies ------------------------------------------------------------------------------------------------------------------------------
+    def reccurent_mini_batch_generator(self, num_mini_batches, num_epochs=8):
+        """The reference formulation of the recurrent update's mini-batches (GO2_FUSED_MLP=0, the CPU; the name is the reference's): contiguous env slices, every
+        epoch in the same order, each slice's episode segments zero-padded into a batch of sequences (utils.EpisodeLayout, which reads the segment count back to
+        the host) with the state every segment starts from.  Tuple: obs, critic obs (padded [T_pad, S, .]), actions ... sigma ([T, B, .]), (actor states, critic
+        states) — [L, S, H], an (h, c) pair for an LSTM — and the validity mask [T_pad, S]."""
+        from ..modules.actor_critic_recurrent import LSTM_CRITIC_STARTS_FROM_ACTOR_STATES
+        from ..utils import EpisodeLayout
+        lay = EpisodeLayout(self.dones)
+        obs = lay.pad(self.observations)
+        cobs = lay.pad(self.privileged_observations) if self.privileged_observations is not None else obs
+        first = lambda saved: [lay.initial_states(s) for s in saved]
+        init_a, init_c = first(self.saved_hidden_states_a), first(self.saved_hidden_states_c)
+        if len(init_a) == 2 and LSTM_CRITIC_STARTS_FROM_ACTOR_STATES:
+            init_c = init_a
+        states = lambda init, seg: init[0][:, seg] if len(init) == 1 else tuple(x[:, seg] for x in init)
+        width = self.num_envs // num_mini_batches
+        batches = []
+        for i in range(num_mini_batches):
+            envs, seg = slice(i * width, (i + 1) * width), lay.segments_of(i * width, (i + 1) * width)
+            rows = [t[:, envs] for t in (self.actions, self.values, self.advantages, self.returns, self.actions_log_prob, self.mu, self.sigma)]
+            batches.append((obs[:, seg], cobs[:, seg], *rows, (states(init_a, seg), states(init_c, seg)), lay.valid[:, seg]))
+        for _ in range(num_epochs):
+            yield from batches
+
+    def recurrent_fixed_batches(self, num_mini_batches):
+        """The same mini-batches at fixed shapes (what modules/fused_rnn.py:RnnFunction takes): per contiguous env slice the [T, B, ...] views of the rollout, the
+        saved states [T, L, B, H] of both memories and the dones [T, B] (uint8).  No host read, no padding; the slices are views (the update graph reads them in place)."""
+        from ..modules.actor_critic_recurrent import LSTM_CRITIC_STARTS_FROM_ACTOR_STATES
+        mb = self.num_envs // num_mini_batches
+        cobs = self.privileged_observations if self.privileged_observations is not None else self.observations
+        out = []
+        for i in range(num_mini_batches):
+            sl = lambda t, i=i: t[:, i * mb:(i + 1) * mb]
+            hid_a = [s[:, :, i * mb:(i + 1) * mb] for s in self.saved_hidden_states_a]
+            hid_c = [s[:, :, i * mb:(i + 1) * mb] for s in self.saved_hidden_states_c]
+            if len(hid_c) == 2 and LSTM_CRITIC_STARTS_FROM_ACTOR_STATES:
+                hid_c = hid_a
+            out.append((sl(self.observations), sl(cobs), sl(self.actions), sl(self.values), sl(self.advantages), sl(self.returns), sl(self.actions_log_prob),
+                        sl(self.mu), sl(self.sigma), (hid_a, hid_c), sl(self.dones)[..., 0]))
+        return out

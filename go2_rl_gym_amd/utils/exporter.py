@@ -157,14 +157,57 @@ class _DualMoECTSPolicy(nn.Module):
         self.history = torch.zeros_like(self.history)
 
 
+class _LSTMPolicy(nn.Module):
+    """forward(obs) -> action with the LSTM's (h, c) carried in the hidden_state / cell_state buffers [num_layers, 1, H]; reset() zeroes them
+    (PolicyExporterLSTM, legged_gym/utils/exporter.py:94-120)"""
+
+    def __init__(self, actor, rnn, normalizer):
+        super().__init__()
+        self.actor, self.memory, self.normalizer = actor, rnn, normalizer
+        self.register_buffer("hidden_state", torch.zeros(rnn.num_layers, 1, rnn.hidden_size))
+        self.register_buffer("cell_state", torch.zeros(rnn.num_layers, 1, rnn.hidden_size))
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        x = self.normalizer(x)
+        out, (h, c) = self.memory(x.unsqueeze(0), (self.hidden_state, self.cell_state))
+        self.hidden_state[:] = h
+        self.cell_state[:] = c
+        return self.actor(out.squeeze(0))
+
+    @torch.jit.export
+    def reset(self):
+        self.hidden_state[:] = 0.0
+        self.cell_state[:] = 0.0
+
+
+class _GRUPolicy(nn.Module):
+    """the GRU twin of _LSTMPolicy (the reference's exporter only has the LSTM form, whose (h, c) unpacking a GRU cannot run): hidden_state only"""
+
+    def __init__(self, actor, rnn, normalizer):
+        super().__init__()
+        self.actor, self.memory, self.normalizer = actor, rnn, normalizer
+        self.register_buffer("hidden_state", torch.zeros(rnn.num_layers, 1, rnn.hidden_size))
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        x = self.normalizer(x)
+        out, h = self.memory(x.unsqueeze(0), self.hidden_state)
+        self.hidden_state[:] = h
+        return self.actor(out.squeeze(0))
+
+    @torch.jit.export
+    def reset(self):
+        self.hidden_state[:] = 0.0
+
+
 def _cpu_copy(m):
     return _plain(copy.deepcopy(m).cpu())
 
 
 def _deployment_module(policy, normalizer=None):
-    if getattr(policy, "is_recurrent", False):
-        raise NotImplementedError("recurrent policies are not part of the go2 tasks")
     norm = _cpu_copy(normalizer) if normalizer else nn.Identity()
+    if getattr(policy, "is_recurrent", False):
+        rnn = copy.deepcopy(policy.memory_a.rnn).cpu()
+        return (_LSTMPolicy if isinstance(rnn, nn.LSTM) else _GRUPolicy)(_cpu_copy(policy.actor), rnn, norm)
     if not hasattr(policy, "actor"):
         raise ValueError("Policy does not have an actor/student module.")
     if hasattr(policy, "actor_mcp"):
@@ -249,6 +292,8 @@ class _OnnxPolicy(nn.Module):
 
 def export_policy_as_onnx(policy, path, normalizer=None, filename="policy.onnx", verbose=False):
     """ONNX graph, opset 11, static shapes (exporter.py:25-40,289-307)."""
+    if getattr(policy, "is_recurrent", False):
+        raise NotImplementedError("ONNX export of recurrent policies (ActorCriticRecurrent) is not implemented: export them as TorchScript (export_policy_as_jit)")
     os.makedirs(path, exist_ok=True)
     mod = _OnnxPolicy(policy, normalizer).to("cpu")
     # output names follow what forward() returns for the policy class (exporter.py:289-307): MCP (mean, weights); AC-MoE / Dual-MoE mean only;

@@ -21,9 +21,10 @@
 extern "C" {
 #endif
 
-#define GO2NN_ABI_VERSION 6      /* 2: + the learner-side kernels (go2nn_head_backward, go2nn_linear_*); 3: + the grouped (actor + critic) layer calls; 4: + split-operand (3 x bf16) products;
+#define GO2NN_ABI_VERSION 7      /* 2: + the learner-side kernels (go2nn_head_backward, go2nn_linear_*); 3: + the grouped (actor + critic) layer calls; 4: + split-operand (3 x bf16) products;
                                     5: + the CTS pieces: layers without activation, plain input gradients, the latent normaliser forward / backward, the split surrogate, two-segment policy inputs;
-                                    6: + Go2nnBwdInJob.x_in: the weight gradient of the layer below out of the input gradient's epilogue (its gz_prev never goes to HBM) */
+                                    6: + Go2nnBwdInJob.x_in: the weight gradient of the layer below out of the input gradient's epilogue (its gz_prev never goes to HBM);
+                                    7: + the recurrent memory's cell steps (LSTM / GRU) and state reset */
 #define GO2NN_MAX_LAYERS 6
 #define GO2NN_MAX_WIDTH 512      /* widest layer input / output (LDS holds two 32-row activation tiles of this width) */
 #define GO2NN_EINVAL (-22)
@@ -236,6 +237,47 @@ int go2nn_moe_mix_forward(const float* logits, const float* outs, const float* b
 /* expert_major 1: outs / d_outs are [E, n, L] (the batched GEMM's own layout: no transposing copies either way).  bias (optional, [E, L]): the expert heads' output bias,
  * added to outs here — autograd then differentiates a plain batched product — with its gradient left as go2nn_l2norm_backward_rows(n) partial rows of E L columns in
  * dbias_partials (a 77 us torch reduction otherwise). */
+
+/* ---- ABI 7: the recurrent memory of ActorCriticRecurrent (rsl_rl/rsl_rl/modules/actor_critic_recurrent.py: Memory = nn.LSTM / nn.GRU, sequence-first, torch's gate
+ * order and formulas).  One time step of one layer is two matrix products on the kernels above (go2nn_linear_elu_forward_group, act 1, split images):
+ *   gi = x W_ih^T + b_ih,  gh = h_prev W_hh^T + b_hh   [B, G H]  (G = 4: i, f, g, o;  G = 3: r, z, n — GRU keeps W_hn h + b_hn apart: n = tanh(gi_n + r (gh_n)))
+ * and ONE cell launch (go2nn_rnn_cell_forward) that applies the non-linearities and the state update for every (row, hidden unit); in the update the input products
+ * of all T steps are one GEMM up front.  The backward step (go2nn_rnn_cell_backward) turns the gradient at h_t (from the heads or the layer above, plus the carried
+ * gradient of step t+1) into the gradients at gi and gh; dW_ih, dW_hh and the biases are then one weight-gradient GEMM / column sum each over all T B rows, and the
+ * carried gradient of step t-1 is dgh W_hh (go2nn_linear_backward_input_group, plain).
+ * Done handling (the fixed-shape form of the reference's split / pad / unpad, rsl_rl/rsl_rl/utils/utils.py:33-71): a row with done[r] set carries sub[r] into the
+ * next step instead of its new state, and no gradient flows back through that carry.
+ * Cell jobs: elementwise, 1..GO2NN_MAX_GROUP jobs (actor and critic memory) per launch, any B >= 1, 1 <= H <= GO2NN_MAX_WIDTH.  Outputs may alias the inputs they
+ * replace element for element (h with h_prev, c with c_prev, dh_carry and dc in place). */
+#define GO2NN_RNN_LSTM 0
+#define GO2NN_RNN_GRU 1
+typedef struct Go2nnRnnCellJob {
+  const float *gi, *gh;          /* [B, G H] the two products of the step, biases included */
+  const float *h_prev, *c_prev;  /* [B, H] the state the step starts from (c: LSTM only) */
+  float *h, *c;                  /* [B, H] the new state (c: LSTM only) */
+  float* gates;                  /* [B, 4 H] or NULL: what the backward step reads — LSTM: i, f, g, o after the non-linearity; GRU: r, z, n, gh_n */
+  float *save_h, *save_c;        /* [B, H] or NULL: h_prev (c_prev) copied here first (the rollout storage slot of the step) */
+  const uint8_t* done;           /* [B] or NULL: rows whose carry into the next step is sub_h (sub_c) instead of the new state */
+  const float *sub_h, *sub_c;    /* [B, H] */
+  float *next_h, *next_c;        /* [B, H] or NULL: the carry = done[r] ? sub[r] : new state (the update's recurrence) */
+  int32_t B, H, type, pad_;
+} Go2nnRnnCellJob;
+typedef struct Go2nnRnnCellBwdJob {
+  const float *gates, *c, *c_prev, *h_prev;   /* step t's saved gates, c_t and c_{t-1} (LSTM) / h_{t-1} (GRU), as the forward step left them */
+  const float* dy;               /* [B, H] d loss / d h_t from outside the recurrence (the heads, or the layer above) */
+  const float* dh_rec;           /* [B, H] or NULL (the last step): dgh_{t+1} W_hh, the gradient at the carry t -> t+1 through the next step's product */
+  float* dh_carry;               /* GRU: [B, H] in: dh_{t+1} z_{t+1} (read when dh_rec is set), out: dh_t z_t.  LSTM: NULL */
+  float* dc;                     /* LSTM: [B, H] in: dc carried from step t+1 (read when dh_rec is set), out: the carry for step t-1.  GRU: NULL */
+  const uint8_t* done;           /* [B] or NULL: done[t] of the forward (rows whose carry t -> t+1 was replaced: dh_rec, dh_carry and dc are not added) */
+  float *dgi, *dgh;              /* [B, G H] out: d loss / d gi, d gh (equal but for the GRU's n block: dgh_n = dgi_n r) */
+  int32_t B, H, type, pad_;
+} Go2nnRnnCellBwdJob;
+int go2nn_rnn_cell_forward(const Go2nnRnnCellJob* jobs, int32_t njobs, void* stream);
+int go2nn_rnn_cell_backward(const Go2nnRnnCellBwdJob* jobs, int32_t njobs, void* stream);
+/* The reset of the rollout (actor_critic_recurrent.py Memory.reset: hidden_state[..., dones, :] = 0): rows r with done[r] != 0 of up to 4 state tensors [L, B, H]
+ * set to 0, one launch, no host read of done (capturable). */
+#define GO2NN_RNN_MAX_STATES 4
+int go2nn_rnn_reset(float* const* states, int32_t nstates, int32_t L, int32_t B, int32_t H, const uint8_t* done, void* stream);
 
 #ifdef __cplusplus
 }
