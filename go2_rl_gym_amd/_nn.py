@@ -12,6 +12,10 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 NN_LIB = os.path.join(_HERE, "libgo2nn_hip.so")
 GO2NN_MAX_LAYERS, GO2NN_MAX_WIDTH, GO2NN_ABI_VERSION, GO2NN_MAX_GROUP = 6, 512, 7, 2
 GO2NN_RNN_LSTM, GO2NN_RNN_GRU, GO2NN_RNN_MAX_STATES = 0, 1, 4
+# the evaluator's accumulators, in the order of the enum GO2NN_EVAL_* of include/go2nn.h (where the formulas are)
+EVAL_METRICS = ("steps", "lin_vel_err", "ang_vel_err", "speed_along_cmd", "tilt", "power", "torque_sq", "action_rate_sq", "dof_limit_steps", "falls")
+GO2NN_EVAL_NUM = len(EVAL_METRICS)
+EVAL_FIELDS = ("commands", "base_lin_vel", "base_ang_vel", "projected_gravity", "dof_state", "torques", "actions", "last_actions", "reset_buf", "time_out_buf")
 _cached = None
 
 
@@ -64,6 +68,14 @@ class Go2nnRnnCellBwdJob(C.Structure):       # ABI 7
                [(k, C.c_int32) for k in ("B", "H", "type", "pad_")]
 
 
+class Go2nnEvalField(C.Structure):          # (within ABI 7) strides in elements
+    _fields_ = [("p", C.c_void_p), ("env_stride", C.c_int32), ("comp_stride", C.c_int32)]
+
+
+class Go2nnEvalIn(C.Structure):
+    _fields_ = [(k, Go2nnEvalField) for k in EVAL_FIELDS] + [("dof_limits", C.c_void_p), ("dof_vel_offset", C.c_int32), ("dt", C.c_float)]
+
+
 def bind(path):
     lib = C.CDLL(path)
     lib.go2nn_last_error.restype = C.c_char_p
@@ -108,6 +120,9 @@ def bind(path):
     lib.go2nn_rnn_cell_forward.argtypes = [C.POINTER(Go2nnRnnCellJob), C.c_int32, C.c_void_p]
     lib.go2nn_rnn_cell_backward.argtypes = [C.POINTER(Go2nnRnnCellBwdJob), C.c_int32, C.c_void_p]
     lib.go2nn_rnn_reset.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.go2nn_eval_clear.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+    lib.go2nn_eval_accumulate.argtypes = [C.POINTER(Go2nnEvalIn), C.c_void_p, C.c_int32, C.c_void_p]
+    lib.go2nn_eval_reduce.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
     if lib.go2nn_abi_version() != GO2NN_ABI_VERSION:
         raise RuntimeError("%s: ABI version %d, expected %d" % (path, lib.go2nn_abi_version(), GO2NN_ABI_VERSION))
     return lib

@@ -1226,3 +1226,4 @@ int go2nn_moe_mix_forward(const float* logits, const float* outs, const float* b
 }  // extern "C"
 
 #include "go2nn_rnn.h"          // ABI 7: the recurrent memory's cell steps
+#include "go2nn_eval.h"         // (within ABI 7) the policy evaluator's metric accumulation and per-group reduction

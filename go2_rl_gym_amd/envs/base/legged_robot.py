@@ -25,6 +25,8 @@ _REWARD_KEY_ALIASES = {"feet_stumble": "stumble"}
 
 
 class LeggedRobot(BaseTask):
+    _terrain_prebuilt = None      # a utils.terrain.Terrain to use instead of generating one (utils/evaluator.py recreates its simulator per evaluation and keeps the terrain on the host)
+
     def __init__(self, cfg: LeggedRobotCfg, sim_params, physics_engine, sim_device, headless, lib=None, env_offset=0, num_envs_global=None):
         self.cfg = cfg
         self.sim_params = sim_params
@@ -77,7 +79,7 @@ class LeggedRobot(BaseTask):
         elif mesh in ("heightfield", "trimesh"):
             # create_sim (:292-310): the Terrain is built on the host; the library copies the int16 samples to HBM at create.
             from ...utils.terrain import Terrain
-            self.terrain = Terrain(cfg.terrain, c.num_envs_global)
+            self.terrain = self._terrain_prebuilt if self._terrain_prebuilt is not None else Terrain(cfg.terrain, c.num_envs_global)
             hs = np.ascontiguousarray(self.terrain.heightsamples, dtype=np.int16)
             org = np.ascontiguousarray(self.terrain.env_origins, dtype=np.float32)
             ids = np.ascontiguousarray(self.terrain.cols2id, dtype=np.int32)

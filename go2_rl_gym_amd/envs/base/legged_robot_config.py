@@ -264,6 +264,19 @@ class LeggedRobotCfgPPO(BaseConfig):
         enabled = False
         port = 9973
 
+    class evaluation:
+        """the native policy evaluator (utils/evaluator.py) in the slot of the reference's RoboGauge call: off by default"""
+        enabled = False
+        interval = 500          # iterations between two evaluations (the reference's RoboGauge cadence); the last model is always evaluated
+        num_envs = 1024
+        seconds = 10.0          # counted horizon
+        warmup_s = 1.0          # uncounted steps after the reset
+        terrain_level = 5       # row of the terrain grid every robot stands on (heightfield / trimesh tasks)
+        seed = 12345
+        replay = False          # True: from an evaluator's second evaluation on, capture one chunk of steps into a HIP graph and replay it (measured slower than eager: DESIGN.md 9)
+        scenarios = [["forward_1.0", 1.0, 0.0, 0.0], ["forward_2.0", 2.0, 0.0, 0.0], ["backward_1.0", -1.0, 0.0, 0.0], ["lateral_0.5", 0.0, 0.5, 0.0],
+                     ["turn_1.0", 0.0, 0.0, 1.0], ["stand", 0.0, 0.0, 0.0]]          # name, vx [m/s], vy [m/s], yaw rate [rad/s]
+
 
 class LeggedRobotCfgCTS(BaseConfig):
     """Concurrent Teacher-Student training (legged_robot_config.py:309-359)."""
@@ -313,6 +326,19 @@ class LeggedRobotCfgCTS(BaseConfig):
     class robogauge:
         enabled = False
         port = 9973
+
+    class evaluation:
+        """the native policy evaluator (utils/evaluator.py) in the slot of the reference's RoboGauge call: off by default"""
+        enabled = False
+        interval = 500          # iterations between two evaluations (the reference's RoboGauge cadence); the last model is always evaluated
+        num_envs = 1024
+        seconds = 10.0          # counted horizon
+        warmup_s = 1.0          # uncounted steps after the reset
+        terrain_level = 5       # row of the terrain grid every robot stands on (heightfield / trimesh tasks)
+        seed = 12345
+        replay = False          # True: from an evaluator's second evaluation on, capture one chunk of steps into a HIP graph and replay it (measured slower than eager: DESIGN.md 9)
+        scenarios = [["forward_1.0", 1.0, 0.0, 0.0], ["forward_2.0", 2.0, 0.0, 0.0], ["backward_1.0", -1.0, 0.0, 0.0], ["lateral_0.5", 0.0, 0.5, 0.0],
+                     ["turn_1.0", 0.0, 0.0, 1.0], ["stand", 0.0, 0.0, 0.0]]          # name, vx [m/s], vy [m/s], yaw rate [rad/s]
 
 
 class LeggedRobotCfgMoECTS(LeggedRobotCfgCTS):

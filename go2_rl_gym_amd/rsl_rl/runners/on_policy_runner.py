@@ -4,7 +4,8 @@ console / scalar names, fps = num_steps_per_env * num_envs / (collection_time + 
 
 Differences that do not change results: the per-step `.cpu()` bookkeeping of the reference (:143-153, a host sync every
 env step) is replaced by device-side buffers read once per iteration; RoboGauge (:103-111,252-295, an external HTTP
-service) is out of scope; with torch.distributed initialised only rank 0 logs and saves.
+service) is out of scope — its call site in save() (:243-250) runs the native policy evaluator instead (update_evaluation; utils/evaluator.py), when the train config's
+`evaluation` section enables it; with torch.distributed initialised only rank 0 logs, saves and evaluates.
 """
 import os
 import statistics
@@ -109,6 +110,10 @@ class OnPolicyRunner:
         self.tot_time = 0
         self.current_learning_iteration = 0
         self.last_fps = None
+        # the native policy evaluator (utils/evaluator.py), created on first use by update_evaluation; nothing exists while `evaluation.enabled` is False.
+        # evaluator_kwargs: extra PolicyEvaluator arguments (tests hand in host libraries)
+        self.eval_cfg = train_cfg.get("evaluation") or {}
+        self.evaluator, self.evaluator_kwargs, self.last_evaluation = None, {}, None
         self.last_collection_time = self.last_learn_time = None
         on_gpu = str(device).startswith("cuda") and getattr(getattr(env, "lib", None), "go2sim_is_device_library", lambda: 0)() == 1
         if on_gpu:
@@ -364,6 +369,38 @@ class OnPolicyRunner:
     def save(self, path, it=None, last_model=False, infos=None):
         torch.save({"model_state_dict": self.alg.actor_critic.state_dict(), "optimizer_state_dict": self.alg.optimizer.state_dict(),
                     "iter": self.current_learning_iteration, "infos": infos}, path)
+        self.update_evaluation(it, last_model)
+
+    def update_evaluation(self, it, last_model=False):
+        """Where the reference calls update_robogauge (on_policy_runner.py:250,252-295): every `evaluation.interval` iterations and for the last model the current weights are
+        scored by the native evaluator; the figures go to the writer as Eval/<metric> and Eval/<terrain>/<scenario>/<metric> and to eval_results/results_{n}.yaml under the
+        log dir (n = the iteration; for the last model the number its checkpoint file carries).  -> the result dict, or None when nothing was evaluated."""
+        ev = self.eval_cfg
+        if not ev.get("enabled", False) or it is None or _rank() != 0:
+            return None
+        if not (last_model or it % max(int(ev.get("interval", 500)), 1) == 0):
+            return None
+        from ...utils import evaluator as E
+        label = self.current_learning_iteration if last_model else it
+        if last_model and self.last_evaluation is not None and self.last_evaluation[0] == it:
+            res = self.last_evaluation[1]          # the last iteration was evaluated a moment ago and nothing has been updated since
+        else:
+            if self.evaluator is None:
+                kw = dict(self.evaluator_kwargs)
+                if self.lib is not None and self.lib.go2sim_is_device_library() != 1:
+                    kw.setdefault("lib", self.lib)
+                self.evaluator = E.PolicyEvaluator(self.env.cfg, ev, task_class=type(self.env), sim_params=self.env.sim_params, device=self.env.sim_device, **kw)
+            res = self.evaluator.evaluate(self.alg.actor_critic)
+            self.last_evaluation = (it, res)
+        if self.writer is not None:
+            for tag, v in E.scalars(res):
+                self.writer.add_scalar(tag, v, label)
+        if self.log_dir is not None:
+            E.write_results(self.log_dir, label, res)
+        o = res["overall"]
+        print("[evaluation] iteration %s: lin_vel_err %.3f m/s, ang_vel_err %.3f rad/s, survival %.3f over %d robots x %d steps (%s)"
+              % (label, o["lin_vel_err"], o["ang_vel_err"], o["survival"], o["n_envs"], res["steps"], res["mode"]))
+        return res
 
     def load(self, path, load_optimizer=True):
         d = torch.load(path, map_location=self.device)

@@ -4,7 +4,8 @@ history the student encoder consumes, teacher/student episode statistics and the
 The history ring [N, 5, 45] lives in one persistent device buffer updated IN PLACE by the library kernel
 go2sim_history_push (zero finished envs, drop the oldest frame, append the new observation — :155-156) instead of a boolean
 index write + torch.cat allocation per step; that also makes the whole 24-step rollout capturable in one HIP graph, exactly
-like the PPO runner's.  RoboGauge (:103-111,271-330, an external HTTP evaluation service) is out of scope."""
+like the PPO runner's.  RoboGauge (:103-111,271-330, an external HTTP evaluation service) is out of scope; save() runs the native evaluator in its place
+(OnPolicyRunner.update_evaluation: the student path is what gets scored)."""
 import ctypes as C
 from collections import deque
 
@@ -106,6 +107,7 @@ class OnPolicyRunnerCTS(OnPolicyRunner):
     def save(self, path, it=None, last_model=False, infos=None):
         torch.save({"model_state_dict": self.alg.model.state_dict(), "optimizer1_state_dict": self.alg.optimizer1.state_dict(),
                     "optimizer2_state_dict": self.alg.optimizer2.state_dict(), "iter": self.current_learning_iteration, "infos": infos}, path)
+        self.update_evaluation(it, last_model)          # (on_policy_runner_cts.py: the twin of the PPO runner's call site)
 
     def load(self, path, load_optimizer=True):
         d = torch.load(path, map_location=self.device)

@@ -1,0 +1,70 @@
+"""python -m go2_rl_gym_amd.scripts.evaluate --task go2_flat [--load_run RUN --checkpoint N] [--all_checkpoints --metric lin_vel_err]
+
+Loads a checkpoint of the task's experiment through the runner (like scripts/play.py), scores it with the native policy evaluator (utils/evaluator.py; the train
+config's `evaluation` section sets robots, horizon and scenarios), prints the per-terrain, per-command table and one JSON line.  --all_checkpoints walks every
+model_*.pt of the run and names the best one by --metric (lower is better for the error / effort metrics, higher for survival and speed_along_cmd)."""
+import json
+import os
+import sys
+from pathlib import Path
+
+from go2_rl_gym_amd.envs import *  # noqa: F401,F403
+from go2_rl_gym_amd.utils import get_args
+from go2_rl_gym_amd.utils.evaluator import PolicyEvaluator, format_table
+from go2_rl_gym_amd.utils.helpers import _checkpoint_number, get_load_path
+from go2_rl_gym_amd.utils.task_registry import ROOT_DIR, task_registry
+
+HIGHER_IS_BETTER = ("survival", "speed_along_cmd")
+
+
+def _own_flags(argv):
+    """--all_checkpoints / --metric / --eval_envs belong to this script; the rest is the common CLI"""
+    own = {"all_checkpoints": False, "metric": "lin_vel_err", "eval_envs": None}
+    rest, k = [], 0
+    while k < len(argv):
+        a = argv[k]
+        if a == "--all_checkpoints":
+            own["all_checkpoints"] = True
+        elif a in ("--metric", "--eval_envs"):
+            own[a[2:]] = argv[k + 1] if a == "--metric" else int(argv[k + 1])
+            k += 1
+        else:
+            rest.append(a)
+        k += 1
+    return own, rest
+
+
+def evaluate(argv=None, log_root="default"):
+    own, rest = _own_flags(list(sys.argv[1:] if argv is None else argv))
+    args = get_args(rest)
+    env_cfg, train_cfg = task_registry.get_cfgs(name=args.task)
+    env_cfg.env.num_envs = min(env_cfg.env.num_envs, 64)          # the runner's own env only carries the model's shapes here; the evaluator brings its own simulator
+    env_cfg.env.test = True
+    env, _ = task_registry.make_env(name=args.task, args=args, env_cfg=env_cfg)
+    train_cfg.runner.resume = True
+    runner, train_cfg = task_registry.make_alg_runner(env=env, name=args.task, args=args, train_cfg=train_cfg, log_root=log_root)
+    root = os.path.join(ROOT_DIR, "logs", train_cfg.runner.experiment_name) if log_root == "default" else log_root
+    first = get_load_path(root, load_run=train_cfg.runner.load_run, checkpoint=train_cfg.runner.checkpoint)
+    paths = sorted(Path(first).parent.glob("model_*.pt"), key=_checkpoint_number) if own["all_checkpoints"] else [Path(first)]
+    ev_cfg = dict(runner.eval_cfg)
+    if own["eval_envs"] is not None:
+        ev_cfg["num_envs"] = own["eval_envs"]
+    ev = PolicyEvaluator(env.cfg, ev_cfg, task_class=type(env), sim_params=env.sim_params, device=env.sim_device, **runner.evaluator_kwargs)
+    rows = []
+    for p in paths:
+        runner.load(str(p), load_optimizer=False)
+        res = ev.evaluate(runner.alg.actor_critic)
+        print("== %s (%s)\n%s" % (p.name, res["mode"], format_table(res)))
+        rows.append({"checkpoint": p.name, "overall": res["overall"], "groups": res["groups"]})
+    metric = own["metric"]
+    key = lambda r: r["overall"][metric]
+    best = (max if metric in HIGHER_IS_BETTER else min)(rows, key=key)
+    out = {"task": args.task, "metric": metric, "best": best["checkpoint"], "best_value": key(best), "checkpoints": rows}
+    print(json.dumps(out))
+    ev.close()
+    env.close()
+    return out
+
+
+if __name__ == "__main__":
+    evaluate()

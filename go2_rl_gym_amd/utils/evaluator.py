@@ -1,0 +1,458 @@
+"""PolicyEvaluator — on-device evaluation of a policy on a fixed, noise-free scenario set, with per-terrain, per-command scores.
+
+It takes the slot the reference fills with RoboGauge (rsl_rl/rsl_rl/runners/on_policy_runner.py:103-111,243-295: every `interval` iterations and for the last model the
+checkpoint is scored, the scores go to TensorBoard and to a results yaml).  RoboGauge itself (an HTTP service in front of MuJoCo) stays out of scope;
+the numbers here are measured in THIS project's physics and are not comparable to the reference's RoboGauge table.
+
+One evaluation = a simulator of its own (never the training env), reset, `warmup_s` of uncounted steps, `seconds` of counted steps of
+    { write the commands, policy (deterministic mean), go2sim_step, go2nn_eval_accumulate }
+then ONE go2nn_eval_reduce and ONE device -> host copy of its [groups, 12] fp64 table — the only synchronisation.  The metric formulas are in include/go2nn.h.
+
+Reproducible: the simulator's random stream is indexed by a step count that the go2sim ABI does not rewind, so every evaluate() builds a FRESH simulator from the same
+config and seed (the generated terrain is kept on the host, which makes that cheap): the same weights give bit-identical numbers.  For the same reason a captured HIP graph
+belongs to one evaluation.  With `evaluation.replay` the first evaluate() of an evaluator runs eagerly and later ones capture ONE chunk of steps on their fresh simulator
+and replay it for the whole horizon, bit-identical to the eager run; GO2_STRICT_GRAPHS=1 makes a failed capture raise, as elsewhere.  It is OFF by default because it
+measured slower: capture + instantiation per evaluation cost more than the ~500 eager enqueues they replace (profiles/eval_bench.json).
+
+Isolated: nothing of the training env, the model, the optimizer or torch's generators is written; policy state the evaluation needs (the CTS observation history, the
+recurrent memory's hidden state) lives in buffers of the evaluator."""
+import copy
+import ctypes as C
+import math
+import os
+
+import numpy as np
+import torch
+
+from .. import _abi
+from .._nn import EVAL_FIELDS, EVAL_METRICS, GO2NN_EVAL_NUM, GO2NN_RNN_GRU, GO2NN_RNN_LSTM, Go2nnEvalIn, Go2nnFwdJob, Go2nnMlpIO, Go2nnRnnCellJob, PackedMlp
+from .helpers import class_to_dict
+
+DEFAULT_SCENARIOS = [["forward_1.0", 1.0, 0.0, 0.0], ["forward_2.0", 2.0, 0.0, 0.0], ["backward_1.0", -1.0, 0.0, 0.0], ["lateral_0.5", 0.0, 0.5, 0.0],
+                     ["turn_1.0", 0.0, 0.0, 1.0], ["stand", 0.0, 0.0, 0.0]]
+MEAN_METRICS = EVAL_METRICS[1:9]          # reported as per-step means; `falls` per robot, `survival`, `n_envs` next to them
+RESULT_KEYS = MEAN_METRICS + ("falls", "survival", "n_envs")
+MAX_CHUNK = 50
+# The accumulate kernel runs AFTER the env step, when the simulator has already rolled its action history (last_actions = this step's actions): the previous step's
+# actions — the kernel's `last_actions` input — are then in the simulator's last_last_actions buffer.
+EVAL_SOURCE = {"last_actions": "last_last_actions"}
+
+
+def _get(section, key, default=None):
+    return section.get(key, default) if isinstance(section, dict) else getattr(section, key, default)
+
+
+def evaluation_env_cfg(env_cfg, ev):
+    """The task's env config as the evaluation runs it: scripts/play.py's edits (noise, pushes and every domain randomisation off, no terrain curriculum, env.test) plus
+    commands that hold — no resampling inside the horizon, no heading controller, no command curricula — and the evaluation's own seed and size."""
+    cfg = copy.deepcopy(env_cfg)
+    horizon = float(_get(ev, "warmup_s", 1.0)) + float(_get(ev, "seconds", 10.0))
+    cfg.env.num_envs = int(_get(ev, "num_envs", 1024))
+    cfg.env.test = True
+    cfg.env.episode_length_s = max(float(cfg.env.episode_length_s), horizon + 1.0)          # no time-out resets inside the horizon
+    cfg.seed = int(_get(ev, "seed", 12345))
+    cfg.noise.add_noise = False
+    cfg.terrain.curriculum = False
+    dr = cfg.domain_rand
+    for k in dir(dr):
+        if k.startswith("randomize_"):
+            setattr(dr, k, False)
+    dr.push_robots = False
+    cm = cfg.commands
+    cm.resampling_time = 10.0 * horizon + 1000.0
+    cm.heading_command = False
+    cm.curriculum = False
+    cm.dynamic_resample_commands = False
+    cm.command_range_curriculum = []
+    cm.zero_command_curriculum = None
+    return cfg
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------------------------------
+# The policy side: the deterministic action mean of the three model families, on the go2nn kernels, with every piece of recurrent state owned here.
+class _Policy:
+    def __init__(self, ev, model):
+        self.ev, self.model = ev, model
+
+    def _stream(self):
+        return self.ev._stream()
+
+    def _check(self, rc, what):
+        if rc != 0:
+            raise RuntimeError("%s failed: %s" % (what, self.ev.nn.go2nn_last_error().decode()))
+
+    def begin(self, obs):
+        """once per evaluation, after the reset: read the CURRENT weights (packed images are rebuilt here, so an evaluation after an update never sees stale ones)"""
+
+    def act(self, obs):
+        raise NotImplementedError
+
+    def after_step(self, obs, dones_u8):
+        pass
+
+
+class _MlpPolicy(_Policy):
+    """ActorCritic: actions = actor(obs), one launch (go2nn_mlp_forward on the packed weights)"""
+
+    def __init__(self, ev, model):
+        super().__init__(ev, model)
+        self.actor = PackedMlp(ev.nn, model.actor)
+
+    def begin(self, obs):
+        self.actor.pack()
+
+    def act(self, obs):
+        return self.actor.forward(obs)
+
+
+class _CtsPolicy(_Policy):
+    """The CTS family's deployment path (modules/actor_critic_cts.py act_inference): student encoder on the observation history -> normalised latent -> actor([latent | obs]).
+    The history ring is the evaluator's (go2sim_history_push, as the CTS runner keeps its own).  A plain Linear / ELU student encoder with an L2 normaliser and the base class's
+    actor run as two go2nn_mlp_forward_rows launches; the other members of the family (mixture encoders, mixture actors) run their modules' own inference formulation."""
+
+    def __init__(self, ev, model):
+        super().__init__(ev, model)
+        from ..rsl_rl.modules.actor_critic_cts import ActorCriticCTS
+        from ..rsl_rl.modules.fused_cts import mlp_linears
+        N, dev = ev.num_envs, ev.device
+        self.H, self.D = model.history_length, model.num_actor_obs
+        self.history = torch.zeros(N, self.H, self.D, device=dev)
+        t = type(model)
+        enc = mlp_linears(model.student_encoder, norm=True) if (t.student_latent is ActorCriticCTS.student_latent and hasattr(model, "student_encoder")) else None
+        act = mlp_linears(model.actor) if (t.policy_mean is ActorCriticCTS.policy_mean and hasattr(model, "actor")) else None
+        self.kernels = enc is not None and act is not None and act[0].in_features == enc[-1].out_features + self.D
+        if self.kernels:
+            self.enc, self.actor = PackedMlp(ev.nn, None, linears=enc), PackedMlp(ev.nn, None, linears=act)
+            self.L = enc[-1].out_features
+            self.latent = torch.zeros(N, self.L, device=dev)
+
+    def _push(self, obs, dones_u8):
+        lib = self.ev.env.lib
+        rc = lib.go2sim_history_push(C.c_void_p(self.history.data_ptr()), C.c_void_p(obs.data_ptr()), C.c_void_p(dones_u8.data_ptr()) if dones_u8 is not None else None,
+                                     self.ev.num_envs, self.H, self.D, self._stream())
+        if rc != 0:
+            raise RuntimeError("go2sim_history_push failed: %s" % lib.go2sim_last_error().decode())
+
+    def begin(self, obs):
+        self.history.zero_()
+        self._push(obs, None)
+        if self.kernels:
+            self.enc.pack(); self.actor.pack()
+
+    def _rows(self, net, io):
+        descs = (C.POINTER(type(net.desc)) * 1)(C.pointer(net.desc))
+        packed = (C.c_void_p * 1)(net.packed.data_ptr())
+        self._check(self.ev.nn.go2nn_mlp_forward_rows(descs, packed, (Go2nnMlpIO * 1)(io), 1, self._stream()), "go2nn_mlp_forward_rows")
+
+    def act(self, obs):
+        N = self.ev.num_envs
+        hist = self.history.view(N, self.H * self.D)
+        if not self.kernels:
+            return self.model.policy_mean(self.model.student_latent(hist)[0], obs).contiguous()
+        A = self.actor.out_dim
+        actions = torch.empty(N, A, device=obs.device)
+        self._rows(self.enc, Go2nnMlpIO(hist.data_ptr(), None, None, self.latent.data_ptr(), self.H * self.D, 0, self.H * self.D, N, self.L, 1))
+        self._rows(self.actor, Go2nnMlpIO(self.latent.data_ptr(), obs.data_ptr(), None, actions.data_ptr(), self.L, obs.shape[1], self.L, N, A, 0))
+        return actions
+
+    def after_step(self, obs, dones_u8):
+        self._push(obs, dones_u8)
+
+
+class _RecurrentPolicy(_Policy):
+    """ActorCriticRecurrent: the actor's memory (LSTM / GRU) on the library's cell kernels with a hidden state of the evaluator's own — zero at the start, zeroed on dones —,
+    then the actor MLP.  Per layer: gi and gh as one grouped product launch (fp32-MFMA kernels: no split image to keep in step with the weights), one cell launch."""
+
+    def __init__(self, ev, model):
+        super().__init__(ev, model)
+        from ..rsl_rl.modules.fused_rnn import _layers, check_shape
+        mem = model.memory_a
+        check_shape(mem)
+        self.lstm, self.layers = mem.is_lstm, _layers(mem)
+        L, H = mem.rnn.num_layers, mem.rnn.hidden_size
+        self.h = torch.zeros(L, ev.num_envs, H, device=ev.device)
+        self.c = torch.zeros_like(self.h) if self.lstm else None
+        self.actor = PackedMlp(ev.nn, model.actor)
+
+    def begin(self, obs):
+        self.h.zero_()
+        if self.c is not None:
+            self.c.zero_()
+        self.actor.pack()
+
+    def act(self, obs):
+        nn_, N = self.ev.nn, self.ev.num_envs
+        G = 4 if self.lstm else 3
+        x = obs
+        for l, (ih, hh) in enumerate(self.layers):
+            H = self.h.shape[2]
+            gi, gh = torch.empty(N, G * H, device=obs.device), torch.empty(N, G * H, device=obs.device)
+            for xin, lin, out in ((x, ih, gi), (self.h[l], hh, gh)):
+                job = Go2nnFwdJob(xin.data_ptr(), lin.weight.data_ptr(), lin.bias.data_ptr(), out.data_ptr(), N, lin.in_features, lin.out_features, 1, None)
+                self._check(nn_.go2nn_linear_elu_forward_group((Go2nnFwdJob * 1)(job), 1, self._stream()), "go2nn_linear_elu_forward_group")
+            h, c = self.h[l], (self.c[l] if self.lstm else None)
+            p = lambda t: t.data_ptr() if t is not None else None
+            job = Go2nnRnnCellJob(p(gi), p(gh), p(h), p(c), p(h), p(c), None, None, None, None, None, None, None, None, N, H, GO2NN_RNN_LSTM if self.lstm else GO2NN_RNN_GRU, 0)
+            self._check(nn_.go2nn_rnn_cell_forward((Go2nnRnnCellJob * 1)(job), 1, self._stream()), "go2nn_rnn_cell_forward")
+            x = h
+        return self.actor.forward(x)
+
+    def after_step(self, obs, dones_u8):
+        sts = [self.h] + ([self.c] if self.lstm else [])
+        L, N, H = self.h.shape
+        arr = (C.c_void_p * len(sts))(*[s.data_ptr() for s in sts])
+        self._check(self.ev.nn.go2nn_rnn_reset(arr, len(sts), L, N, H, C.c_void_p(dones_u8.data_ptr()), self._stream()), "go2nn_rnn_reset")
+
+
+def _make_policy(ev, model):
+    from ..rsl_rl.modules import ActorCritic, ActorCriticRecurrent
+    from ..rsl_rl.modules.actor_critic_cts import ActorCriticCTS
+    if isinstance(model, ActorCriticRecurrent):
+        return _RecurrentPolicy(ev, model)
+    if isinstance(model, ActorCriticCTS):
+        return _CtsPolicy(ev, model)
+    if isinstance(model, ActorCritic):
+        return _MlpPolicy(ev, model)
+    raise TypeError("PolicyEvaluator: no evaluation path for %s (ActorCritic, ActorCriticRecurrent and the ActorCriticCTS family are covered)" % type(model).__name__)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------------------------------
+class PolicyEvaluator:
+    def __init__(self, env_cfg, evaluation, task_class=None, sim_params=None, device="cuda:0", lib=None, nn_lib=None, step_callback=None):
+        """env_cfg: the task's env config (copied, never modified);  evaluation: the train config's `evaluation` section (class or dict).
+        lib / nn_lib: the go2sim / go2nn libraries — tests hand in the CPU oracle and the host build; the product passes neither and runs on the HIP libraries or not at all.
+        step_callback(evaluator, step, counted): called after every eager step with the buffers the accumulate kernel has just read (tests record them)."""
+        from ..envs.base.legged_robot import LeggedRobot
+        self.ev = evaluation
+        self.cfg = evaluation_env_cfg(env_cfg, evaluation)
+        self.task_class = task_class or LeggedRobot
+        self.sim_params = sim_params
+        self._lib, self.device_arg = lib, device
+        self.step_callback = step_callback
+        self.scenarios = [list(s) for s in (_get(evaluation, "scenarios") or DEFAULT_SCENARIOS)]
+        self.terrain_level = int(_get(evaluation, "terrain_level", 5))
+        self.num_envs = self.cfg.env.num_envs
+        self.env = self._terrain = None
+        self._make_env()
+        self.device = self.env.device
+        self.on_device = self.env.lib.go2sim_is_device_library() == 1
+        if nn_lib is None:
+            if not self.on_device:
+                raise RuntimeError("PolicyEvaluator on a host simulator library needs the go2nn host build passed as nn_lib (tests only)")
+            from .._nn import load_nn
+            nn_lib = load_nn()
+        self.nn = nn_lib
+        self.dt = float(self.env.dt)
+        self.warmup_steps = int(round(float(_get(evaluation, "warmup_s", 1.0)) / self.dt))
+        self.steps = max(1, int(round(float(_get(evaluation, "seconds", 10.0)) / self.dt)))
+        g = math.gcd(self.warmup_steps, self.steps)
+        self.chunk = max(d for d in range(1, min(g, MAX_CHUNK) + 1) if g % d == 0)
+        self._build_groups()
+        N = self.num_envs
+        self.acc = torch.zeros(GO2NN_EVAL_NUM, N, device=self.device)
+        self.out = torch.zeros(len(self.groups), GO2NN_EVAL_NUM + 2, dtype=torch.float64, device=self.device)
+        self.dof_limits = self.env.dof_pos_limits.contiguous().clone()
+        self._policy, self._policy_of = None, None
+        self.evaluations = 0
+        self.last_mode = None          # "eager" / "graph": how the latest evaluation's steps ran
+
+    # ------------------------------------------------------------------ the simulator of one evaluation
+    def _make_env(self):
+        """a fresh simulator in the evaluation's initial state: same config, same seed, same (host-resident) terrain"""
+        if self.env is not None:
+            self.env.close()
+        if self.cfg.terrain.mesh_type != "plane" and self._terrain is None:
+            from .terrain import Terrain
+            state = np.random.get_state()          # the terrain generators draw from numpy's global stream: seed it for the evaluation, hand it back untouched
+            np.random.seed(self.cfg.seed)
+            tcfg = copy.deepcopy(self.cfg.terrain)
+            tcfg.curriculum = True                 # the LAYOUT by terrain kind (columns by terrain_proportions, rows by difficulty); nothing moves between levels (below)
+            self._terrain = Terrain(tcfg, self.num_envs)
+            np.random.set_state(state)
+        sp = self.sim_params
+        if sp is None:
+            from .helpers import SimParams
+            sim = class_to_dict(self.cfg.sim)
+            sp = SimParams(dt=sim.get("dt", 0.005), substeps=sim.get("substeps", 1), gravity=sim.get("gravity", (0.0, 0.0, -9.81)))
+        cls = type("_Eval" + self.task_class.__name__, (self.task_class,), {"_terrain_prebuilt": self._terrain})
+        kw = {} if self._lib is None else {"lib": self._lib}
+        self.env = cls(cfg=self.cfg, sim_params=sp, physics_engine=1, sim_device=self.device_arg, headless=True, **kw)
+        env = self.env
+        if env.custom_origins:          # every env at the evaluation's terrain level, in the column the simulator gave it
+            lv = min(max(self.terrain_level, 0), self.cfg.terrain.num_rows - 1)
+            env.terrain_levels.fill_(lv)
+            env.env_origins.copy_(env.terrain_origins[lv, env.terrain_types])
+
+    def _build_groups(self):
+        """env -> (terrain kind x scenario) group, built once on the host: the kinds are those of the columns the envs stand in (one kind, 'plane', without a terrain mesh);
+        within a kind the envs take the scenarios in turn, so the groups of a kind differ by at most one env"""
+        from .terrain import KIND_NAMES
+        N, S = self.num_envs, len(self.scenarios)
+        if self.env.custom_origins:
+            kind_of_env = self.env.terrain_cols2id.cpu().numpy()[self.env.terrain_types.cpu().numpy()]
+            kinds = [int(k) for k in sorted(set(kind_of_env.tolist()))]
+            self.terrain_names = [KIND_NAMES[k] if 0 <= k < len(KIND_NAMES) else "kind_%d" % k for k in kinds]
+        else:
+            kind_of_env, kinds, self.terrain_names = np.zeros(N, np.int64), [0], ["plane"]
+        group = np.zeros(N, np.int32)
+        scen = np.zeros(N, np.int64)
+        for ki, k in enumerate(kinds):
+            ids = np.nonzero(kind_of_env == k)[0]
+            scen[ids] = np.arange(len(ids)) % S
+            group[ids] = ki * S + scen[ids]
+        self.groups = [(t, s[0]) for t in self.terrain_names for s in self.scenarios]
+        self.group_host = group
+        self.group = torch.from_numpy(group).to(self.device)
+        cmd = np.zeros((N, 4), np.float32)
+        cmd[:, :3] = np.asarray([s[1:4] for s in self.scenarios], np.float32)[scen]
+        self.commands_host = cmd
+        self.commands = torch.from_numpy(cmd).to(self.device)
+
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream) if self.on_device else None
+
+    def _check(self, rc, what):
+        if rc != 0:
+            raise RuntimeError("%s failed: %s" % (what, self.nn.go2nn_last_error().decode()))
+
+    def _eval_in(self):
+        """the accumulate kernel's view of the simulator's buffers: (pointer, env stride, component stride) in elements from the torch views' own strides"""
+        env, a = self.env, Go2nnEvalIn()
+        b = env._buf
+        for name in EVAL_FIELDS:
+            t = b[EVAL_SOURCE.get(name, name)]
+            f = getattr(a, name)
+            f.p, f.env_stride, f.comp_stride = t.data_ptr(), t.stride(0), (t.stride(1) if t.dim() > 1 else 0)
+        a.dof_vel_offset = b["dof_state"].stride(2)
+        a.dof_limits, a.dt = self.dof_limits.data_ptr(), self.dt
+        return a
+
+    # ------------------------------------------------------------------ one env step of the evaluation (pure enqueue)
+    def _step(self, pol, ein):
+        env = self.env
+        actions = pol.act(env.obs_buf)
+        _abi.check(env.lib, env.lib.go2sim_step(env.handle, C.c_void_p(actions.data_ptr()), self._stream()), "go2sim_step")
+        env.commands.copy_(self.commands)          # a robot that fell was reset by the step and drew a new command: the scenario's command holds
+        self._check(self.nn.go2nn_eval_accumulate(C.byref(ein), C.c_void_p(self.acc.data_ptr()), self.num_envs, self._stream()), "go2nn_eval_accumulate")
+        pol.after_step(env.obs_buf, env._buf["reset_buf"])
+
+    def _clear(self):
+        self._check(self.nn.go2nn_eval_clear(C.c_void_p(self.acc.data_ptr()), self.num_envs, self._stream()), "go2nn_eval_clear")
+
+    def _run_eager(self, pol, ein):
+        for k in range(self.warmup_steps + self.steps):
+            if k == self.warmup_steps:
+                self._clear()
+            self._step(pol, ein)
+            if self.step_callback is not None:
+                self.step_callback(self, k, k >= self.warmup_steps)
+
+    def _run_graph(self, pol, ein):
+        """capture `chunk` steps on this evaluation's simulator, replay them for the whole horizon -> False if the capture failed (nothing has run then)"""
+        from ..rsl_rl.algorithms._graph import no_gc, strict_graphs
+        torch.cuda.synchronize(self.device)
+        g = torch.cuda.CUDAGraph()
+        try:
+            with no_gc(), torch.cuda.graph(g):
+                for _ in range(self.chunk):
+                    self._step(pol, ein)
+        except Exception as e:      # noqa: BLE001
+            if strict_graphs():
+                raise RuntimeError("HIP-graph capture of the evaluation failed (%s: %s)" % (type(e).__name__, e)) from e
+            print("[go2_rl_gym_amd] HIP-graph capture of the evaluation failed (%s: %s); evaluating eagerly" % (type(e).__name__, e))
+            torch.cuda.synchronize(self.device)
+            return False
+        for k in range(0, self.warmup_steps + self.steps, self.chunk):
+            if k == self.warmup_steps:
+                self._clear()
+            g.replay()
+            self.env.lib.go2sim_notify_replayed(self.env.handle, self.chunk)
+        self._graph = g          # alive until the results have been read
+        return True
+
+    # ------------------------------------------------------------------ the public call
+    def evaluate(self, actor_critic, use_graph=None):
+        """-> {"overall": {...}, "groups": {terrain: {scenario: {...}}}, "terrain_names", "scenarios", "steps", "dt", "mode"}; every leaf dict has RESULT_KEYS.
+        use_graph: None = eager, or with `evaluation.replay` eager the first time and a captured chunk afterwards (on the GPU); True / False force it."""
+        with torch.inference_mode():
+            if self.evaluations > 0:
+                self._make_env()
+            if self._policy_of is not actor_critic:
+                self._policy, self._policy_of = _make_policy(self, actor_critic), actor_critic
+            pol, env = self._policy, self.env
+            _abi.check(env.lib, env.lib.go2sim_reset_all(env.handle, self._stream()), "go2sim_reset_all")
+            env.commands.copy_(self.commands)
+            zero = torch.zeros(self.num_envs, env.num_actions, device=self.device)
+            _abi.check(env.lib, env.lib.go2sim_step(env.handle, C.c_void_p(zero.data_ptr()), self._stream()), "go2sim_step")          # BaseTask.reset: the first observations
+            env.commands.copy_(self.commands)
+            pol.begin(env.obs_buf)
+            self._clear()
+            ein = self._eval_in()
+            replay = bool(_get(self.ev, "replay", False))
+            graph = (replay and self.on_device and self.evaluations > 0 and self.step_callback is None) if use_graph is None else bool(use_graph and self.on_device)
+            done = graph and self._run_graph(pol, ein)
+            if not done:
+                self._run_eager(pol, ein)
+            self.last_mode = "graph" if done else "eager"
+            self._check(self.nn.go2nn_eval_reduce(C.c_void_p(self.acc.data_ptr()), C.c_void_p(self.group.data_ptr()), self.num_envs, len(self.groups),
+                                                  C.c_void_p(self.out.data_ptr()), self._stream()), "go2nn_eval_reduce")
+            table = self.out.cpu().numpy().copy()          # the one device -> host copy (and synchronisation) of an evaluation
+            self._graph = None
+            self.evaluations += 1
+        return self._results(table)
+
+    @staticmethod
+    def _row(r):
+        """one row of the reduce table (sums of the ten accumulators, envs, envs without a fall) -> the reported figures; an empty group reports NaN (as episode_info does)"""
+        n, steps = float(r[GO2NN_EVAL_NUM]), float(r[0])
+        d = {m: (float(r[1 + i]) / steps if steps > 0 else float("nan")) for i, m in enumerate(MEAN_METRICS)}
+        d["falls"] = float(r[EVAL_METRICS.index("falls")]) / n if n > 0 else float("nan")
+        d["survival"] = float(r[GO2NN_EVAL_NUM + 1]) / n if n > 0 else float("nan")
+        d["n_envs"] = int(n)
+        return d
+
+    def _results(self, table):
+        S = len(self.scenarios)
+        groups = {t: {s[0]: self._row(table[ti * S + si]) for si, s in enumerate(self.scenarios)} for ti, t in enumerate(self.terrain_names)}
+        return {"overall": self._row(table.sum(0)), "groups": groups, "terrain_names": list(self.terrain_names), "scenarios": [s[0] for s in self.scenarios],
+                "steps": self.steps, "dt": self.dt, "mode": self.last_mode, "table": table}
+
+    def close(self):
+        if self.env is not None:
+            self.env.close()
+            self.env = None
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------------------------------
+def scalars(res):
+    """[(tag, value)]: 'Eval/<metric>' for the overall figures, 'Eval/<terrain>/<scenario>/<metric>' per group"""
+    out = [("Eval/" + k, res["overall"][k]) for k in RESULT_KEYS]
+    for t, per in res["groups"].items():
+        for s, d in per.items():
+            out += [("Eval/%s/%s/%s" % (t, s, k), d[k]) for k in RESULT_KEYS]
+    return out
+
+
+def results_dict(res, it=None):
+    """what eval_results/results_{it}.yaml holds (plain Python numbers)"""
+    d = {"iteration": it, "steps": res["steps"], "dt": res["dt"], "overall": dict(res["overall"]), "groups": {t: {s: dict(v) for s, v in per.items()} for t, per in res["groups"].items()}}
+    return d
+
+
+def format_table(res):
+    cols = ("lin_vel_err", "ang_vel_err", "speed_along_cmd", "tilt", "power", "falls", "survival", "n_envs")
+    lines = ["%-16s %-14s " % ("terrain", "scenario") + " ".join("%15s" % c for c in cols)]
+    rows = [(t, s, d) for t, per in res["groups"].items() for s, d in per.items()] + [("all", "all", res["overall"])]
+    for t, s, d in rows:
+        lines.append("%-16s %-14s " % (t, s) + " ".join("%15.4f" % d[c] if c != "n_envs" else "%15d" % d[c] for c in cols))
+    return "\n".join(lines)
+
+
+def write_results(log_dir, it, res):
+    import yaml
+    path = os.path.join(log_dir, "eval_results")
+    os.makedirs(path, exist_ok=True)
+    out = os.path.join(path, "results_%s.yaml" % it)
+    with open(out, "w") as f:
+        yaml.safe_dump(results_dict(res, it), f)
+    return out

@@ -279,6 +279,44 @@ int go2nn_rnn_cell_backward(const Go2nnRnnCellBwdJob* jobs, int32_t njobs, void*
 #define GO2NN_RNN_MAX_STATES 4
 int go2nn_rnn_reset(float* const* states, int32_t nstates, int32_t L, int32_t B, int32_t H, const uint8_t* done, void* stream);
 
+/* ---- the policy evaluator's metrics (go2_rl_gym_amd/utils/evaluator.py; the slot the reference fills with RoboGauge, rsl_rl/rsl_rl/runners/on_policy_runner.py:103-111,243-295).
+ * ADDED WITHIN ABI 7: three new entry points, nothing existing changes, GO2NN_ABI_VERSION stays 7.
+ * An evaluation is { policy, go2sim_step, go2nn_eval_accumulate } per env step and one go2nn_eval_reduce at the end; all three calls are plain launches (capturable).
+ *
+ * go2nn_eval_accumulate adds, per env e and step, to acc[m, e] (acc: fp32 [GO2NN_EVAL_NUM, N], metric-major, read-modify-written in place; one lane per env, no atomics):
+ *   STEPS            1
+ *   LIN_VEL_ERR      |cmd_xy - v_xy|_2                       v = base_lin_vel (base frame), cmd = commands
+ *   ANG_VEL_ERR      |cmd_yaw - w_z|                         w = base_ang_vel, cmd_yaw = commands[2]
+ *   SPEED_ALONG_CMD  v_xy . cmd_xy / |cmd_xy|                0 when |cmd_xy| < 1e-6
+ *   TILT             sqrt(g_x^2 + g_y^2)                     g = projected_gravity
+ *   POWER            sum_j |tau_j qd_j|                      tau = torques, qd = joint velocities (dof_state[..., 1])
+ *   TORQUE_SQ        sum_j tau_j^2
+ *   ACTION_RATE_SQ   sum_j (a_j - a_j^prev)^2                a = actions, a^prev = last_actions
+ *   DOF_LIMIT_STEPS  1 if any joint position q_j < dof_limits[j][0] or > dof_limits[j][1]
+ *   FALLS            1 if reset_buf and not time_out_buf
+ * Every input is a Go2SimBuffers field described by (pointer, env stride, component stride) in ELEMENTS, so the same kernel reads the HIP simulator's field-major buffers
+ * (go2sim_buffer_layout() == 1: env stride 1, component stride N — consecutive lanes read consecutive addresses) and row-major ones (layout 0: env stride = row length,
+ * component stride 1).  dof_state [N,12,2]: comp_stride is the stride between JOINTS and dof_vel_offset the distance from a joint's position to its velocity (row-major:
+ * 2 and 1; field-major: N and 12 N).  reset_buf / time_out_buf are uint8.  dof_limits: [12,2] floats in the buffers' memory space.  dt (the policy step) is carried for
+ * the consumer that turns per-step sums into per-second figures; the accumulators are per-step sums and do not use it. */
+enum {
+  GO2NN_EVAL_STEPS = 0, GO2NN_EVAL_LIN_VEL_ERR, GO2NN_EVAL_ANG_VEL_ERR, GO2NN_EVAL_SPEED_ALONG_CMD, GO2NN_EVAL_TILT, GO2NN_EVAL_POWER, GO2NN_EVAL_TORQUE_SQ,
+  GO2NN_EVAL_ACTION_RATE_SQ, GO2NN_EVAL_DOF_LIMIT_STEPS, GO2NN_EVAL_FALLS, GO2NN_EVAL_NUM
+};
+typedef struct Go2nnEvalField { const void* p; int32_t env_stride; int32_t comp_stride; } Go2nnEvalField;
+typedef struct Go2nnEvalIn {
+  Go2nnEvalField commands, base_lin_vel, base_ang_vel, projected_gravity, dof_state, torques, actions, last_actions, reset_buf, time_out_buf;
+  const float* dof_limits;
+  int32_t dof_vel_offset;
+  float dt;
+} Go2nnEvalIn;
+int go2nn_eval_clear(float* acc, int32_t N, void* stream);          /* acc[GO2NN_EVAL_NUM, N] = 0 */
+int go2nn_eval_accumulate(const Go2nnEvalIn* in, float* acc, int32_t N, void* stream);
+/* out [G, GO2NN_EVAL_NUM + 2] (fp64): per group g the sums over the envs e with group[e] == g of the ten accumulators, then the number of such envs, then the number of them
+ * with acc[FALLS, e] == 0.  Group ids outside [0, G) are ignored; an empty group gives a row of zeros.  Every sum is formed in an order that depends on (N, G) only — 256
+ * strided fp64 partials, then a fixed tree; no floating-point atomics —, so equal inputs give bit-equal outputs.  1 <= G <= 65535. */
+int go2nn_eval_reduce(const float* acc, const int32_t* group, int32_t N, int32_t G, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

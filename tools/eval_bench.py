@@ -1,0 +1,106 @@
+"""What one policy evaluation costs (utils/evaluator.py), and what the metric kernel saves over torch expressions.
+
+    python tools/eval_bench.py [--task go2_flat] [--reps 3] [--out profiles/eval_bench.json]
+
+Measures, on cuda:0, with the task's default `evaluation` section (1024 robots, 1 s + 10 s):
+  * wall time of evaluate() run eagerly and with the captured chunk of steps replayed (simulator re-creation, capture and the final host copy included: it is what
+    the training loop waits for), best and median of --reps;
+  * go2nn_eval_accumulate per launch, from device events around 200 back-to-back launches on the evaluator's own buffers (for the kernel's own duration run this tool
+    under `rocprofv3 --kernel-trace --stats -- python tools/eval_bench.py --kernel_only` and read go2nn_eval_accumulate_kernel);
+  * the same ten per-step terms written as torch expressions on the same (strided) buffers, per step, eager and replayed from a HIP graph.
+Writes one JSON file and prints it."""
+import argparse
+import ctypes as C
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import torch  # noqa: E402
+
+from go2_rl_gym_amd.envs import task_registry  # noqa: E402
+from go2_rl_gym_amd.utils.evaluator import EVAL_SOURCE, PolicyEvaluator  # noqa: E402
+from go2_rl_gym_amd.utils.helpers import class_to_dict  # noqa: E402
+
+
+def torch_metrics(b, lim, acc):
+    """the table of include/go2nn.h as torch expressions on the simulator's buffer views, accumulated into acc [10, N]"""
+    c, v = b["commands"], b["base_lin_vel"]
+    cn = torch.sqrt(c[:, 0] ** 2 + c[:, 1] ** 2)
+    q, qd, tau = b["dof_state"][:, :, 0], b["dof_state"][:, :, 1], b["torques"]
+    acc[0] += 1.0
+    acc[1] += torch.sqrt((c[:, 0] - v[:, 0]) ** 2 + (c[:, 1] - v[:, 1]) ** 2)
+    acc[2] += (c[:, 2] - b["base_ang_vel"][:, 2]).abs()
+    acc[3] += torch.where(cn < 1e-6, torch.zeros_like(cn), (v[:, 0] * c[:, 0] + v[:, 1] * c[:, 1]) / cn.clamp_min(1e-6))
+    acc[4] += torch.sqrt(b["projected_gravity"][:, 0] ** 2 + b["projected_gravity"][:, 1] ** 2)
+    acc[5] += (tau * qd).abs().sum(1)
+    acc[6] += (tau * tau).sum(1)
+    acc[7] += ((b["actions"] - b[EVAL_SOURCE["last_actions"]]) ** 2).sum(1)
+    acc[8] += ((q < lim[:, 0]) | (q > lim[:, 1])).any(1).float()
+    acc[9] += (b["reset_buf"].bool() & ~b["time_out_buf"].bool()).float()
+
+
+def timed(fn, n):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    e0.record()
+    for _ in range(n):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) * 1e3 / n, (time.perf_counter() - t0) * 1e6 / n          # device us, wall us per call
+
+
+def main():
+    p = argparse.ArgumentParser()
+    p.add_argument("--task", default="go2_flat")
+    p.add_argument("--reps", type=int, default=3)
+    p.add_argument("--kernel_only", action="store_true")
+    p.add_argument("--out", default=os.path.join(ROOT, "profiles", "eval_bench.json"))
+    a = p.parse_args()
+    env_cfg, train_cfg = task_registry.get_cfgs(a.task)
+    ev = PolicyEvaluator(env_cfg, class_to_dict(train_cfg.evaluation), task_class=task_registry.get_task_class(a.task), device="cuda:0")
+    from go2_rl_gym_amd.rsl_rl.modules import ActorCritic
+    torch.manual_seed(0)
+    ac = ActorCritic(45, 263, 12, **{k: v for k, v in class_to_dict(train_cfg.policy).items() if k in ("actor_hidden_dims", "critic_hidden_dims", "activation", "init_noise_std")}).to("cuda:0")
+    out = {"task": a.task, "device": torch.cuda.get_device_name(0), "num_envs": ev.num_envs, "steps": ev.warmup_steps + ev.steps, "chunk": ev.chunk}
+    ev.evaluate(ac, use_graph=False)
+    ein, st = ev._eval_in(), ev._stream()
+    acc_fn = lambda: ev.nn.go2nn_eval_accumulate(C.byref(ein), C.c_void_p(ev.acc.data_ptr()), ev.num_envs, st)
+    timed(acc_fn, 20)
+    dev_us, wall_us = timed(acc_fn, 200)
+    out["accumulate_kernel"] = {"device_us_per_launch_back_to_back": dev_us, "host_us_per_call": wall_us}
+    if not a.kernel_only:
+        walls = {"eager": [], "replayed": []}
+        for _ in range(a.reps):
+            for mode, g in (("eager", False), ("replayed", True)):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                res = ev.evaluate(ac, use_graph=g)
+                walls[mode].append((time.perf_counter() - t0) * 1e3)
+                assert res["mode"] == ("graph" if g else "eager")
+        out["evaluate_wall_ms"] = {m: {"best": min(w), "median": statistics.median(w)} for m, w in walls.items()}
+        b, lim, acc = ev.env._buf, ev.dof_limits, torch.zeros_like(ev.acc)
+        tm = lambda: torch_metrics(b, lim, acc)
+        timed(tm, 5)
+        d_e, w_e = timed(tm, 50)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            tm()
+        timed(g.replay, 5)
+        d_g, w_g = timed(g.replay, 50)
+        out["torch_expressions_per_step"] = {"eager_device_us": d_e, "eager_host_us": w_e, "replayed_device_us": d_g, "replayed_host_us": w_g}
+        os.makedirs(os.path.dirname(a.out), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(out, f, indent=1)
+    print(json.dumps(out))
+    ev.close()
+
+
+if __name__ == "__main__":
+    main()
