@@ -16,6 +16,15 @@ GO2NN_RNN_LSTM, GO2NN_RNN_GRU, GO2NN_RNN_MAX_STATES = 0, 1, 4
 EVAL_METRICS = ("steps", "lin_vel_err", "ang_vel_err", "speed_along_cmd", "tilt", "power", "torque_sq", "action_rate_sq", "dof_limit_steps", "falls")
 GO2NN_EVAL_NUM = len(EVAL_METRICS)
 EVAL_FIELDS = ("commands", "base_lin_vel", "base_ang_vel", "projected_gravity", "dof_state", "torques", "actions", "last_actions", "reset_buf", "time_out_buf")
+# the trajectory recorder's frame: (block, floats) in the order of the enum GO2NN_TRACE_* of include/go2nn.h (the one specification; tests/test_trace_host.py holds this
+# table to it), and the source buffers of Go2nnTraceIn in the struct's order
+TRACE_BLOCKS = (("root_pos", 3), ("root_quat", 4), ("root_lin_vel", 3), ("root_ang_vel", 3), ("dof_pos", 12), ("dof_vel", 12), ("torques", 12), ("actions", 12),
+                ("commands", 3), ("base_lin_vel", 3), ("base_ang_vel", 3), ("projected_gravity", 3), ("foot_pos", 12), ("foot_vel", 12), ("foot_force", 12),
+                ("reward", 1), ("reset", 1), ("time_out", 1))
+GO2NN_TRACE_WIDTH = sum(w for _, w in TRACE_BLOCKS)
+TRACE_OFFSET = {name: sum(w for _, w in TRACE_BLOCKS[:i]) for i, (name, _) in enumerate(TRACE_BLOCKS)}
+TRACE_FIELDS = ("root_states", "dof_state", "torques", "actions", "commands", "base_lin_vel", "base_ang_vel", "projected_gravity", "rigid_body_states", "contact_forces",
+                "rew_buf", "reset_buf", "time_out_buf")
 _cached = None
 
 
@@ -76,6 +85,26 @@ class Go2nnEvalIn(C.Structure):
     _fields_ = [(k, Go2nnEvalField) for k in EVAL_FIELDS] + [("dof_limits", C.c_void_p), ("dof_vel_offset", C.c_int32), ("dt", C.c_float)]
 
 
+class Go2nnTraceIn(C.Structure):          # (within ABI 7)
+    _fields_ = [(k, Go2nnEvalField) for k in TRACE_FIELDS] + [("dof_vel_offset", C.c_int32), ("rigid_body_stride", C.c_int32), ("contact_body_stride", C.c_int32),
+                                                              ("foot_body", C.c_int32 * 4), ("pad_", C.c_int32)]
+
+
+def trace_env_ids(env_ids, num_envs):
+    """the tracked robots of go2nn_trace_record as the kernel needs them -> int32 numpy [K], strictly increasing, each in [0, num_envs).  The kernel cannot report a bad
+    index (it would read outside the buffers), so anything else raises here."""
+    import numpy as np
+    ids = env_ids.detach().cpu().numpy() if torch.is_tensor(env_ids) else np.asarray(env_ids)
+    if ids.ndim != 1 or ids.size < 1 or ids.dtype.kind not in "iu":
+        raise ValueError("env_ids: a non-empty 1-d sequence of integers is needed, got %r" % (env_ids,))
+    ids = ids.astype(np.int64)
+    if ids.min() < 0 or ids.max() >= int(num_envs):
+        raise ValueError("env_ids outside [0, %d): %s" % (num_envs, ids.tolist()))
+    if (np.diff(ids) <= 0).any():
+        raise ValueError("env_ids must be strictly increasing: %s" % ids.tolist())
+    return np.ascontiguousarray(ids, np.int32)
+
+
 def bind(path):
     lib = C.CDLL(path)
     lib.go2nn_last_error.restype = C.c_char_p
@@ -123,6 +152,8 @@ def bind(path):
     lib.go2nn_eval_clear.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
     lib.go2nn_eval_accumulate.argtypes = [C.POINTER(Go2nnEvalIn), C.c_void_p, C.c_int32, C.c_void_p]
     lib.go2nn_eval_reduce.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.go2nn_trace_record.argtypes = [C.POINTER(Go2nnTraceIn), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+    lib.go2nn_trace_clear.argtypes = [C.c_void_p, C.c_void_p]
     if lib.go2nn_abi_version() != GO2NN_ABI_VERSION:
         raise RuntimeError("%s: ABI version %d, expected %d" % (path, lib.go2nn_abi_version(), GO2NN_ABI_VERSION))
     return lib

@@ -274,6 +274,7 @@ class LeggedRobotCfgPPO(BaseConfig):
         terrain_level = 5       # row of the terrain grid every robot stands on (heightfield / trimesh tasks)
         seed = 12345
         replay = False          # True: from an evaluator's second evaluation on, capture one chunk of steps into a HIP graph and replay it (measured slower than eager: DESIGN.md 9)
+        record = 0              # robots per (terrain x scenario) group whose per-step frames are recorded (utils/recorder.py -> eval_results/trace_<it>.npz); 0: no recorder exists
         scenarios = [["forward_1.0", 1.0, 0.0, 0.0], ["forward_2.0", 2.0, 0.0, 0.0], ["backward_1.0", -1.0, 0.0, 0.0], ["lateral_0.5", 0.0, 0.5, 0.0],
                      ["turn_1.0", 0.0, 0.0, 1.0], ["stand", 0.0, 0.0, 0.0]]          # name, vx [m/s], vy [m/s], yaw rate [rad/s]
 
@@ -337,6 +338,7 @@ class LeggedRobotCfgCTS(BaseConfig):
         terrain_level = 5       # row of the terrain grid every robot stands on (heightfield / trimesh tasks)
         seed = 12345
         replay = False          # True: from an evaluator's second evaluation on, capture one chunk of steps into a HIP graph and replay it (measured slower than eager: DESIGN.md 9)
+        record = 0              # robots per (terrain x scenario) group whose per-step frames are recorded (utils/recorder.py -> eval_results/trace_<it>.npz); 0: no recorder exists
         scenarios = [["forward_1.0", 1.0, 0.0, 0.0], ["forward_2.0", 2.0, 0.0, 0.0], ["backward_1.0", -1.0, 0.0, 0.0], ["lateral_0.5", 0.0, 0.5, 0.0],
                      ["turn_1.0", 0.0, 0.0, 1.0], ["stand", 0.0, 0.0, 0.0]]          # name, vx [m/s], vy [m/s], yaw rate [rad/s]
 

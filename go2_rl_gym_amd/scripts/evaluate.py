@@ -2,7 +2,8 @@
 
 Loads a checkpoint of the task's experiment through the runner (like scripts/play.py), scores it with the native policy evaluator (utils/evaluator.py; the train
 config's `evaluation` section sets robots, horizon and scenarios), prints the per-terrain, per-command table and one JSON line.  --all_checkpoints walks every
-model_*.pt of the run and names the best one by --metric (lower is better for the error / effort metrics, higher for survival and speed_along_cmd)."""
+model_*.pt of the run and names the best one by --metric (lower is better for the error / effort metrics, higher for survival and speed_along_cmd).
+--record N also records N robots of every (terrain x scenario) group and writes eval_results/trace_<checkpoint number>.npz into the run's directory."""
 import json
 import os
 import sys
@@ -56,6 +57,9 @@ def evaluate(argv=None, log_root="default"):
         res = ev.evaluate(runner.alg.actor_critic)
         print("== %s (%s)\n%s" % (p.name, res["mode"], format_table(res)))
         rows.append({"checkpoint": p.name, "overall": res["overall"], "groups": res["groups"]})
+        if res.get("trace") is not None:
+            from go2_rl_gym_amd.utils.recorder import write_trace
+            print("trace: %s" % write_trace(os.path.join(str(p.parent), "eval_results", "trace_%s.npz" % _checkpoint_number(p)), res["trace"]))
     metric = own["metric"]
     key = lambda r: r["overall"][metric]
     best = (max if metric in HIGHER_IS_BETTER else min)(rows, key=key)

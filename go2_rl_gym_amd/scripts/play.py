@@ -1,7 +1,10 @@
 """python -m go2_rl_gym_amd.scripts.play --task go2_flat  (legged_gym/scripts/play.py:15-62, headless).
 
 Loads the latest checkpoint of the task's experiment through the runner, exports the deployment policy
-(TorchScript / pkl, and ONNX when the `onnx` package is present) and rolls it out with a fixed 1 m/s command."""
+(TorchScript / pkl, and ONNX when the `onnx` package is present) and rolls it out with a fixed 1 m/s command.
+
+--record N [--record_steps S]: the first N envs are recorded on the device (utils/recorder.py: one small kernel call per step, no host read), the last S steps (default
+500) go to <log root>/exported/traces/play_<task>.npz and a one-line gait summary per robot is printed.  Without the flag nothing of this exists."""
 import os
 
 import torch
@@ -43,6 +46,10 @@ def play(args, steps=None, log_root="default", export_policy=None):
             print("ONNX export skipped:", type(e).__name__, e)
         print("Exported policy to: ", path)
     n = steps if steps is not None else 10 * int(env.max_episode_length)
+    recorder = None
+    if getattr(args, "record", None):
+        from go2_rl_gym_amd.utils.recorder import TrajectoryRecorder
+        recorder = TrajectoryRecorder(env, range(min(int(args.record), env.num_envs)), max(1, min(int(getattr(args, "record_steps", None) or 500), n)))
     with torch.inference_mode():
         for _ in range(n):
             actions = policy(obs.detach())
@@ -51,6 +58,15 @@ def play(args, steps=None, log_root="default", export_policy=None):
                 env.commands[:, 1] = 0.0
                 env.commands[:, 2] = 0.0
             obs, _, rews, dones, infos = env.step(actions.detach())
+            if recorder is not None:
+                recorder.record()
+    if recorder is not None:
+        from go2_rl_gym_amd.utils.recorder import format_gait, write_trace
+        root = os.path.join(ROOT_DIR, "logs", train_cfg.runner.experiment_name) if log_root == "default" else log_root
+        trace = recorder.fetch()
+        env.trace_path = write_trace(os.path.join(root, "exported", "traces", "play_%s.npz" % args.task), trace)          # where a caller of play() finds the file
+        print("Recorded %d steps of %d robots to: %s" % (trace["frames"].shape[0], trace["frames"].shape[1], env.trace_path))
+        print("\n".join(format_gait(trace)))
     return env, exported
 
 

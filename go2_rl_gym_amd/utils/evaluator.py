@@ -14,6 +14,10 @@ belongs to one evaluation.  With `evaluation.replay` the first evaluate() of an 
 and replay it for the whole horizon, bit-identical to the eager run; GO2_STRICT_GRAPHS=1 makes a failed capture raise, as elsewhere.  It is OFF by default because it
 measured slower: capture + instantiation per evaluation cost more than the ~500 eager enqueues they replace (profiles/eval_bench.json).
 
+Looking at the motion: with `evaluation.record = r > 0` a TrajectoryRecorder (utils/recorder.py) keeps the per-step frames of the first r robots of every group over the
+counted steps — one more kernel call per step, after the accumulate call and inside the captured chunk —, evaluate() returns them as res["trace"] and write_results puts
+them next to the yaml as trace_<it>.npz.  The scores do not depend on it (the recorder only reads); with record = 0 no recorder exists.
+
 Isolated: nothing of the training env, the model, the optimizer or torch's generators is written; policy state the evaluation needs (the CTS observation history, the
 recurrent memory's hidden state) lives in buffers of the evaluator."""
 import copy
@@ -253,6 +257,12 @@ class PolicyEvaluator:
         self.out = torch.zeros(len(self.groups), GO2NN_EVAL_NUM + 2, dtype=torch.float64, device=self.device)
         self.dof_limits = self.env.dof_pos_limits.contiguous().clone()
         self._policy, self._policy_of = None, None
+        self.recorder = None
+        per_group = int(_get(evaluation, "record", 0) or 0)
+        if per_group > 0:          # the first `record` env indices of every group, for the counted steps
+            from .recorder import TrajectoryRecorder
+            ids = np.sort(np.concatenate([np.nonzero(self.group_host == g)[0][:per_group] for g in range(len(self.groups))]))
+            self.recorder = TrajectoryRecorder(self.env, ids, self.steps, nn_lib=self.nn)
         self.evaluations = 0
         self.last_mode = None          # "eager" / "graph": how the latest evaluation's steps ran
 
@@ -334,10 +344,14 @@ class PolicyEvaluator:
         _abi.check(env.lib, env.lib.go2sim_step(env.handle, C.c_void_p(actions.data_ptr()), self._stream()), "go2sim_step")
         env.commands.copy_(self.commands)          # a robot that fell was reset by the step and drew a new command: the scenario's command holds
         self._check(self.nn.go2nn_eval_accumulate(C.byref(ein), C.c_void_p(self.acc.data_ptr()), self.num_envs, self._stream()), "go2nn_eval_accumulate")
+        if self.recorder is not None:
+            self.recorder.record()
         pol.after_step(env.obs_buf, env._buf["reset_buf"])
 
     def _clear(self):
         self._check(self.nn.go2nn_eval_clear(C.c_void_p(self.acc.data_ptr()), self.num_envs, self._stream()), "go2nn_eval_clear")
+        if self.recorder is not None:
+            self.recorder.clear()
 
     def _run_eager(self, pol, ein):
         for k in range(self.warmup_steps + self.steps):
@@ -373,6 +387,8 @@ class PolicyEvaluator:
     # ------------------------------------------------------------------ the public call
     def evaluate(self, actor_critic, use_graph=None):
         """-> {"overall": {...}, "groups": {terrain: {scenario: {...}}}, "terrain_names", "scenarios", "steps", "dt", "mode"}; every leaf dict has RESULT_KEYS.
+        With `evaluation.record` also "trace": TrajectoryRecorder.fetch() of the counted steps plus "group_of_robot" (index into terrain_names x scenarios, terrain-major,
+        per tracked robot), "terrain_names" and "scenarios".
         use_graph: None = eager, or with `evaluation.replay` eager the first time and a captured chunk afterwards (on the GPU); True / False force it."""
         with torch.inference_mode():
             if self.evaluations > 0:
@@ -386,6 +402,8 @@ class PolicyEvaluator:
             _abi.check(env.lib, env.lib.go2sim_step(env.handle, C.c_void_p(zero.data_ptr()), self._stream()), "go2sim_step")          # BaseTask.reset: the first observations
             env.commands.copy_(self.commands)
             pol.begin(env.obs_buf)
+            if self.recorder is not None:
+                self.recorder.bind(env)
             self._clear()
             ein = self._eval_in()
             replay = bool(_get(self.ev, "replay", False))
@@ -397,9 +415,14 @@ class PolicyEvaluator:
             self._check(self.nn.go2nn_eval_reduce(C.c_void_p(self.acc.data_ptr()), C.c_void_p(self.group.data_ptr()), self.num_envs, len(self.groups),
                                                   C.c_void_p(self.out.data_ptr()), self._stream()), "go2nn_eval_reduce")
             table = self.out.cpu().numpy().copy()          # the one device -> host copy (and synchronisation) of an evaluation
+            trace = self.recorder.fetch() if self.recorder is not None else None
             self._graph = None
             self.evaluations += 1
-        return self._results(table)
+        res = self._results(table)
+        if trace is not None:
+            trace.update(group_of_robot=self.group_host[trace["env_ids"]].copy(), terrain_names=list(self.terrain_names), scenarios=[s[0] for s in self.scenarios])
+            res["trace"] = trace
+        return res
 
     @staticmethod
     def _row(r):
@@ -455,4 +478,7 @@ def write_results(log_dir, it, res):
     out = os.path.join(path, "results_%s.yaml" % it)
     with open(out, "w") as f:
         yaml.safe_dump(results_dict(res, it), f)
+    if res.get("trace") is not None:
+        from .recorder import write_trace
+        write_trace(os.path.join(path, "trace_%s.npz" % it), res["trace"])
     return out

@@ -317,6 +317,41 @@ int go2nn_eval_accumulate(const Go2nnEvalIn* in, float* acc, int32_t N, void* st
  * strided fp64 partials, then a fixed tree; no floating-point atomics —, so equal inputs give bit-equal outputs.  1 <= G <= 65535. */
 int go2nn_eval_reduce(const float* acc, const int32_t* group, int32_t N, int32_t G, double* out, void* stream);
 
+/* ---- the trajectory recorder (go2_rl_gym_amd/utils/recorder.py): per-step frames of chosen robots, kept on the device.
+ * ADDED WITHIN ABI 7: two new entry points, nothing existing changes, GO2NN_ABI_VERSION stays 7.
+ * A FRAME is GO2NN_TRACE_WIDTH floats of one robot after one env step; every column is a plain copy of a simulator buffer (no arithmetic; the uint8 flags become 0.0 / 1.0).
+ * This enum is the one specification of the frame: column offset of each block, the block's length being the distance to the next one.
+ *   ROOT_POS 3, ROOT_QUAT 4 (xyzw), ROOT_LIN_VEL 3, ROOT_ANG_VEL 3 (world; root_states[0:13])     DOF_POS 12, DOF_VEL 12 (dof_state[..., 0 / 1])     TORQUES 12, ACTIONS 12
+ *   COMMANDS 3 (vx, vy, yaw rate)     BASE_LIN_VEL 3, BASE_ANG_VEL 3, PROJECTED_GRAVITY 3 (base frame)
+ *   FOOT_POS 4 x 3, FOOT_VEL 4 x 3 (world; rigid_body_states[foot_body[f], 0:3 / 7:10])     FOOT_FORCE 4 x 3 (world; contact_forces[foot_body[f]])
+ *   REWARD 1 (rew_buf), RESET 1 (reset_buf), TIME_OUT 1 (time_out_buf) */
+enum {
+  GO2NN_TRACE_ROOT_POS = 0, GO2NN_TRACE_ROOT_QUAT = 3, GO2NN_TRACE_ROOT_LIN_VEL = 7, GO2NN_TRACE_ROOT_ANG_VEL = 10, GO2NN_TRACE_DOF_POS = 13, GO2NN_TRACE_DOF_VEL = 25,
+  GO2NN_TRACE_TORQUES = 37, GO2NN_TRACE_ACTIONS = 49, GO2NN_TRACE_COMMANDS = 61, GO2NN_TRACE_BASE_LIN_VEL = 64, GO2NN_TRACE_BASE_ANG_VEL = 67,
+  GO2NN_TRACE_PROJECTED_GRAVITY = 70, GO2NN_TRACE_FOOT_POS = 73, GO2NN_TRACE_FOOT_VEL = 85, GO2NN_TRACE_FOOT_FORCE = 97, GO2NN_TRACE_REWARD = 109, GO2NN_TRACE_RESET = 110,
+  GO2NN_TRACE_TIME_OUT = 111, GO2NN_TRACE_WIDTH = 112
+};
+/* The sources, each as (pointer, env stride, component stride) in ELEMENTS like Go2nnEvalIn's, so field-major and row-major buffers are read unchanged.  dof_state: as in
+ * Go2nnEvalIn (comp_stride between joints, dof_vel_offset from a position to its velocity).  rigid_body_states [N, bodies, 13] and contact_forces [N, bodies, 3]: comp_stride
+ * is the stride between the COMPONENTS of one body and *_body_stride the stride between bodies; foot_body names the four foot bodies.  rew_buf is fp32, reset_buf and
+ * time_out_buf are uint8 (comp_stride unused, may be 0). */
+typedef struct Go2nnTraceIn {
+  Go2nnEvalField root_states, dof_state, torques, actions, commands, base_lin_vel, base_ang_vel, projected_gravity, rigid_body_states, contact_forces, rew_buf, reset_buf,
+      time_out_buf;
+  int32_t dof_vel_offset;
+  int32_t rigid_body_stride;
+  int32_t contact_body_stride;
+  int32_t foot_body[4];
+  int32_t pad_;
+} Go2nnTraceIn;
+/* frames: fp32 [T, K, GO2NN_TRACE_WIDTH] row-major, a ring of T steps;  env_ids: int32 [K], strictly increasing, each in [0, N) (the caller's duty: the kernel cannot check
+ * it);  cursor: ONE int32 in the buffers' memory space = frames recorded since the last clear.  The call writes the frame of every tracked robot to slot (*cursor) % T and
+ * then adds 1 to *cursor: the slot is read from the cursor by the kernel, never passed by the host, so a captured launch lands in a new slot on every replay.  Two plain
+ * launches on `stream` (the frame kernel, one lane per output float; then one lane that advances the cursor), no atomics.  After c calls the ring holds the steps
+ * max(0, c - T) .. c - 1, step s in slot s % T. */
+int go2nn_trace_record(const Go2nnTraceIn* in, const int32_t* env_ids, int32_t K, float* frames, int32_t* cursor, int32_t T, void* stream);
+int go2nn_trace_clear(int32_t* cursor, void* stream);          /* *cursor = 0; the frames are left as they are */
+
 #ifdef __cplusplus
 }
 #endif
