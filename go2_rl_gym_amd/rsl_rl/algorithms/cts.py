@@ -14,17 +14,10 @@ import itertools
 import os
 
 import torch
-import torch.distributed as dist
-import torch.nn as nn
-import torch.optim as optim
 
 from ..storage import RolloutStorageCTS
-from ._graph import CapturedStep, FusedClipAdam, GradBucket, ReducedStep, all_captured
-from .ppo import _ADAM_IMPL, _RANDPERM, _collectives_on, _FusedPPOLoss, _RolloutHeads, _world, allreduce_mean_bucket
-
-
-def _allreduce_mean_grads(params, world, extra=None):
-    return allreduce_mean_bucket([p.grad for p in params if p.grad is not None], world, extra)
+from ._base import _RANDPERM, _FusedPPOLoss, _RolloutHeads, _collectives_on, _world
+from ._graph import CapturedStep, GradBucket, all_captured
 
 
 class CTS(_RolloutHeads):
@@ -32,36 +25,19 @@ class CTS(_RolloutHeads):
                  value_loss_coef=1.0, entropy_coef=0.0, learning_rate=1e-3, student_encoder_learning_rate=1e-3, max_grad_norm=1.0,
                  use_clipped_value_loss=True, schedule="fixed", desired_kl=0.01, teacher_env_ratio=0.75, device="cpu", lib=None,
                  use_graphs=None, fused_loss=None, fused_rollout=None):
-        self.device, self.lib = device, lib
         self.desired_kl, self.schedule, self.learning_rate = desired_kl, schedule, learning_rate
         self.history_length = history_length
         self.model = model
-        self.model.to(self.device)
+        self.model.to(device)
         self.storage = None
-        on_gpu = str(device).startswith("cuda")
-        self.use_graphs = on_gpu if use_graphs is None else bool(use_graphs and on_gpu)
-        self._capture = self.use_graphs and use_graphs != "uncaptured"
-        if use_graphs == "uncaptured":     # the graph-mode update run eagerly on any device (CPU tests), see PPO
-            self.use_graphs = True
-        self.fused_loss = (on_gpu and lib is not None) if fused_loss is None else bool(fused_loss and lib is not None)
-        self.fused_rollout = (on_gpu and lib is not None) if fused_rollout is None else bool(fused_rollout and lib is not None)
+        self._init_modes(device, lib, learning_rate, use_graphs, fused_loss, fused_rollout)
         if getattr(model, "state_dependent_std", False):       # MCP actor: the fused heads assume one std per action dimension
             self.fused_loss = self.fused_rollout = False
-        if on_gpu and lib is not None and os.environ.get("GO2_FUSED_MLP", "1") == "1":
-            from ..modules import fused
-            fused.set_library(lib)
         groups1 = [{"params": g} for g in self.model.policy_parameter_groups()]                           # same 4 groups as the reference (:72-77)
         self._params1 = list(itertools.chain.from_iterable(g["params"] for g in groups1))
         self._params2 = list(self.model.student_parameters())
-        if self.use_graphs:
-            self._lr_t = torch.tensor(float(learning_rate), device=device)
-            kw = dict(capturable=True, **_ADAM_IMPL) if self._capture else dict(foreach=False)
-            self.optimizer1 = optim.Adam(groups1, lr=self._lr_t, **kw)
-            self.optimizer2 = optim.Adam(self._params2, lr=torch.tensor(float(student_encoder_learning_rate), device=device), **kw)
-        else:
-            self._lr_t = None
-            self.optimizer1 = optim.Adam(groups1, lr=learning_rate)
-            self.optimizer2 = optim.Adam(self._params2, lr=student_encoder_learning_rate)
+        self.optimizer1 = self._make_adam(groups1)
+        self.optimizer2 = self._make_adam(self._params2, student_encoder_learning_rate)
         self.transition = RolloutStorageCTS.Transition()
         self.clip_param, self.num_learning_epochs, self.num_mini_batches = clip_param, num_learning_epochs, num_mini_batches
         self.value_loss_coef, self.entropy_coef, self.gamma, self.lam = value_loss_coef, entropy_coef, gamma, lam
@@ -78,10 +54,7 @@ class CTS(_RolloutHeads):
         self._steps = None
         self._step_reps = None
         self._plan = False                  # the no-autograd mini-batch (modules/fused_cts.py): decided at the first graph-mode update (None: not applicable)
-        self._fused_adam1 = self._fused_adam2 = None
-        if _world() > 1:
-            for p in self.model.parameters():
-                dist.broadcast(p.data, src=0)
+        self._sync_replicas(self.model)
 
     # the runner reaches the networks through either name
     @property
@@ -120,74 +93,40 @@ class CTS(_RolloutHeads):
         return latent
 
     def act(self, obs, privileged_obs, history):
-        st, t, m = self.storage, self.transition, self.model
-        s = st.step
-        if s >= st.num_transitions_per_env:
-            raise AssertionError("Rollout buffer overflow")
-        # record what env.step() is about to overwrite (the env's buffers and the runner's history ring are updated in place)
-        if obs.data_ptr() != st.observations[s].data_ptr():                     # (the env wrote this row itself: LeggedRobot.step(rollout=...))
-            st.observations[s].copy_(obs)
-        if privileged_obs.data_ptr() != st.privileged_observations[s].data_ptr():
-            st.privileged_observations[s].copy_(privileged_obs)
-        st.history[s].copy_(history)
+        st, m = self.storage, self.model
+        s = self._begin_step()
+        self._store_obs_rows(obs, privileged_obs, s)
+        st.history[s].copy_(history)          # (the runner's history ring is updated in place too)
         pk = self._policy_kernel() if self.fused_rollout else None
-        if pk is not None and all(x.is_contiguous() and x.dtype == torch.float32 for x in (obs, privileged_obs, history)):
+        if not all(x.is_contiguous() and x.dtype == torch.float32 for x in (obs, privileged_obs, history)):
+            pk = None
+        self._ensure_packed(pk, s)
+        if pk is not None:
             # two launches (include/go2nn.h ABI 5): both encoders on their env subsets -> the env-ordered latent; actor + critic + sampling head on [latent | obs] / [latent | priv]
-            if s == 0 or not self._pk_packed:
-                self._img_cache = {}
-                pk.pack()                  # the parameters only change in update(): once per rollout (inside the captured rollout graph too)
-                self._pk_packed = True
-                self._pk_recorded = self._pk_recorded or s == 0
             latent = self._rollout_latent(pk, privileged_obs, history)
-            actions = pk.act(latent, obs, privileged_obs, self._rollout_noise(m, st, s), st.actions[s], st.mu[s], st.sigma[s], st.actions_log_prob[s].view(-1), st.values[s].view(-1))
-            t.actions, t.values, t.actions_log_prob = actions, st.values[s], st.actions_log_prob[s].view(-1)
-            t.action_mean, t.action_sigma = st.mu[s], st.sigma[s]
-            return actions
-        if s == 0:
-            self._pk_recorded = False
+            return self._transition_from_rows(pk.act(latent, obs, privileged_obs, self._rollout_noise(m, st, s), st.actions[s], st.mu[s], st.sigma[s],
+                                                     st.actions_log_prob[s].view(-1), st.values[s].view(-1)), s)
         latent = self._latent_env_order(privileged_obs, history)
         if self.fused_rollout:
             mu, value = self._pair(lambda: m.policy_mean(latent, obs), lambda: m.evaluate_joint(privileged_obs, latent, obs), enabled=self._capture and not m.heads_share_parameters)
             return self._act_head(mu, m.std, m._noise(mu), value, s)      # (MCP-CTS: state-dependent std, no storage-shaped stand-in for the noise)
-        t.actions = m.act_joint(obs, latent).detach()
-        t.values = m.evaluate_joint(privileged_obs, latent, obs).detach()
-        t.actions_log_prob = m.get_actions_log_prob(t.actions).detach()
-        t.action_mean, t.action_sigma = m.action_mean.detach(), m.action_std.detach()
-        st.actions[s].copy_(t.actions)
-        st.values[s].copy_(t.values)
-        st.actions_log_prob[s].copy_(t.actions_log_prob.view(-1, 1))
-        st.mu[s].copy_(t.action_mean)
-        st.sigma[s].copy_(t.action_sigma)
-        return t.actions
+        return self._transition_to_rows(m, m.act_joint(obs, latent), m.evaluate_joint(privileged_obs, latent, obs), s)
 
     def process_env_step(self, rewards, dones, infos):
-        st = self.storage
-        s = st.step
-        if self.fused_rollout:
-            self._store_transition(rewards, dones, infos, s)
-        else:
-            r = rewards.clone()
-            if "time_outs" in infos:   # bootstrap on time-outs (:156-158)
-                r += self.gamma * torch.squeeze(st.values[s] * infos["time_outs"].unsqueeze(1).to(self.device), 1)
-            st.rewards[s].copy_(r.view(-1, 1))
-            st.dones[s].copy_(dones.view(-1, 1))
-        st.step += 1
-        self.transition.clear()
+        self._record_env_step(rewards, dones, infos)
         # model.reset(dones) (:163): the deployment-side history inside the module (written by act_inference only) — all zeros throughout training, where zeroing
         # rows of it is a no-op: two launches per env step saved
         if getattr(self.model, "_history_dirty", True):
             self.model.history.masked_fill_(dones.view(-1, 1, 1) > 0, 0.0)          # without a boolean-index sync
 
     def compute_returns(self, last_privileged_obs, last_history, last_obs=None):
-        pk = self._pk if self._pk not in (None, False) else None
+        pk = self._kernel()
         if pk is not None and self._pk_packed and all(x.is_contiguous() and x.dtype == torch.float32 for x in (last_privileged_obs, last_history)):
             last_values = pk.value(self._rollout_latent(pk, last_privileged_obs, last_history), last_privileged_obs)      # on the weights packed for this rollout (unchanged since)
         else:
             latent = self._latent_env_order(last_privileged_obs, last_history)
             last_values = self.model.evaluate_joint(last_privileged_obs, latent, last_obs).detach()
         self.storage.compute_returns(last_values, self.gamma, self.lam)
-
-    _pk = None
 
     def _policy_kernel(self):
         """-> _nn.PolicyKernelCTS for this model, or None (GO2_FUSED_POLICY=0, or heads / encoders the kernel does not cover: modules/fused_cts.py:cts_plan).  On a
@@ -212,7 +151,7 @@ class CTS(_RolloutHeads):
                         self._latent_buf = torch.zeros(self.storage.num_envs, plan.L, device=self.device)
                 except ValueError:          # (a width the kernel's LDS tiles do not hold)
                     self._pk = False
-        return self._pk if self._pk is not False else None
+        return self._kernel()
 
     def _rollout_latent(self, pk, privileged_obs, history):
         """-> the env-ordered latent [N, L]: one launch for both encoders; a student encoder that is not a plain MLP (MoE) runs as torch modules, without gradient, on the same stream"""
@@ -246,22 +185,7 @@ class CTS(_RolloutHeads):
         m.update_distribution(torch.cat([latent, obs_b], dim=1))
         lp_b = m.get_actions_log_prob(act_b)
         val_b, aux = m.value(latent, obs_b, priv_b)
-        mu_b, sig_b, ent_b = m.action_mean, m.action_std, m.entropy
-        with torch.no_grad():
-            kl = torch.sum(torch.log(sig_b / old_sig_b + 1.0e-5) + (torch.square(old_sig_b) + torch.square(old_mu_b - mu_b)) / (2.0 * torch.square(sig_b)) - 0.5, axis=-1)
-            kl_mean = torch.mean(kl)
-        ratio = torch.exp(lp_b - torch.squeeze(old_lp_b))
-        sur = -torch.squeeze(adv_b) * ratio
-        sur_clip = -torch.squeeze(adv_b) * torch.clamp(ratio, 1.0 - self.clip_param, 1.0 + self.clip_param)
-        sl = torch.max(sur, sur_clip)
-        surrogate_loss = sl[:n_t].mean() + sl[n_t:].mean()
-        if self.use_clipped_value_loss:
-            v_clip = tv_b + (val_b - tv_b).clamp(-self.clip_param, self.clip_param)
-            value_loss = torch.max((val_b - ret_b).pow(2), (v_clip - ret_b).pow(2)).mean()
-        else:
-            value_loss = (ret_b - val_b).pow(2).mean()
-        ent = ent_b.mean()
-        loss = surrogate_loss + self.value_loss_coef * value_loss - self.entropy_coef * ent
+        loss, value_loss, surrogate_loss, ent, kl_mean = self.ppo_terms(lp_b, val_b, m.action_mean, m.action_std, m.entropy, tv_b, adv_b, ret_b, old_lp_b, old_mu_b, old_sig_b, n_t)
         return self._policy_extra(loss, aux), value_loss, surrogate_loss, ent, kl_mean
 
     _NUM_POLICY_LOGS = 0
@@ -296,29 +220,12 @@ class CTS(_RolloutHeads):
     def _update_eager(self):
         fl, n_t = self.storage.flat(), self._teacher_rows()
         idx = self.storage.mini_batch_indices(self.num_mini_batches)
-        world, sync = _world(), _collectives_on()
         P = self._NUM_POLICY_LOGS
         acc = [0.0] * (3 + P + self._NUM_STUDENT_LOGS)
         for _ in range(self.num_learning_epochs):
             for b in idx:
                 loss, value_loss, surrogate_loss, ent, kl_mean = self._policy_losses(*self._gather(fl, b), n_t)
-                adaptive = self.desired_kl is not None and self.schedule == "adaptive"
-                self.optimizer1.zero_grad()
-                loss.backward()
-                if sync:
-                    kl_mean = _allreduce_mean_grads(self._params1, world, kl_mean if adaptive else None)
-                if adaptive:     # decided after backward (the rate is only read by optimizer1.step()) so the KL shares the gradient all-reduce
-                    if kl_mean > self.desired_kl * 2.0:
-                        self.learning_rate = max(1e-5, self.learning_rate / 1.5)
-                    elif kl_mean < self.desired_kl / 2.0 and kl_mean > 0.0:
-                        self.learning_rate = min(1e-2, self.learning_rate * 1.5)
-                    for g in self.optimizer1.param_groups:
-                        if torch.is_tensor(g["lr"]):
-                            g["lr"].fill_(self.learning_rate)
-                        else:
-                            g["lr"] = self.learning_rate
-                nn.utils.clip_grad_norm_(self._params1, self.max_grad_norm)
-                self.optimizer1.step()
+                self._eager_step(loss, self.optimizer1, self._params1, kl_mean)
                 acc[0] += value_loss.item(); acc[1] += surrogate_loss.item(); acc[2] += ent.item()
                 for i, v in enumerate(self._policy_logs):
                     acc[3 + i] += v.item()
@@ -326,12 +233,7 @@ class CTS(_RolloutHeads):
             for b in idx:
                 bs = b[n_t:]
                 loss, logs = self._student_losses(fl["hist"][bs], fl["cobs"][bs])
-                self.optimizer2.zero_grad()
-                loss.backward()
-                if sync:
-                    _allreduce_mean_grads(self._params2, world)
-                nn.utils.clip_grad_norm_(self._params2, self.max_grad_norm)
-                self.optimizer2.step()
+                self._eager_step(loss, self.optimizer2, self._params2)
                 for i, v in enumerate(logs):
                     acc[3 + P + i] += v.item()
         n = self.num_learning_epochs * self.num_mini_batches
@@ -344,9 +246,6 @@ class CTS(_RolloutHeads):
 
     # ---- graph mode: every decision on the device; one captured policy step and one captured student step per mini-batch slot ----
     _KEYS = ("obs", "cobs", "hist", "act", "val", "adv", "ret", "logp", "mu", "sig")
-
-    def _adaptive(self):
-        return self.desired_kl is not None and self.schedule == "adaptive"
 
     def _own_plan(self):
         """The CTS mini-batch as explicit launches without autograd (modules/fused_cts.py), when it covers this model and algorithm — the plain CTS heads and loss
@@ -386,21 +285,7 @@ class CTS(_RolloutHeads):
             self._kl = kl_mean
 
     def _policy_back(self, split=False):
-        if split:
-            kl_mean = self._bucket1.unpack(_world())
-        else:
-            kl_mean = self._kl
-        if self._fused_adam1 is None:
-            self._fused_adam1 = FusedClipAdam(self.lib, self.optimizer1, self._params1, self.max_grad_norm)
-        if self._fused_adam1.usable and self._fused_adam1.step(kl_mean if self._adaptive() else None, self.desired_kl if self._adaptive() else 0.0):
-            return
-        if self._adaptive():
-            lr = self._lr_t
-            kl_mean = kl_mean.reshape(())
-            up, down = torch.clamp(lr * 1.5, max=1e-2), torch.clamp(lr / 1.5, min=1e-5)
-            lr.copy_(torch.where(kl_mean > self.desired_kl * 2.0, down, torch.where((kl_mean < self.desired_kl / 2.0) & (kl_mean > 0.0), up, lr)))
-        nn.utils.clip_grad_norm_(self._params1, self.max_grad_norm, foreach=True)
-        self.optimizer1.step()
+        self._clip_adam(self.optimizer1, self._params1, self._bucket1.unpack(_world()) if split else self._kl)
 
     def _policy_step(self, i):
         self._policy_front(i)
@@ -423,12 +308,7 @@ class CTS(_RolloutHeads):
     def _student_back(self, split=False):
         if split:
             self._bucket2.unpack(_world())
-        if self._fused_adam2 is None:
-            self._fused_adam2 = FusedClipAdam(self.lib, self.optimizer2, self._params2, self.max_grad_norm)
-        if self._fused_adam2.usable and self._fused_adam2.step():
-            return
-        nn.utils.clip_grad_norm_(self._params2, self.max_grad_norm, foreach=True)
-        self.optimizer2.step()
+        self._clip_adam(self.optimizer2, self._params2)          # (its rate is fixed: no KL)
 
     def _student_backward(self, hist_s, priv_s, teacher_latent):
         """forward + backward of the student loss on one mini-batch's student rows (graph mode); the logs are added to the accumulators"""
@@ -448,24 +328,16 @@ class CTS(_RolloutHeads):
             for k in self._KEYS:
                 torch.index_select(self._flat[k], 0, order, out=self._perm[k])
             return
-        import ctypes as C
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream) if str(self.device).startswith("cuda") else None
         self._order_live = order.to(torch.int64).contiguous()          # (alive until the launch has run)
-        rc = self.lib.go2sim_shuffle_gather(self._gather_jobs, len(self._gather_jobs), int(order.numel()), C.c_void_p(self._order_live.data_ptr()), None,
-                                            C.c_void_p(self._accbuf.data_ptr()), int(self._accbuf.numel()), stream)
-        if rc != 0:
-            raise RuntimeError("go2sim_shuffle_gather failed: %s" % self.lib.go2sim_last_error().decode())
+        self._call("go2sim_shuffle_gather", self._gather_jobs, len(self._gather_jobs), int(order.numel()), self._ptr(self._order_live), None,
+                   self._ptr(self._accbuf), int(self._accbuf.numel()), self._stream(self._accbuf))
 
     def _update_head(self):
         """rollout_storage_cts.py:152-160 on the device: the two keyed permutations -> the update's index list (go2sim_cts_minibatch_indices), the gather, the student latents"""
-        import ctypes as C
         st, nmb = self.storage, self.num_mini_batches
         T = st.num_transitions_per_env
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream) if str(self.device).startswith("cuda") else None
-        rc = self.lib.go2sim_cts_minibatch_indices(C.c_void_p(self._order.data_ptr()), nmb, st.teacher_num_envs * T, st.student_num_envs * T, C.c_void_p(st.ref2mine.data_ptr()),
-                                                   C.c_void_p(self._shuffle_key.data_ptr()), stream)
-        if rc != 0:
-            raise RuntimeError("go2sim_cts_minibatch_indices failed: %s" % self.lib.go2sim_last_error().decode())
+        self._call("go2sim_cts_minibatch_indices", self._ptr(self._order), nmb, st.teacher_num_envs * T, st.student_num_envs * T, self._ptr(st.ref2mine),
+                   self._ptr(self._shuffle_key), self._stream(self._order))
         self._gather_update(self._order)
         self._student_latents()
 
@@ -517,7 +389,6 @@ class CTS(_RolloutHeads):
             self._gather_jobs = None
             self._tlat, self._tlat_step = None, None
             if plan is not None:
-                import ctypes as C
                 from ..._abi import Go2GatherJob
                 L, no, npriv = plan.L, self._flat["obs"].shape[1], self._flat["cobs"].shape[1]
                 self._perm["ain"], self._perm["cin"] = new(rows, L + no), new(rows, L + npriv)
@@ -533,16 +404,12 @@ class CTS(_RolloutHeads):
                     self._tlat_step = CapturedStep(self._teacher_latents, enabled=self._capture, warmup=2, name="CTS teacher latents of the student rows", optional=True)
                 self._head_step = CapturedStep(self._update_head, enabled=self._capture, warmup=2, name="CTS update head (permutation, gather, student latents)", optional=True)
             self._step_reps = None          # (set by the branch whose graphs span every epoch)
-            if _collectives_on():     # two captured halves per slot, the gradient all-reduce eager between them
-                mk = lambda front, back, bucket, name: [ReducedStep((lambda i=i: front(i, True)), (lambda: back(True)), bucket, enabled=self._capture, warmup=3 if i == 0 else 1,
-                                                                    name="CTS %s step %d" % (name, i)) for i in range(nmb)]
-                self._steps = (mk(self._policy_front, self._policy_back, (lambda: self._bucket1), "policy"),
-                               mk(self._student_front, self._student_back, (lambda: self._bucket2), "student"))
+            if _collectives_on():
+                self._steps = (self._reduced_steps(self._policy_front, self._policy_back, (lambda: self._bucket1), "CTS policy"),
+                               self._reduced_steps(self._student_front, self._student_back, (lambda: self._bucket2), "CTS student"))
             elif plan is not None:
-                # one rank, own path: a whole PHASE (every epoch's nmb steps, each on its own chunk of the permuted rollout) is one graph, as in PPO (1 + 1 graph launches per update instead of 20 + 20)
-                ne = self.num_learning_epochs
-                mk = lambda fn, name: [CapturedStep((lambda: [fn(i) for _ in range(ne) for i in range(nmb)] and None), enabled=self._capture, warmup=1, name="CTS %s phase (%d epochs x %d steps)" % (name, ne, nmb))]
-                self._steps = (mk(self._policy_step, "policy"), mk(self._student_step, "student"))
+                # one rank, own path: a whole PHASE is one graph, as the whole update in PPO (1 + 1 graph launches per update instead of 20 + 20)
+                self._steps = (self._whole_update_step(self._policy_step, "CTS policy phase"), self._whole_update_step(self._student_step, "CTS student phase"))
                 self._step_reps = 1
             else:
                 mk = lambda fn, name: [CapturedStep((lambda i=i: fn(i)), enabled=self._capture, warmup=3 if i == 0 else 1, name="CTS %s step %d" % (name, i)) for i in range(nmb)]
@@ -567,9 +434,7 @@ class CTS(_RolloutHeads):
             own, P = self._acc_own, self._NUM_POLICY_LOGS
             parts = [own[1:2], own[0:1], own[3:4], acc[3:3 + P], own[4:5] if self._own_student() else acc[3 + P:3 + P + 1], acc[3 + P + 1:]]
             acc = torch.cat(parts)
-        out = torch.cat([acc / n, self._lr_t.reshape(1)]).tolist()          # ONE device -> host read per update
-        self.learning_rate = float(out.pop())
-        return self._ordered(tuple(out))
+        return self._ordered(tuple(self._read_back(acc, n)))
 
     def graphs_captured(self):
         """True iff every policy / student mini-batch step is being replayed from a HIP graph."""
@@ -579,8 +444,7 @@ class CTS(_RolloutHeads):
         return bool(self.use_graphs and self._capture and all_captured(self._steps) and all(h.graph is not None for h in heads))
 
     def update(self):
-        self._pk_packed = False          # the optimizer steps below change the parameters: the next rollout re-packs
-        self._img_cache = None
+        self.parameters_changed()          # the optimizer steps below change the parameters: the next rollout re-packs
         out = self._update_graphs() if self.use_graphs else self._update_eager()
         self.storage.clear()
         return out

@@ -5,6 +5,20 @@ import torch
 from .cts import CTS
 
 
+def _balance(weights):
+    """mean((mean_batch(gate) - 1/E)^2) (moe_cts.py:205-209, ac_moe_cts.py:186-189)"""
+    return (weights.mean(dim=0) - 1.0 / weights.shape[1]).pow(2).mean()
+
+
+def _moe_student_losses(alg, hist_s, priv_s, teacher_latent=None):
+    """CTS._student_losses for a mixture-of-experts student encoder: the latent loss + load_balance_coef * the balance of its gate; both are logged"""
+    student_latent, gate = alg.model.student_latent(hist_s)
+    teacher_latent = alg._teacher_latent(priv_s, teacher_latent)
+    latent_loss = (teacher_latent - student_latent).pow(2).mean()
+    load_balance_loss = _balance(gate)
+    return latent_loss + alg.load_balance_coef * load_balance_loss, (latent_loss, load_balance_loss)
+
+
 class MoECTS(CTS):
     _NUM_STUDENT_LOGS = 2
 
@@ -12,14 +26,7 @@ class MoECTS(CTS):
         super().__init__(model, num_envs, history_length, **kwargs)
         self.load_balance_coef = load_balance_coef
 
-    def _student_losses(self, hist_s, priv_s, teacher_latent=None):
-        student_latent, gate = self.model.student_latent(hist_s)
-        teacher_latent = self._teacher_latent(priv_s, teacher_latent)
-        latent_loss = (teacher_latent - student_latent).pow(2).mean()
-        usage = gate.mean(dim=0)
-        load_balance_loss = (usage - 1.0 / gate.shape[1]).pow(2).mean()
-        return latent_loss + self.load_balance_coef * load_balance_loss, (latent_loss, load_balance_loss)
-
+    _student_losses = _moe_student_losses
 
     def _student_backward(self, hist_s, priv_s, teacher_latent):
         """Graph mode on the library pair: the mixture, the normaliser, both losses and their backward as two launches (modules/fused_cts.py:moe_head_grads) — autograd
@@ -36,11 +43,6 @@ class MoECTS(CTS):
 
 class MoENGCTS(MoECTS):
     """rsl_rl/rsl_rl/algorithms/moe_ng_cts.py: MoECTS whose student latent comes from the no-goal encoder (the model's `student_latent` hook)."""
-
-
-def _balance(weights):
-    """mean((mean_batch(gate) - 1/E)^2) (ac_moe_cts.py:186-189)"""
-    return (weights.mean(dim=0) - 1.0 / weights.shape[1]).pow(2).mean()
 
 
 class ACMoECTS(CTS):
@@ -63,15 +65,10 @@ class ACMoECTS(CTS):
 
 
 class DualMoECTS(ACMoECTS):
-    """AC-MoE heads + the MoE student encoder (dual_moe_cts.py:40-262): returns (..., latent, student load balance, actor load balance)."""
+    """AC-MoE heads + the MoE student encoder (dual_moe_cts.py:40-262): returns (..., latent, student load balance, actor load balance).
+    (The student step's backward stays CTS's autograd one, not MoECTS's fused mixture head.)"""
     _NUM_STUDENT_LOGS = 2
-
-    def _student_losses(self, hist_s, priv_s, teacher_latent=None):
-        student_latent, gate = self.model.student_latent(hist_s)
-        teacher_latent = self._teacher_latent(priv_s, teacher_latent)
-        latent_loss = (teacher_latent - student_latent).pow(2).mean()
-        lb = _balance(gate)
-        return latent_loss + self.load_balance_coef * lb, (latent_loss, lb)
+    _student_losses = _moe_student_losses
 
 
 class MCPCTS(CTS):

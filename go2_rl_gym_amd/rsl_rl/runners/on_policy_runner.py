@@ -170,7 +170,7 @@ class OnPolicyRunner:
         """compute_returns (bootstrap value of the last observations, GAE, advantage normalisation: on_policy_runner.py:158, rollout_storage.py:123-137)
         — replayed from its own small HIP graph when the rollout is (eager it is ~10 launches with host gaps between them); eager whenever a
         collective sits inside it (more than one rank: the advantage-statistics all-reduce)."""
-        from ..algorithms.ppo import _collectives_on
+        from ..algorithms._base import _collectives_on
         if self._rollout_graph is None or _collectives_on():
             return self._compute_returns()
         if self._returns_graph is None:
@@ -405,6 +405,7 @@ class OnPolicyRunner:
     def load(self, path, load_optimizer=True):
         d = torch.load(path, map_location=self.device)
         self.alg.actor_critic.load_state_dict(d["model_state_dict"])
+        self.alg.parameters_changed()          # (what the rollout's kernels hold packed is stale now)
         if load_optimizer:
             load_optimizer_state(self.alg.optimizer, d["optimizer_state_dict"])
             self.alg.rebind_lr()

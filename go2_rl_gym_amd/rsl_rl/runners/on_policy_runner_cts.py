@@ -112,6 +112,7 @@ class OnPolicyRunnerCTS(OnPolicyRunner):
     def load(self, path, load_optimizer=True):
         d = torch.load(path, map_location=self.device)
         self.alg.model.load_state_dict(d["model_state_dict"])
+        self.alg.parameters_changed()          # (what the rollout's kernels hold packed is stale now)
         if load_optimizer:
             load_optimizer_state(self.alg.optimizer1, d["optimizer1_state_dict"])
             load_optimizer_state(self.alg.optimizer2, d["optimizer2_state_dict"])

@@ -251,9 +251,10 @@ def test_split_surrogate_kernel_matches_autograd():
     assert all(p.grad is None for p in m.student_encoder.parameters())      # the policy loss never reaches the student encoder
 
 
-def test_checkpoint_roundtrip(tmp_path):
+def test_checkpoint_roundtrip(tmp_path, monkeypatch):
     """save -> load (with optimizers) restores weights, iteration and learning rate; a checkpoint with FLOAT learning rates
-    (the reference's format) loads too."""
+    (the reference's format) loads too.  load() also tells the algorithm that its parameters changed: the next act(), though not the first step of a
+    rollout, packs the policy kernel's weights again."""
     g = dict(np.load(os.path.join(G, "cts_iteration.npz")))
     T = g["rew"].shape[0]
     r1 = OnPolicyRunnerCTS(ScriptedEnv(g, load_oracle()), _train_cfg("CTS", T), log_dir=str(tmp_path / "a"), device="cpu")
@@ -267,6 +268,34 @@ def test_checkpoint_roundtrip(tmp_path):
         assert torch.equal(a, b), k
     st1, st2 = r1.alg.optimizer1.state_dict()["state"], r2.alg.optimizer1.state_dict()["state"]
     assert all(torch.equal(st1[i]["exp_avg"], st2[i]["exp_avg"]) for i in st1)
+    # load() in the middle of a rollout collected on the policy kernel (host builds, as in test_one_iteration_matches_reference["own"])
+    from helpers import load_nn_emu
+    from go2_rl_gym_amd.rsl_rl.modules import fused as fmod
+    monkeypatch.setattr(fmod, "_LIB", load_oracle()); monkeypatch.setattr(fmod, "_NN", load_nn_emu())
+    env = ScriptedEnv(g, load_oracle())
+    r3 = OnPolicyRunnerCTS(env, _train_cfg("CTS", T), log_dir=None, device="cpu", use_graphs="uncaptured")
+    alg = r3.alg
+    alg.fused_loss = alg.fused_rollout = True
+    alg.nn_lib = load_nn_emu()
+    pk = alg._policy_kernel()
+    assert pk is not None
+    packs, pack = [], pk.pack
+    monkeypatch.setattr(pk, "pack", lambda: (packs.append(alg.storage.step), pack())[1])
+
+    def step():
+        a = alg.act(env.obs_seq[env.t], env.priv_seq[env.t], r3.history.flatten(1))
+        alg.process_env_step(*env.step(a)[2:])
+        return a
+    step(); step()
+    assert packs == [0]                       # once per rollout
+    r3.load(p)
+    a = step()
+    assert packs == [0, 2] and alg._pk_packed            # the loaded weights were packed at step 2 ...
+    with torch.no_grad():                     # ... and are what that step acted on
+        lat = alg._latent_env_order(env.priv_seq[2], r3.history.flatten(1))
+        mu = r1.alg.model.policy_mean(lat, env.obs_seq[2])
+    np.testing.assert_allclose(alg.storage.mu[2].numpy(), mu.numpy(), atol=2e-6)
+    assert a.shape == mu.shape
 
 
 def test_midrun_checkpoints_carry_their_iteration(tmp_path):
