@@ -25,6 +25,14 @@ GO2NN_TRACE_WIDTH = sum(w for _, w in TRACE_BLOCKS)
 TRACE_OFFSET = {name: sum(w for _, w in TRACE_BLOCKS[:i]) for i, (name, _) in enumerate(TRACE_BLOCKS)}
 TRACE_FIELDS = ("root_states", "dof_state", "torques", "actions", "commands", "base_lin_vel", "base_ang_vel", "projected_gravity", "rigid_body_states", "contact_forces",
                 "rew_buf", "reset_buf", "time_out_buf")
+# the evaluator's perturbations: the rows of the table [GO2NN_ROBUST_NUM, N] in the order of the enum GO2NN_ROBUST_* of include/go2nn.h (per-env state first, then the
+# accumulators go2nn_robust_reduce sums), the buffers of Go2nnRobustIn in the struct's order, and the mask bit of each writable dynamics row
+ROBUST_ROWS = ("step", "open", "peak_err", "peak_tilt", "ok_run", "done", "pushes", "push_falls", "recovered", "recovery_steps", "peak_err_sum", "peak_tilt_sum")
+GO2NN_ROBUST_NUM, GO2NN_ROBUST_ACC_FIRST, GO2NN_ROBUST_MAX_SPECS = len(ROBUST_ROWS), ROBUST_ROWS.index("pushes"), 64
+GO2NN_ROBUST_ACC_NUM = GO2NN_ROBUST_NUM - GO2NN_ROBUST_ACC_FIRST
+ROBUST_FIELDS = ("root_states", "commands", "base_lin_vel", "projected_gravity", "reset_buf", "time_out_buf", "motor_strengths", "p_gains_multiplier", "d_gains_multiplier",
+                 "added_base_mass", "friction_coeffs")
+ROBUST_MASK = {"strength": 1, "kp_mul": 2, "kd_mul": 4, "added_mass": 8, "friction": 16}
 _cached = None
 
 
@@ -88,6 +96,15 @@ class Go2nnEvalIn(C.Structure):
 class Go2nnTraceIn(C.Structure):          # (within ABI 7)
     _fields_ = [(k, Go2nnEvalField) for k in TRACE_FIELDS] + [("dof_vel_offset", C.c_int32), ("rigid_body_stride", C.c_int32), ("contact_body_stride", C.c_int32),
                                                               ("foot_body", C.c_int32 * 4), ("pad_", C.c_int32)]
+
+
+class Go2nnRobustSpec(C.Structure):          # (within ABI 7)
+    _fields_ = [("dv", C.c_float * 3), ("first", C.c_int32), ("period", C.c_int32), ("count", C.c_int32), ("window", C.c_int32), ("hold", C.c_int32), ("thr", C.c_float),
+                ("strength", C.c_float), ("kp_mul", C.c_float), ("kd_mul", C.c_float), ("added_mass", C.c_float), ("friction", C.c_float), ("mask", C.c_int32), ("pad_", C.c_int32)]
+
+
+class Go2nnRobustIn(C.Structure):          # (within ABI 7)
+    _fields_ = [(k, Go2nnEvalField) for k in ROBUST_FIELDS] + [("num_specs", C.c_int32), ("pad_", C.c_int32)]
 
 
 def trace_env_ids(env_ids, num_envs):
@@ -154,6 +171,11 @@ def bind(path):
     lib.go2nn_eval_reduce.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
     lib.go2nn_trace_record.argtypes = [C.POINTER(Go2nnTraceIn), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
     lib.go2nn_trace_clear.argtypes = [C.c_void_p, C.c_void_p]
+    lib.go2nn_robust_check_specs.argtypes = [C.c_void_p, C.c_int32]
+    lib.go2nn_robust_begin.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
+    lib.go2nn_robust_apply.argtypes = [C.POINTER(Go2nnRobustIn), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+    lib.go2nn_robust_accumulate.argtypes = [C.POINTER(Go2nnRobustIn), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+    lib.go2nn_robust_reduce.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
     if lib.go2nn_abi_version() != GO2NN_ABI_VERSION:
         raise RuntimeError("%s: ABI version %d, expected %d" % (path, lib.go2nn_abi_version(), GO2NN_ABI_VERSION))
     return lib

@@ -11,8 +11,10 @@
 
 #ifdef GO2_EMU
 #define EVAL_FN static inline
+#define EVAL_MEMBER inline
 #else
 #define EVAL_FN __device__ __forceinline__
+#define EVAL_MEMBER __device__ __forceinline__
 #endif
 #define EVAL_THREADS 256
 
@@ -60,6 +62,43 @@ EVAL_FN double eval_reduce_term(const float* acc, int N, int e, int c) {
   return acc[(long long)GO2NN_EVAL_FALLS * N + e] == 0.f ? 1.0 : 0.0;
 }
 
+struct EvalTerm {
+  const float* acc; int N, c;
+  EVAL_MEMBER double operator()(int e) const { return eval_reduce_term(acc, N, e, c); }
+};
+
+// The sum of term(e) over the envs e of group g, in an order that depends on N only: partial t adds the envs t, t + 256, ... in fp64, then a fixed tree over the 256
+// partials.  Device: called by every thread of a 256-thread workgroup, the sum is valid in thread 0.  Shared by go2nn_eval_reduce and go2nn_robust_reduce (go2nn_robust.h).
+#ifdef GO2_EMU
+template <class Term> static inline double eval_group_sum(const int32_t* group, int N, int g, Term term) {
+  double part[EVAL_THREADS];
+  for (int t = 0; t < EVAL_THREADS; ++t) {
+    double s = 0.0;
+    for (int e = t; e < N; e += EVAL_THREADS)
+      if (group[e] == g) s += term(e);
+    part[t] = s;
+  }
+  for (int w = EVAL_THREADS / 2; w > 0; w >>= 1)
+    for (int t = 0; t < w; ++t) part[t] += part[t + w];
+  return part[0];
+}
+#else
+template <class Term> __device__ __forceinline__ double eval_group_sum(const int32_t* group, int N, int g, Term term) {
+  __shared__ double part[EVAL_THREADS];
+  const int t = threadIdx.x;
+  double s = 0.0;
+  for (int e = t; e < N; e += EVAL_THREADS)
+    if (group[e] == g) s += term(e);
+  part[t] = s;
+  __syncthreads();
+  for (int w = EVAL_THREADS / 2; w > 0; w >>= 1) {
+    if (t < w) part[t] += part[t + w];
+    __syncthreads();
+  }
+  return part[0];
+}
+#endif
+
 #ifndef GO2_EMU
 __global__ void __launch_bounds__(EVAL_THREADS) go2nn_eval_accumulate_kernel(const Go2nnEvalIn in, float* acc, int N) {
   const int e = blockIdx.x * EVAL_THREADS + threadIdx.x;
@@ -71,18 +110,9 @@ __global__ void __launch_bounds__(EVAL_THREADS) go2nn_eval_clear_kernel(float* a
 }
 // grid = (G, GO2NN_EVAL_NUM + 2)
 __global__ void __launch_bounds__(EVAL_THREADS) go2nn_eval_reduce_kernel(const float* acc, const int32_t* group, int N, double* out) {
-  __shared__ double part[EVAL_THREADS];
-  const int g = blockIdx.x, c = blockIdx.y, t = threadIdx.x;
-  double s = 0.0;
-  for (int e = t; e < N; e += EVAL_THREADS)
-    if (group[e] == g) s += eval_reduce_term(acc, N, e, c);
-  part[t] = s;
-  __syncthreads();
-  for (int w = EVAL_THREADS / 2; w > 0; w >>= 1) {
-    if (t < w) part[t] += part[t + w];
-    __syncthreads();
-  }
-  if (t == 0) out[(long long)g * (GO2NN_EVAL_NUM + 2) + c] = part[0];
+  const int g = blockIdx.x, c = blockIdx.y;
+  const double s = eval_group_sum(group, N, g, EvalTerm{acc, N, c});
+  if (threadIdx.x == 0) out[(long long)g * (GO2NN_EVAL_NUM + 2) + c] = s;
 }
 #endif
 
@@ -126,18 +156,7 @@ int go2nn_eval_reduce(const float* acc, const int32_t* group, int32_t N, int32_t
 #ifdef GO2_EMU
   (void)stream;
   for (int g = 0; g < G; ++g)
-    for (int c = 0; c < GO2NN_EVAL_NUM + 2; ++c) {
-      double part[EVAL_THREADS];
-      for (int t = 0; t < EVAL_THREADS; ++t) {
-        double s = 0.0;
-        for (int e = t; e < N; e += EVAL_THREADS)
-          if (group[e] == g) s += eval_reduce_term(acc, N, e, c);
-        part[t] = s;
-      }
-      for (int w = EVAL_THREADS / 2; w > 0; w >>= 1)
-        for (int t = 0; t < w; ++t) part[t] += part[t + w];
-      out[(long long)g * (GO2NN_EVAL_NUM + 2) + c] = part[0];
-    }
+    for (int c = 0; c < GO2NN_EVAL_NUM + 2; ++c) out[(long long)g * (GO2NN_EVAL_NUM + 2) + c] = eval_group_sum(group, N, g, EvalTerm{acc, N, c});
 #else
   hipLaunchKernelGGL(go2nn_eval_reduce_kernel, dim3((unsigned)G, GO2NN_EVAL_NUM + 2), dim3(EVAL_THREADS), 0, (hipStream_t)stream, acc, group, N, out);
   HIPCHK(hipGetLastError());

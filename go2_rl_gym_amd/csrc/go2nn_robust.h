@@ -1,0 +1,211 @@
+// go2nn_robust.h — the evaluator's perturbation kernels (include/go2nn.h: go2nn_robust_*, added within ABI 7; go2_rl_gym_amd/utils/evaluator.py).
+// Included at the end of go2nn_impl.cpp after go2nn_trace.h (FAIL, HIPCHK are the former's helpers; EVAL_FN, eval_f, eval_b, eval_group_sum go2nn_eval.h's).
+//
+// Two launches per env step, one lane per env, no LDS, no atomics, no cross-lane traffic.  go2nn_robust_apply (before the step) writes the env's masked dynamics rows —
+// up to 38 floats — and, on a scheduled step, adds the rotated impulse to three root-state floats; go2nn_robust_accumulate (after it) reads 7 floats and two flags and
+// read-modify-writes the env's column of the table [GO2NN_ROBUST_NUM, N].  With the HIP simulator's field-major buffers (env stride 1) consecutive lanes touch consecutive
+// addresses of every component and of every table row: each load / store instruction of a wave is one dense 256-byte line.  The spec is read through pert_of_env — at most 64
+// specs of 64 bytes, resident in L2 / the vector cache after the first wave.  Both kernels are launch-bound at evaluation sizes (1024 lanes = 16 waves).
+// The step counter is the table's STEP row, advanced by the accumulate kernel: no host argument changes between steps, so a captured pair advances on every replay.
+// The host build runs the same element functions in plain loops.
+#ifndef GO2NN_ROBUST_H
+#define GO2NN_ROBUST_H
+
+EVAL_FN float* robust_w(const Go2nnEvalField& f, int e, int c) { return (float*)f.p + ((long long)e * f.env_stride + (long long)c * f.comp_stride); }
+
+// does a push fire at step s?  (period >= 1 is the host check's duty; a bad spec that got here never fires instead of dividing by zero)
+EVAL_FN bool robust_fires(const Go2nnRobustSpec& sp, int s) {
+  if (sp.count <= 0 || sp.period < 1 || s < sp.first) return false;
+  const int d = s - sp.first;
+  return d % sp.period == 0 && d / sp.period < sp.count;
+}
+
+EVAL_FN void robust_apply_env(const Go2nnRobustIn& in, const Go2nnRobustSpec* specs, const int32_t* pert_of_env, float* table, int N, int e) {
+  const int p = pert_of_env[e];
+  if (p < 0 || p >= in.num_specs) return;
+  const Go2nnRobustSpec sp = specs[p];
+  if (sp.mask & GO2NN_ROBUST_MASK_STRENGTH)
+    for (int j = 0; j < 12; ++j) *robust_w(in.motor_strengths, e, j) = sp.strength;
+  if (sp.mask & GO2NN_ROBUST_MASK_KP)
+    for (int j = 0; j < 12; ++j) *robust_w(in.p_gains_multiplier, e, j) = sp.kp_mul;
+  if (sp.mask & GO2NN_ROBUST_MASK_KD)
+    for (int j = 0; j < 12; ++j) *robust_w(in.d_gains_multiplier, e, j) = sp.kd_mul;
+  if (sp.mask & GO2NN_ROBUST_MASK_ADDED_MASS) *robust_w(in.added_base_mass, e, 0) = sp.added_mass;
+  if (sp.mask & GO2NN_ROBUST_MASK_FRICTION) *robust_w(in.friction_coeffs, e, 0) = sp.friction;
+  float* col = table + e;
+  if (!robust_fires(sp, (int)col[(long long)GO2NN_ROBUST_STEP * N])) return;
+  const float qx = eval_f(in.root_states, e, 3), qy = eval_f(in.root_states, e, 4), qz = eval_f(in.root_states, e, 5), qw = eval_f(in.root_states, e, 6);
+  float c = 1.f - 2.f * (qy * qy + qz * qz), s = 2.f * (qx * qy + qw * qz);
+  const float n = sqrtf(c * c + s * s);
+  if (n < 1e-6f) { c = 1.f; s = 0.f; } else { c /= n; s /= n; }
+  *robust_w(in.root_states, e, 7) += c * sp.dv[0] - s * sp.dv[1];
+  *robust_w(in.root_states, e, 8) += s * sp.dv[0] + c * sp.dv[1];
+  *robust_w(in.root_states, e, 9) += sp.dv[2];
+  col[(long long)GO2NN_ROBUST_OPEN * N] = 1.f;
+  col[(long long)GO2NN_ROBUST_PEAK_ERR * N] = 0.f;
+  col[(long long)GO2NN_ROBUST_PEAK_TILT * N] = 0.f;
+  col[(long long)GO2NN_ROBUST_OK_RUN * N] = 0.f;
+  col[(long long)GO2NN_ROBUST_DONE * N] = 0.f;
+  col[(long long)GO2NN_ROBUST_PUSHES * N] += 1.f;
+}
+
+EVAL_FN void robust_accumulate_env(const Go2nnRobustIn& in, const Go2nnRobustSpec* specs, const int32_t* pert_of_env, float* table, int N, int e) {
+  float* col = table + e;
+#define ROW(r) col[(long long)GO2NN_ROBUST_##r * N]
+  const int p = pert_of_env[e];
+  const float open = ROW(OPEN);
+  if (p >= 0 && p < in.num_specs && open > 0.f) {
+    const Go2nnRobustSpec sp = specs[p];
+    if (ROW(DONE) == 0.f) {
+      const float dx = eval_f(in.commands, e, 0) - eval_f(in.base_lin_vel, e, 0), dy = eval_f(in.commands, e, 1) - eval_f(in.base_lin_vel, e, 1);
+      const float gx = eval_f(in.projected_gravity, e, 0), gy = eval_f(in.projected_gravity, e, 1);
+      const float err = sqrtf(dx * dx + dy * dy), tilt = sqrtf(gx * gx + gy * gy);
+      const bool fall = eval_b(in.reset_buf, e) != 0 && eval_b(in.time_out_buf, e) == 0;
+      ROW(PEAK_ERR) = fmaxf(ROW(PEAK_ERR), err);
+      ROW(PEAK_TILT) = fmaxf(ROW(PEAK_TILT), tilt);
+      if (fall) {
+        ROW(PUSH_FALLS) += 1.f;
+        ROW(DONE) = 1.f;
+      } else if (err < sp.thr) {
+        const float run = ROW(OK_RUN) + 1.f;
+        ROW(OK_RUN) = run;
+        if (run == (float)sp.hold) {
+          ROW(RECOVERED) += 1.f;
+          ROW(RECOVERY_STEPS) += open;
+          ROW(DONE) = 1.f;
+        }
+      } else {
+        ROW(OK_RUN) = 0.f;
+      }
+    }
+    if (open >= (float)sp.window) {
+      ROW(PEAK_ERR_SUM) += ROW(PEAK_ERR);
+      ROW(PEAK_TILT_SUM) += ROW(PEAK_TILT);
+      ROW(OPEN) = 0.f;
+    } else {
+      ROW(OPEN) = open + 1.f;
+    }
+  }
+  ROW(STEP) += 1.f;
+#undef ROW
+}
+
+// column c of go2nn_robust_reduce's output: the accumulator rows, then 1 (the group's size)
+struct RobustTerm {
+  const float* table; int N, c;
+  EVAL_MEMBER double operator()(int e) const { return c < GO2NN_ROBUST_ACC_NUM ? (double)table[(long long)(GO2NN_ROBUST_ACC_FIRST + c) * N + e] : 1.0; }
+};
+
+#ifndef GO2_EMU
+__global__ void __launch_bounds__(EVAL_THREADS) go2nn_robust_begin_kernel(float* table, int N, float start) {
+  const long long k = (long long)blockIdx.x * EVAL_THREADS + threadIdx.x;
+  static_assert(GO2NN_ROBUST_STEP == 0, "the STEP row is the table's first N floats");
+  if (k < (long long)GO2NN_ROBUST_NUM * N) table[k] = k < N ? start : 0.f;
+}
+__global__ void __launch_bounds__(EVAL_THREADS) go2nn_robust_apply_kernel(const Go2nnRobustIn in, const Go2nnRobustSpec* specs, const int32_t* pert_of_env, float* table, int N) {
+  const int e = blockIdx.x * EVAL_THREADS + threadIdx.x;
+  if (e < N) robust_apply_env(in, specs, pert_of_env, table, N, e);
+}
+__global__ void __launch_bounds__(EVAL_THREADS) go2nn_robust_accumulate_kernel(const Go2nnRobustIn in, const Go2nnRobustSpec* specs, const int32_t* pert_of_env, float* table,
+                                                                                int N) {
+  const int e = blockIdx.x * EVAL_THREADS + threadIdx.x;
+  if (e < N) robust_accumulate_env(in, specs, pert_of_env, table, N, e);
+}
+// grid = (G, GO2NN_ROBUST_ACC_NUM + 1)
+__global__ void __launch_bounds__(EVAL_THREADS) go2nn_robust_reduce_kernel(const float* table, const int32_t* group, int N, double* out) {
+  const int g = blockIdx.x, c = blockIdx.y;
+  const double s = eval_group_sum(group, N, g, RobustTerm{table, N, c});
+  if (threadIdx.x == 0) out[(long long)g * (GO2NN_ROBUST_ACC_NUM + 1) + c] = s;
+}
+#endif
+
+static const char* robust_in_bad(const Go2nnRobustIn* in) {
+  const Go2nnEvalField* vec[] = {&in->root_states, &in->commands, &in->base_lin_vel, &in->projected_gravity, &in->motor_strengths, &in->p_gains_multiplier,
+                                 &in->d_gains_multiplier};
+  const Go2nnEvalField* scalar[] = {&in->reset_buf, &in->time_out_buf, &in->added_base_mass, &in->friction_coeffs};
+  for (const Go2nnEvalField* x : vec) {
+    if (!x->p) return "a null buffer pointer";
+    if (x->env_stride < 1 || x->comp_stride < 1) return "a vector field with an env stride or a component stride < 1";
+  }
+  for (const Go2nnEvalField* x : scalar) {
+    if (!x->p) return "a null buffer pointer";
+    if (x->env_stride < 1 || x->comp_stride < 0) return "a per-env field with an env stride < 1";
+  }
+  if (in->num_specs < 1 || in->num_specs > GO2NN_ROBUST_MAX_SPECS) return "num_specs outside [1, 64]";
+  return nullptr;
+}
+
+extern "C" {
+
+int go2nn_robust_check_specs(const Go2nnRobustSpec* specs, int32_t P) {
+  if (!specs) FAIL(GO2NN_EINVAL, "robust specs: null pointer");
+  if (P < 1 || P > GO2NN_ROBUST_MAX_SPECS) FAIL(GO2NN_EINVAL, "robust specs: P = %d perturbations (1 .. %d)", P, GO2NN_ROBUST_MAX_SPECS);
+  for (int p = 0; p < P; ++p) {
+    const Go2nnRobustSpec& s = specs[p];
+    if (s.hold < 1) FAIL(GO2NN_EINVAL, "robust spec %d: hold = %d steps (>= 1)", p, s.hold);
+    if (s.first < 0 || s.count < 0) FAIL(GO2NN_EINVAL, "robust spec %d: first = %d, count = %d (both >= 0)", p, s.first, s.count);
+    if (s.count > 0 && s.period < 1) FAIL(GO2NN_EINVAL, "robust spec %d: period = %d steps (>= 1 when count > 0)", p, s.period);
+    if (s.count > 0 && (s.window < 1 || s.window > s.period))
+      FAIL(GO2NN_EINVAL, "robust spec %d: window = %d steps (1 .. period = %d when count > 0: windows do not overlap)", p, s.window, s.period);
+  }
+  return 0;
+}
+
+int go2nn_robust_begin(float* table, int32_t N, int32_t start, void* stream) {
+  if (!table || N < 1) FAIL(GO2NN_EINVAL, "robust begin: bad argument (a table and N >= 1)");
+  const long long n = (long long)GO2NN_ROBUST_NUM * N;
+#ifdef GO2_EMU
+  (void)stream;
+  for (long long k = 0; k < n; ++k) table[k] = 0.f;
+  for (int e = 0; e < N; ++e) table[(long long)GO2NN_ROBUST_STEP * N + e] = (float)start;
+#else
+  hipLaunchKernelGGL(go2nn_robust_begin_kernel, dim3((unsigned)((n + EVAL_THREADS - 1) / EVAL_THREADS)), dim3(EVAL_THREADS), 0, (hipStream_t)stream, table, N, (float)start);
+  HIPCHK(hipGetLastError());
+#endif
+  return 0;
+}
+
+int go2nn_robust_apply(const Go2nnRobustIn* in, const Go2nnRobustSpec* specs, const int32_t* pert_of_env, float* table, int32_t N, void* stream) {
+  if (!in || !specs || !pert_of_env || !table || N < 1) FAIL(GO2NN_EINVAL, "robust apply: null argument or N < 1");
+  if (const char* bad = robust_in_bad(in)) FAIL(GO2NN_EINVAL, "robust apply: %s", bad);
+#ifdef GO2_EMU
+  (void)stream;
+  for (int e = 0; e < N; ++e) robust_apply_env(*in, specs, pert_of_env, table, N, e);
+#else
+  hipLaunchKernelGGL(go2nn_robust_apply_kernel, dim3((unsigned)((N + EVAL_THREADS - 1) / EVAL_THREADS)), dim3(EVAL_THREADS), 0, (hipStream_t)stream, *in, specs, pert_of_env,
+                     table, N);
+  HIPCHK(hipGetLastError());
+#endif
+  return 0;
+}
+
+int go2nn_robust_accumulate(const Go2nnRobustIn* in, const Go2nnRobustSpec* specs, const int32_t* pert_of_env, float* table, int32_t N, void* stream) {
+  if (!in || !specs || !pert_of_env || !table || N < 1) FAIL(GO2NN_EINVAL, "robust accumulate: null argument or N < 1");
+  if (const char* bad = robust_in_bad(in)) FAIL(GO2NN_EINVAL, "robust accumulate: %s", bad);
+#ifdef GO2_EMU
+  (void)stream;
+  for (int e = 0; e < N; ++e) robust_accumulate_env(*in, specs, pert_of_env, table, N, e);
+#else
+  hipLaunchKernelGGL(go2nn_robust_accumulate_kernel, dim3((unsigned)((N + EVAL_THREADS - 1) / EVAL_THREADS)), dim3(EVAL_THREADS), 0, (hipStream_t)stream, *in, specs,
+                     pert_of_env, table, N);
+  HIPCHK(hipGetLastError());
+#endif
+  return 0;
+}
+
+int go2nn_robust_reduce(const float* table, const int32_t* group, int32_t N, int32_t G, double* out, void* stream) {
+  if (!table || !group || !out || N < 1 || G < 1 || G > 65535) FAIL(GO2NN_EINVAL, "robust reduce: bad argument (1 <= G <= 65535)");
+#ifdef GO2_EMU
+  (void)stream;
+  for (int g = 0; g < G; ++g)
+    for (int c = 0; c < GO2NN_ROBUST_ACC_NUM + 1; ++c) out[(long long)g * (GO2NN_ROBUST_ACC_NUM + 1) + c] = eval_group_sum(group, N, g, RobustTerm{table, N, c});
+#else
+  hipLaunchKernelGGL(go2nn_robust_reduce_kernel, dim3((unsigned)G, GO2NN_ROBUST_ACC_NUM + 1), dim3(EVAL_THREADS), 0, (hipStream_t)stream, table, group, N, out);
+  HIPCHK(hipGetLastError());
+#endif
+  return 0;
+}
+
+}  // extern "C"
+
+#endif  // GO2NN_ROBUST_H

@@ -277,6 +277,12 @@ class LeggedRobotCfgPPO(BaseConfig):
         record = 0              # robots per (terrain x scenario) group whose per-step frames are recorded (utils/recorder.py -> eval_results/trace_<it>.npz); 0: no recorder exists
         scenarios = [["forward_1.0", 1.0, 0.0, 0.0], ["forward_2.0", 2.0, 0.0, 0.0], ["backward_1.0", -1.0, 0.0, 0.0], ["lateral_0.5", 0.0, 0.5, 0.0],
                      ["turn_1.0", 0.0, 0.0, 1.0], ["stand", 0.0, 0.0, 0.0]]          # name, vx [m/s], vy [m/s], yaw rate [rad/s]
+        perturbations = None    # None: ideal conditions only.  A list of [name, {field: value}] (fields: dv [m/s, heading frame], strength, kp_mul, kd_mul, added_mass [kg], friction); --robust: utils/evaluator.py DEFAULT_PERTURBATIONS
+        push_first_s = 1.0      # the push schedule of every perturbation, in counted time: first push, ...
+        push_period_s = 2.5     # ... time between two pushes (as many as have their whole window inside the horizon), ...
+        push_window_s = 2.0     # ... and the time after a push over which fall, recovery and peaks are scored (<= the period)
+        recover_thr = 0.3       # [m/s] recovered = the velocity error stays below this ...
+        recover_hold_s = 0.2    # ... for this long
 
 
 class LeggedRobotCfgCTS(BaseConfig):
@@ -341,6 +347,12 @@ class LeggedRobotCfgCTS(BaseConfig):
         record = 0              # robots per (terrain x scenario) group whose per-step frames are recorded (utils/recorder.py -> eval_results/trace_<it>.npz); 0: no recorder exists
         scenarios = [["forward_1.0", 1.0, 0.0, 0.0], ["forward_2.0", 2.0, 0.0, 0.0], ["backward_1.0", -1.0, 0.0, 0.0], ["lateral_0.5", 0.0, 0.5, 0.0],
                      ["turn_1.0", 0.0, 0.0, 1.0], ["stand", 0.0, 0.0, 0.0]]          # name, vx [m/s], vy [m/s], yaw rate [rad/s]
+        perturbations = None    # None: ideal conditions only.  A list of [name, {field: value}] (fields: dv [m/s, heading frame], strength, kp_mul, kd_mul, added_mass [kg], friction); --robust: utils/evaluator.py DEFAULT_PERTURBATIONS
+        push_first_s = 1.0      # the push schedule of every perturbation, in counted time: first push, ...
+        push_period_s = 2.5     # ... time between two pushes (as many as have their whole window inside the horizon), ...
+        push_window_s = 2.0     # ... and the time after a push over which fall, recovery and peaks are scored (<= the period)
+        recover_thr = 0.3       # [m/s] recovered = the velocity error stays below this ...
+        recover_hold_s = 0.2    # ... for this long
 
 
 class LeggedRobotCfgMoECTS(LeggedRobotCfgCTS):

@@ -3,6 +3,8 @@
 Loads a checkpoint of the task's experiment through the runner (like scripts/play.py), scores it with the native policy evaluator (utils/evaluator.py; the train
 config's `evaluation` section sets robots, horizon and scenarios), prints the per-terrain, per-command table and one JSON line.  --all_checkpoints walks every
 model_*.pt of the run and names the best one by --metric (lower is better for the error / effort metrics, higher for survival and speed_along_cmd).
+--robust also scores the default perturbations (pushes, payload, weak motors, soft gains, low friction: utils/evaluator.py DEFAULT_PERTURBATIONS); --metric then also
+takes push_falls, recovered, recovery_time_s, peak_lin_vel_err and peak_tilt.
 --record N also records N robots of every (terrain x scenario) group and writes eval_results/trace_<checkpoint number>.npz into the run's directory."""
 import json
 import os
@@ -15,7 +17,7 @@ from go2_rl_gym_amd.utils.evaluator import PolicyEvaluator, format_table
 from go2_rl_gym_amd.utils.helpers import _checkpoint_number, get_load_path
 from go2_rl_gym_amd.utils.task_registry import ROOT_DIR, task_registry
 
-HIGHER_IS_BETTER = ("survival", "speed_along_cmd")
+HIGHER_IS_BETTER = ("survival", "speed_along_cmd", "recovered")
 
 
 def _own_flags(argv):
@@ -57,6 +59,8 @@ def evaluate(argv=None, log_root="default"):
         res = ev.evaluate(runner.alg.actor_critic)
         print("== %s (%s)\n%s" % (p.name, res["mode"], format_table(res)))
         rows.append({"checkpoint": p.name, "overall": res["overall"], "groups": res["groups"]})
+        if res.get("perturbations") is not None:
+            rows[-1]["perturbations"] = res["perturbations"]
         if res.get("trace") is not None:
             from go2_rl_gym_amd.utils.recorder import write_trace
             print("trace: %s" % write_trace(os.path.join(str(p.parent), "eval_results", "trace_%s.npz" % _checkpoint_number(p)), res["trace"]))

@@ -18,6 +18,16 @@ Looking at the motion: with `evaluation.record = r > 0` a TrajectoryRecorder (ut
 counted steps — one more kernel call per step, after the accumulate call and inside the captured chunk —, evaluate() returns them as res["trace"] and write_results puts
 them next to the yaml as trace_<it>.npz.  The scores do not depend on it (the recorder only reads); with record = 0 no recorder exists.
 
+Beyond ideal conditions: with `evaluation.perturbations` (a list of [name, {field: value}]; DEFAULT_PERTURBATIONS is what --robust selects) every robot also belongs to one
+perturbation — a velocity impulse `dv` [m/s, heading frame] on a fixed schedule, and / or changed dynamics: `strength` (motor strength), `kp_mul`, `kd_mul`, `added_mass` [kg],
+`friction` (the robot's shape coefficient; the contact uses the mean of it and the terrain's).  Within a terrain kind the robots take the (scenario, perturbation) cells in
+turn.  Every perturbation carries the push schedule (`dv` defaults to 0: a sham push), so every cell has the same windows and `nominal` gives their baseline.  A step is then
+    { policy, go2nn_robust_apply, go2sim_step, write the commands, go2nn_eval_accumulate, go2nn_robust_accumulate }
+— two more launches (csrc/go2nn_robust.h; the formulas and the recovery rule are in include/go2nn.h), inside the captured chunk — and one more reduce at the end.  Per push:
+`push_falls` (share of pushes after which the robot fell inside the window), `recovered` (share after which the velocity error stayed below `recover_thr` for
+`recover_hold_s`), `recovery_time_s` (push -> end of that hold, mean over the recovered pushes), `peak_lin_vel_err` / `peak_tilt` (largest value inside the window, mean
+over pushes).  With `perturbations = None` nothing of this is allocated or launched.
+
 Isolated: nothing of the training env, the model, the optimizer or torch's generators is written; policy state the evaluation needs (the CTS observation history, the
 recurrent memory's hidden state) lives in buffers of the evaluator."""
 import copy
@@ -29,13 +39,18 @@ import numpy as np
 import torch
 
 from .. import _abi
-from .._nn import EVAL_FIELDS, EVAL_METRICS, GO2NN_EVAL_NUM, GO2NN_RNN_GRU, GO2NN_RNN_LSTM, Go2nnEvalIn, Go2nnFwdJob, Go2nnMlpIO, Go2nnRnnCellJob, PackedMlp
+from .._nn import (EVAL_FIELDS, EVAL_METRICS, GO2NN_EVAL_NUM, GO2NN_RNN_GRU, GO2NN_RNN_LSTM, GO2NN_ROBUST_ACC_NUM, GO2NN_ROBUST_MAX_SPECS, GO2NN_ROBUST_NUM, ROBUST_FIELDS, ROBUST_MASK,
+                   Go2nnEvalIn, Go2nnFwdJob, Go2nnMlpIO, Go2nnRnnCellJob, Go2nnRobustIn, Go2nnRobustSpec, PackedMlp)
 from .helpers import class_to_dict
 
 DEFAULT_SCENARIOS = [["forward_1.0", 1.0, 0.0, 0.0], ["forward_2.0", 2.0, 0.0, 0.0], ["backward_1.0", -1.0, 0.0, 0.0], ["lateral_0.5", 0.0, 0.5, 0.0],
                      ["turn_1.0", 0.0, 0.0, 1.0], ["stand", 0.0, 0.0, 0.0]]
 MEAN_METRICS = EVAL_METRICS[1:9]          # reported as per-step means; `falls` per robot, `survival`, `n_envs` next to them
 RESULT_KEYS = MEAN_METRICS + ("falls", "survival", "n_envs")
+# name, {field: value}; fields: dv [m/s: forward, left, up in the heading frame] and the dynamics values of ROBUST_MASK.  `nominal` is the sham push: the same windows, dv = 0
+DEFAULT_PERTURBATIONS = [["nominal", {}], ["push_front_1.0", {"dv": [1.0, 0.0, 0.0]}], ["push_side_1.0", {"dv": [0.0, 1.0, 0.0]}], ["payload_3kg", {"added_mass": 3.0}],
+                         ["motor_0.8", {"strength": 0.8}], ["kp_0.8", {"kp_mul": 0.8}], ["friction_0.3", {"friction": 0.3}]]
+ROBUST_KEYS = ("pushes", "push_falls", "recovered", "recovery_time_s", "peak_lin_vel_err", "peak_tilt")
 MAX_CHUNK = 50
 # The accumulate kernel runs AFTER the env step, when the simulator has already rolled its action history (last_actions = this step's actions): the previous step's
 # actions — the kernel's `last_actions` input — are then in the simulator's last_last_actions buffer.
@@ -69,6 +84,9 @@ def evaluation_env_cfg(env_cfg, ev):
     cm.dynamic_resample_commands = False
     cm.command_range_curriculum = []
     cm.zero_command_curriculum = None
+    if any("strength" in (p[1] or {}) for p in (_get(ev, "perturbations") or [])):
+        # the simulator applies motor_strengths only when it was created with the randomisation on: on, with the range [1, 1] — a reset draws exactly 1, a product with 1 is exact
+        dr.randomize_motor_strength, dr.motor_strength_range = True, [1.0, 1.0]
     return cfg
 
 
@@ -222,17 +240,20 @@ def _make_policy(ev, model):
 
 # ---------------------------------------------------------------------------------------------------------------------------------------------------------------
 class PolicyEvaluator:
-    def __init__(self, env_cfg, evaluation, task_class=None, sim_params=None, device="cuda:0", lib=None, nn_lib=None, step_callback=None):
+    def __init__(self, env_cfg, evaluation, task_class=None, sim_params=None, device="cuda:0", lib=None, nn_lib=None, step_callback=None, apply_callback=None):
         """env_cfg: the task's env config (copied, never modified);  evaluation: the train config's `evaluation` section (class or dict).
         lib / nn_lib: the go2sim / go2nn libraries — tests hand in the CPU oracle and the host build; the product passes neither and runs on the HIP libraries or not at all.
-        step_callback(evaluator, step, counted): called after every eager step with the buffers the accumulate kernel has just read (tests record them)."""
+        step_callback(evaluator, step, counted): called after every eager step with the buffers the accumulate kernel has just read (tests record them).
+        apply_callback(evaluator, step, counted): with perturbations, called in every eager step right after go2nn_robust_apply, before the simulator steps."""
         from ..envs.base.legged_robot import LeggedRobot
         self.ev = evaluation
         self.cfg = evaluation_env_cfg(env_cfg, evaluation)
         self.task_class = task_class or LeggedRobot
         self.sim_params = sim_params
         self._lib, self.device_arg = lib, device
-        self.step_callback = step_callback
+        self.step_callback, self.apply_callback = step_callback, apply_callback
+        perts = _get(evaluation, "perturbations")
+        self.perturbations = [[str(p[0]), dict(p[1] or {})] for p in perts] if perts else None
         self.scenarios = [list(s) for s in (_get(evaluation, "scenarios") or DEFAULT_SCENARIOS)]
         self.terrain_level = int(_get(evaluation, "terrain_level", 5))
         self.num_envs = self.cfg.env.num_envs
@@ -254,14 +275,16 @@ class PolicyEvaluator:
         self._build_groups()
         N = self.num_envs
         self.acc = torch.zeros(GO2NN_EVAL_NUM, N, device=self.device)
-        self.out = torch.zeros(len(self.groups), GO2NN_EVAL_NUM + 2, dtype=torch.float64, device=self.device)
+        self.out = torch.zeros(self.num_cells, GO2NN_EVAL_NUM + 2, dtype=torch.float64, device=self.device)
+        if self.perturbations is not None:
+            self._build_robust()
         self.dof_limits = self.env.dof_pos_limits.contiguous().clone()
         self._policy, self._policy_of = None, None
         self.recorder = None
         per_group = int(_get(evaluation, "record", 0) or 0)
         if per_group > 0:          # the first `record` env indices of every group, for the counted steps
             from .recorder import TrajectoryRecorder
-            ids = np.sort(np.concatenate([np.nonzero(self.group_host == g)[0][:per_group] for g in range(len(self.groups))]))
+            ids = np.sort(np.concatenate([np.nonzero(self.cell_host == g)[0][:per_group] for g in range(self.num_cells)]))          # (a cell is a group without perturbations)
             self.recorder = TrajectoryRecorder(self.env, ids, self.steps, nn_lib=self.nn)
         self.evaluations = 0
         self.last_mode = None          # "eager" / "graph": how the latest evaluation's steps ran
@@ -295,9 +318,10 @@ class PolicyEvaluator:
 
     def _build_groups(self):
         """env -> (terrain kind x scenario) group, built once on the host: the kinds are those of the columns the envs stand in (one kind, 'plane', without a terrain mesh);
-        within a kind the envs take the scenarios in turn, so the groups of a kind differ by at most one env"""
+        within a kind the envs take the scenarios in turn, so the groups of a kind differ by at most one env.  With P perturbations they take the (scenario, perturbation)
+        CELLS in turn; cell index = (terrain * S + scenario) * P + perturbation — the kernels' group —, and a group is the union of its P cells (P = 1 without)"""
         from .terrain import KIND_NAMES
-        N, S = self.num_envs, len(self.scenarios)
+        N, S, P = self.num_envs, len(self.scenarios), len(self.perturbations or [None])
         if self.env.custom_origins:
             kind_of_env = self.env.terrain_cols2id.cpu().numpy()[self.env.terrain_types.cpu().numpy()]
             kinds = [int(k) for k in sorted(set(kind_of_env.tolist()))]
@@ -305,18 +329,55 @@ class PolicyEvaluator:
         else:
             kind_of_env, kinds, self.terrain_names = np.zeros(N, np.int64), [0], ["plane"]
         group = np.zeros(N, np.int32)
-        scen = np.zeros(N, np.int64)
+        scen, pert = np.zeros(N, np.int64), np.zeros(N, np.int32)
         for ki, k in enumerate(kinds):
             ids = np.nonzero(kind_of_env == k)[0]
-            scen[ids] = np.arange(len(ids)) % S
+            turn = np.arange(len(ids)) % (S * P)
+            scen[ids], pert[ids] = turn // P, turn % P
             group[ids] = ki * S + scen[ids]
         self.groups = [(t, s[0]) for t in self.terrain_names for s in self.scenarios]
-        self.group_host = group
-        self.group = torch.from_numpy(group).to(self.device)
+        self.group_host, self.pert_host = group, pert
+        self.cell_host, self.num_cells = group * P + pert, len(self.groups) * P
+        self.group = torch.from_numpy(self.cell_host).to(self.device)          # what the reduce kernels group by
         cmd = np.zeros((N, 4), np.float32)
         cmd[:, :3] = np.asarray([s[1:4] for s in self.scenarios], np.float32)[scen]
         self.commands_host = cmd
         self.commands = torch.from_numpy(cmd).to(self.device)
+
+    def _build_robust(self):
+        """the perturbations as the kernels read them: P specs and the env -> perturbation map in device memory, the per-env table and the reduce output"""
+        ev, perts, P = self.ev, self.perturbations, len(self.perturbations)
+        if P > GO2NN_ROBUST_MAX_SPECS or len({p[0] for p in perts}) != P:
+            raise ValueError("evaluation.perturbations: 1 .. %d perturbations with distinct names, got %r" % (GO2NN_ROBUST_MAX_SPECS, [p[0] for p in perts]))
+        steps_of = lambda key, default: int(round(float(_get(ev, key, default)) / self.dt))
+        first, period, window = steps_of("push_first_s", 1.0), max(1, steps_of("push_period_s", 2.5)), max(1, steps_of("push_window_s", 2.0))
+        hold, thr = max(1, steps_of("recover_hold_s", 0.2)), float(_get(ev, "recover_thr", 0.3))
+        # every window closes inside the horizon: the window of the push at step s ends with the accumulate call of step s + window - 1
+        count = (self.steps - first - window) // period + 1 if self.steps - first - window >= 0 else 0
+        self.push_first, self.push_period, self.push_window, self.push_hold, self.push_count = first, period, window, hold, count
+        self.push_steps = np.asarray([first + k * period for k in range(count)], np.int64)
+        specs = (Go2nnRobustSpec * P)()
+        for sp, (name, fields) in zip(specs, perts):
+            unknown = set(fields) - {"dv"} - set(ROBUST_MASK)
+            if unknown:
+                raise ValueError("perturbation %r: unknown field(s) %s (dv, %s)" % (name, sorted(unknown), ", ".join(ROBUST_MASK)))
+            sp.dv[:] = [float(x) for x in fields.get("dv", (0.0, 0.0, 0.0))]
+            sp.first, sp.period, sp.count, sp.window, sp.hold, sp.thr = first, period, count, window, hold, thr
+            sp.strength, sp.kp_mul, sp.kd_mul, sp.added_mass, sp.friction = 1.0, 1.0, 1.0, 0.0, 1.0
+            for k, bit in ROBUST_MASK.items():
+                if k in fields:
+                    setattr(sp, k, float(fields[k]))
+                    sp.mask |= bit
+        self._check(self.nn.go2nn_robust_check_specs(C.cast(specs, C.c_void_p), P), "go2nn_robust_check_specs")
+        self.specs_host = specs
+        self.specs = torch.from_numpy(np.frombuffer(bytes(specs), np.uint8).copy()).to(self.device)
+        self.pert = torch.from_numpy(self.pert_host).to(self.device)
+        self.rtable = torch.zeros(GO2NN_ROBUST_NUM, self.num_envs, device=self.device)
+        self.rout = torch.zeros(self.num_cells, GO2NN_ROBUST_ACC_NUM + 1, dtype=torch.float64, device=self.device)
+        sizes = np.bincount(self.cell_host, minlength=self.num_cells)
+        if sizes.min() < 4:
+            print("[go2_rl_gym_amd] evaluation: %d of %d (terrain x scenario x perturbation) cells have fewer than 4 robots (smallest: %d); raise evaluation.num_envs"
+                  % (int((sizes < 4).sum()), self.num_cells, int(sizes.min())))
 
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream) if self.on_device else None
@@ -324,6 +385,18 @@ class PolicyEvaluator:
     def _check(self, rc, what):
         if rc != 0:
             raise RuntimeError("%s failed: %s" % (what, self.nn.go2nn_last_error().decode()))
+
+    def _robust_in(self):
+        """the perturbation kernels' view of the simulator's buffers (as _eval_in)"""
+        b, a = self.env._buf, Go2nnRobustIn()
+        for name in ROBUST_FIELDS:
+            t, f = b[name], getattr(a, name)
+            f.p, f.env_stride, f.comp_stride = t.data_ptr(), t.stride(0), (t.stride(1) if t.dim() > 1 else 0)
+        a.num_specs = len(self.perturbations)
+        return a
+
+    def _robust(self, fn, what, rin):
+        self._check(fn(C.byref(rin), C.c_void_p(self.specs.data_ptr()), C.c_void_p(self.pert.data_ptr()), C.c_void_p(self.rtable.data_ptr()), self.num_envs, self._stream()), what)
 
     def _eval_in(self):
         """the accumulate kernel's view of the simulator's buffers: (pointer, env stride, component stride) in elements from the torch views' own strides"""
@@ -338,12 +411,19 @@ class PolicyEvaluator:
         return a
 
     # ------------------------------------------------------------------ one env step of the evaluation (pure enqueue)
-    def _step(self, pol, ein):
+    def _step(self, pol, ein, rin=None, k=None):
+        """rin: the perturbation kernels' input (None without perturbations);  k: the step's index in an eager run (None inside a capture: no callback there)"""
         env = self.env
         actions = pol.act(env.obs_buf)
+        if rin is not None:
+            self._robust(self.nn.go2nn_robust_apply, "go2nn_robust_apply", rin)
+            if k is not None and self.apply_callback is not None:
+                self.apply_callback(self, k, k >= self.warmup_steps)
         _abi.check(env.lib, env.lib.go2sim_step(env.handle, C.c_void_p(actions.data_ptr()), self._stream()), "go2sim_step")
         env.commands.copy_(self.commands)          # a robot that fell was reset by the step and drew a new command: the scenario's command holds
         self._check(self.nn.go2nn_eval_accumulate(C.byref(ein), C.c_void_p(self.acc.data_ptr()), self.num_envs, self._stream()), "go2nn_eval_accumulate")
+        if rin is not None:
+            self._robust(self.nn.go2nn_robust_accumulate, "go2nn_robust_accumulate", rin)
         if self.recorder is not None:
             self.recorder.record()
         pol.after_step(env.obs_buf, env._buf["reset_buf"])
@@ -353,15 +433,15 @@ class PolicyEvaluator:
         if self.recorder is not None:
             self.recorder.clear()
 
-    def _run_eager(self, pol, ein):
+    def _run_eager(self, pol, ein, rin):
         for k in range(self.warmup_steps + self.steps):
             if k == self.warmup_steps:
                 self._clear()
-            self._step(pol, ein)
+            self._step(pol, ein, rin, k)
             if self.step_callback is not None:
                 self.step_callback(self, k, k >= self.warmup_steps)
 
-    def _run_graph(self, pol, ein):
+    def _run_graph(self, pol, ein, rin):
         """capture `chunk` steps on this evaluation's simulator, replay them for the whole horizon -> False if the capture failed (nothing has run then)"""
         from ..rsl_rl.algorithms._graph import no_gc, strict_graphs
         torch.cuda.synchronize(self.device)
@@ -369,7 +449,7 @@ class PolicyEvaluator:
         try:
             with no_gc(), torch.cuda.graph(g):
                 for _ in range(self.chunk):
-                    self._step(pol, ein)
+                    self._step(pol, ein, rin)
         except Exception as e:      # noqa: BLE001
             if strict_graphs():
                 raise RuntimeError("HIP-graph capture of the evaluation failed (%s: %s)" % (type(e).__name__, e)) from e
@@ -405,22 +485,32 @@ class PolicyEvaluator:
             if self.recorder is not None:
                 self.recorder.bind(env)
             self._clear()
-            ein = self._eval_in()
+            ein, rin = self._eval_in(), None
+            if self.perturbations is not None:          # the table's step counter starts at -warmup_steps: nothing is pushed or counted before step 0, no clear at the boundary
+                rin = self._robust_in()
+                self._check(self.nn.go2nn_robust_begin(C.c_void_p(self.rtable.data_ptr()), self.num_envs, -self.warmup_steps, self._stream()), "go2nn_robust_begin")
             replay = bool(_get(self.ev, "replay", False))
             graph = (replay and self.on_device and self.evaluations > 0 and self.step_callback is None) if use_graph is None else bool(use_graph and self.on_device)
-            done = graph and self._run_graph(pol, ein)
+            done = graph and self._run_graph(pol, ein, rin)
             if not done:
-                self._run_eager(pol, ein)
+                self._run_eager(pol, ein, rin)
             self.last_mode = "graph" if done else "eager"
-            self._check(self.nn.go2nn_eval_reduce(C.c_void_p(self.acc.data_ptr()), C.c_void_p(self.group.data_ptr()), self.num_envs, len(self.groups),
+            self._check(self.nn.go2nn_eval_reduce(C.c_void_p(self.acc.data_ptr()), C.c_void_p(self.group.data_ptr()), self.num_envs, self.num_cells,
                                                   C.c_void_p(self.out.data_ptr()), self._stream()), "go2nn_eval_reduce")
-            table = self.out.cpu().numpy().copy()          # the one device -> host copy (and synchronisation) of an evaluation
+            rtable = None
+            if rin is not None:
+                self._check(self.nn.go2nn_robust_reduce(C.c_void_p(self.rtable.data_ptr()), C.c_void_p(self.group.data_ptr()), self.num_envs, self.num_cells,
+                                                        C.c_void_p(self.rout.data_ptr()), self._stream()), "go2nn_robust_reduce")
+                rtable = self.rout.cpu().numpy().copy()
+            table = self.out.cpu().numpy().copy()          # the device -> host copy (and synchronisation) of an evaluation
             trace = self.recorder.fetch() if self.recorder is not None else None
             self._graph = None
             self.evaluations += 1
-        res = self._results(table)
+        res = self._results(table, rtable)
         if trace is not None:
             trace.update(group_of_robot=self.group_host[trace["env_ids"]].copy(), terrain_names=list(self.terrain_names), scenarios=[s[0] for s in self.scenarios])
+            if self.perturbations is not None:          # push_steps: the counted steps (= frame indices) whose go2nn_robust_apply pushed; the frame holds the state AFTER that step
+                trace.update(perturbations=[p[0] for p in self.perturbations], pert_of_robot=self.pert_host[trace["env_ids"]].copy(), push_steps=self.push_steps.copy())
             res["trace"] = trace
         return res
 
@@ -434,11 +524,31 @@ class PolicyEvaluator:
         d["n_envs"] = int(n)
         return d
 
-    def _results(self, table):
-        S = len(self.scenarios)
+    def _robust_row(self, r):
+        """one row of go2nn_robust_reduce (sums of the six accumulators, envs) -> the per-push figures; without a push (a recovered push) they are NaN"""
+        pushes, rec = float(r[0]), float(r[2])
+        per_push = lambda x: float(x) / pushes if pushes > 0 else float("nan")
+        return {"pushes": int(pushes), "push_falls": per_push(r[1]), "recovered": per_push(r[2]), "recovery_time_s": float(r[3]) / rec * self.dt if rec > 0 else float("nan"),
+                "peak_lin_vel_err": per_push(r[4]), "peak_tilt": per_push(r[5])}
+
+    def _results(self, cells, rcells=None):
+        """cells: the eval reduce table per (terrain, scenario, perturbation) cell; rcells: the robust one (None without perturbations: a cell is a group then)"""
+        S, P = len(self.scenarios), len(self.perturbations or [None])
+        table = cells.reshape(len(self.groups), P, -1).sum(1)          # P = 1: the cells' rows themselves
         groups = {t: {s[0]: self._row(table[ti * S + si]) for si, s in enumerate(self.scenarios)} for ti, t in enumerate(self.terrain_names)}
-        return {"overall": self._row(table.sum(0)), "groups": groups, "terrain_names": list(self.terrain_names), "scenarios": [s[0] for s in self.scenarios],
-                "steps": self.steps, "dt": self.dt, "mode": self.last_mode, "table": table}
+        res = {"overall": self._row(table.sum(0)), "groups": groups, "terrain_names": list(self.terrain_names), "scenarios": [s[0] for s in self.scenarios],
+               "steps": self.steps, "dt": self.dt, "mode": self.last_mode, "table": table}
+        if rcells is not None:
+            both = lambda e, r: dict(self._row(e), **self._robust_row(r))
+            names = [p[0] for p in self.perturbations]
+            c3, r3 = cells.reshape(len(self.groups), P, -1), rcells.reshape(len(self.groups), P, -1)
+            res["cells"] = {t: {s[0]: {n: both(c3[ti * S + si, pi], r3[ti * S + si, pi]) for pi, n in enumerate(names)} for si, s in enumerate(self.scenarios)}
+                            for ti, t in enumerate(self.terrain_names)}
+            res["perturbations"] = {n: both(c3[:, pi].sum(0), r3[:, pi].sum(0)) for pi, n in enumerate(names)}
+            res["overall"].update(self._robust_row(rcells.sum(0)))
+            res.update(perturbation_names=names, cell_table=cells, robust_table=rcells, push_steps=self.push_steps.tolist(),
+                       push={"first": self.push_first, "period": self.push_period, "window": self.push_window, "hold": self.push_hold, "count": self.push_count})
+        return res
 
     def close(self):
         if self.env is not None:
@@ -448,17 +558,22 @@ class PolicyEvaluator:
 
 # ---------------------------------------------------------------------------------------------------------------------------------------------------------------
 def scalars(res):
-    """[(tag, value)]: 'Eval/<metric>' for the overall figures, 'Eval/<terrain>/<scenario>/<metric>' per group"""
+    """[(tag, value)]: 'Eval/<metric>' for the overall figures, 'Eval/<terrain>/<scenario>/<metric>' per group and, with perturbations, 'Eval/robust/<name>/<metric>'"""
     out = [("Eval/" + k, res["overall"][k]) for k in RESULT_KEYS]
     for t, per in res["groups"].items():
         for s, d in per.items():
             out += [("Eval/%s/%s/%s" % (t, s, k), d[k]) for k in RESULT_KEYS]
+    for n, d in (res.get("perturbations") or {}).items():
+        out += [("Eval/robust/%s/%s" % (n, k), d[k]) for k in RESULT_KEYS + ROBUST_KEYS]
     return out
 
 
 def results_dict(res, it=None):
     """what eval_results/results_{it}.yaml holds (plain Python numbers)"""
     d = {"iteration": it, "steps": res["steps"], "dt": res["dt"], "overall": dict(res["overall"]), "groups": {t: {s: dict(v) for s, v in per.items()} for t, per in res["groups"].items()}}
+    if res.get("perturbations") is not None:
+        d["perturbations"] = {n: dict(v) for n, v in res["perturbations"].items()}
+        d["push"] = dict(res["push"])
     return d
 
 
@@ -468,6 +583,12 @@ def format_table(res):
     rows = [(t, s, d) for t, per in res["groups"].items() for s, d in per.items()] + [("all", "all", res["overall"])]
     for t, s, d in rows:
         lines.append("%-16s %-14s " % (t, s) + " ".join("%15.4f" % d[c] if c != "n_envs" else "%15d" % d[c] for c in cols))
+    if res.get("perturbations") is not None:          # the second block: one line per perturbation, over every terrain and scenario
+        cols = ("lin_vel_err", "torque_sq", "falls", "survival") + ROBUST_KEYS + ("n_envs",)
+        whole = ("pushes", "n_envs")
+        lines += ["", "%-20s " % "perturbation" + " ".join("%16s" % c for c in cols)]
+        for n, d in list(res["perturbations"].items()) + [("all", res["overall"])]:
+            lines.append("%-20s " % n + " ".join("%16d" % d[c] if c in whole else "%16.4f" % d[c] for c in cols))
     return "\n".join(lines)
 
 

@@ -352,6 +352,77 @@ typedef struct Go2nnTraceIn {
 int go2nn_trace_record(const Go2nnTraceIn* in, const int32_t* env_ids, int32_t K, float* frames, int32_t* cursor, int32_t T, void* stream);
 int go2nn_trace_clear(int32_t* cursor, void* stream);          /* *cursor = 0; the frames are left as they are */
 
+/* ---- the evaluator's perturbations: scheduled pushes, perturbed dynamics and what happens next (go2_rl_gym_amd/utils/evaluator.py, `evaluation.perturbations`).
+ * ADDED WITHIN ABI 7: five new entry points, nothing existing changes, GO2NN_ABI_VERSION stays 7.
+ * A perturbed evaluation step is { policy, go2nn_robust_apply, go2sim_step, go2nn_eval_accumulate, go2nn_robust_accumulate }: two more plain launches per step
+ * (capturable; one lane per env, no atomics), and one go2nn_robust_reduce at the end.  Every env e belongs to one perturbation pert_of_env[e] in [0, P), P <= 64;
+ * an env with pert_of_env[e] outside [0, P) is left alone (only its step counter runs).
+ * A perturbation is one Go2nnRobustSpec (an array of P of them in the buffers' memory space):
+ *   dv[3]                  velocity impulse [m/s] in the robot's HEADING frame: x forward, y left, z up
+ *   first, period, count   the push schedule in counted steps: a push fires at step s when s >= first, (s - first) % period == 0 and (s - first) / period < count;
+ *                          count = 0: no pushes
+ *   window W, hold H, thr  the recovery rule (below), W and H in steps, thr in m/s
+ *   strength, kp_mul, kd_mul, added_mass, friction   the values written to the env's rows of motor_strengths, p_gains_multiplier, d_gains_multiplier (all 12 joints),
+ *                          added_base_mass [kg] and friction_coeffs; only the rows named in `mask` are written.  Identity: 1, 1, 1, 0 and the simulator's own friction.
+ *                          friction is the robot's SHAPE coefficient: the simulator's contact uses the mean of it and the terrain's (go2sim_impl.cpp lane_load_phys: ph.mu).
+ *                          The simulator multiplies torques by motor_strengths only when it was created with randomize_motor_strength set.
+ * The table: fp32 [GO2NN_ROBUST_NUM, N], row-major by row of the enum below, column e = env e.
+ * go2nn_robust_begin: table = 0, then STEP[e] = start for every e (the evaluator passes -warmup_steps: nothing is pushed while STEP < 0 when first >= 0).
+ * go2nn_robust_apply (BEFORE go2sim_step), per env with a perturbation:
+ *   the masked dynamics rows are rewritten (every step: idempotent, and a reset inside the step cannot erase them);
+ *   if a push fires at s = STEP[e]:  root_states[e, 7:10] += (c dv_x - s dv_y, s dv_x + c dv_y, dv_z) with the heading (c, s) = (1 - 2 (y^2 + z^2), 2 (x y + w z)) of the root
+ *   quaternion (x, y, z, w) = root_states[e, 3:7], normalised, (1, 0) if its norm is below 1e-6 (no trigonometric function is evaluated);
+ *   OPEN = 1, PEAK_ERR = PEAK_TILT = OK_RUN = DONE = 0, PUSHES += 1.
+ * go2nn_robust_accumulate (AFTER the step), per env: err = |cmd_xy - v_xy|_2 (as LIN_VEL_ERR above), tilt = |g_xy|_2, fall = reset_buf and not time_out_buf.
+ *   With a perturbation and OPEN > 0 (a window is open, this being its OPEN-th step):
+ *     if not DONE:  PEAK_ERR = max(PEAK_ERR, err), PEAK_TILT = max(PEAK_TILT, tilt);
+ *                   fall:            PUSH_FALLS += 1, DONE = 1
+ *                   else err < thr:  OK_RUN += 1; at OK_RUN == H:  RECOVERED += 1, RECOVERY_STEPS += OPEN, DONE = 1
+ *                   else:            OK_RUN = 0
+ *     OPEN == W:  PEAK_ERR_SUM += PEAK_ERR, PEAK_TILT_SUM += PEAK_TILT, OPEN = 0 (closed);  otherwise OPEN += 1
+ *   Always: STEP += 1 — the step counter lives in the table, so a captured launch advances on every replay.
+ * The scores are per PUSH: a robot that falls after its window has closed, or outside any window, counts in the evaluator's FALLS only. */
+enum {
+  GO2NN_ROBUST_STEP = 0, GO2NN_ROBUST_OPEN, GO2NN_ROBUST_PEAK_ERR, GO2NN_ROBUST_PEAK_TILT, GO2NN_ROBUST_OK_RUN, GO2NN_ROBUST_DONE,
+  GO2NN_ROBUST_PUSHES, GO2NN_ROBUST_PUSH_FALLS, GO2NN_ROBUST_RECOVERED, GO2NN_ROBUST_RECOVERY_STEPS, GO2NN_ROBUST_PEAK_ERR_SUM, GO2NN_ROBUST_PEAK_TILT_SUM, GO2NN_ROBUST_NUM
+};
+#define GO2NN_ROBUST_ACC_FIRST GO2NN_ROBUST_PUSHES                          /* rows below it are per-env state, rows from it on are accumulators */
+#define GO2NN_ROBUST_ACC_NUM (GO2NN_ROBUST_NUM - GO2NN_ROBUST_ACC_FIRST)
+#define GO2NN_ROBUST_MAX_SPECS 64
+#define GO2NN_ROBUST_MASK_STRENGTH 1
+#define GO2NN_ROBUST_MASK_KP 2
+#define GO2NN_ROBUST_MASK_KD 4
+#define GO2NN_ROBUST_MASK_ADDED_MASS 8
+#define GO2NN_ROBUST_MASK_FRICTION 16
+typedef struct Go2nnRobustSpec {
+  float dv[3];
+  int32_t first, period, count;
+  int32_t window, hold;
+  float thr;
+  float strength, kp_mul, kd_mul, added_mass, friction;
+  int32_t mask;
+  int32_t pad_;
+} Go2nnRobustSpec;
+/* The buffers as (pointer, env stride, component stride) in ELEMENTS like Go2nnEvalIn's.  root_states [N,13], commands, base_lin_vel, projected_gravity as above;
+ * reset_buf / time_out_buf uint8; motor_strengths, p_gains_multiplier, d_gains_multiplier [N,12]; added_base_mass, friction_coeffs [N] (comp_stride unused).
+ * The five dynamics buffers and root_states are WRITTEN by go2nn_robust_apply.  num_specs = P. */
+typedef struct Go2nnRobustIn {
+  Go2nnEvalField root_states, commands, base_lin_vel, projected_gravity, reset_buf, time_out_buf;
+  Go2nnEvalField motor_strengths, p_gains_multiplier, d_gains_multiplier, added_base_mass, friction_coeffs;
+  int32_t num_specs;
+  int32_t pad_;
+} Go2nnRobustIn;
+/* Host-side check of P specs in HOST memory, before they are copied to the buffers' memory space (the launches cannot read them back): GO2NN_EINVAL with a message for
+ * P outside [1, 64], a null pointer, hold < 1, first < 0, count < 0, and — where count > 0 — period < 1, window < 1 or window > period (windows never overlap). */
+int go2nn_robust_check_specs(const Go2nnRobustSpec* host_specs, int32_t P);
+int go2nn_robust_begin(float* table, int32_t N, int32_t start, void* stream);
+/* GO2NN_EINVAL for null pointers, N < 1, num_specs outside [1, 64], an env stride < 1 or (vector fields) a component stride < 1. */
+int go2nn_robust_apply(const Go2nnRobustIn* in, const Go2nnRobustSpec* specs, const int32_t* pert_of_env, float* table, int32_t N, void* stream);
+int go2nn_robust_accumulate(const Go2nnRobustIn* in, const Go2nnRobustSpec* specs, const int32_t* pert_of_env, float* table, int32_t N, void* stream);
+/* out [G, GO2NN_ROBUST_ACC_NUM + 1] (fp64): per group the sums of the accumulator rows over its envs, then the number of its envs — the summation scheme (and the device
+ * function) of go2nn_eval_reduce: fixed order, bit-equal outputs for equal inputs, group ids outside [0, G) ignored, an empty group gives zeros.  1 <= G <= 65535. */
+int go2nn_robust_reduce(const float* table, const int32_t* group, int32_t N, int32_t G, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

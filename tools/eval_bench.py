@@ -1,6 +1,6 @@
 """What one policy evaluation costs (utils/evaluator.py), and what the metric kernel saves over torch expressions.
 
-    python tools/eval_bench.py [--task go2_flat] [--reps 3] [--out profiles/eval_bench.json]
+    python tools/eval_bench.py [--task go2_flat] [--reps 3] [--robust] [--out profiles/eval_bench.json]
 
 Measures, on cuda:0, with the task's default `evaluation` section (1024 robots, 1 s + 10 s):
   * wall time of evaluate() run eagerly and with the captured chunk of steps replayed (simulator re-creation, capture and the final host copy included: it is what
@@ -8,6 +8,8 @@ Measures, on cuda:0, with the task's default `evaluation` section (1024 robots, 
   * go2nn_eval_accumulate per launch, from device events around 200 back-to-back launches on the evaluator's own buffers (for the kernel's own duration run this tool
     under `rocprofv3 --kernel-trace --stats -- python tools/eval_bench.py --kernel_only` and read go2nn_eval_accumulate_kernel);
   * the same ten per-step terms written as torch expressions on the same (strided) buffers, per step, eager and replayed from a HIP graph.
+--robust: the same with the default perturbations on (evaluation.perturbations = DEFAULT_PERTURBATIONS), plus go2nn_robust_apply + go2nn_robust_accumulate per pair of
+back-to-back launches; the torch-expression comparison is left out.
 Writes one JSON file and prints it."""
 import argparse
 import ctypes as C
@@ -23,7 +25,7 @@ sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 
 from go2_rl_gym_amd.envs import task_registry  # noqa: E402
-from go2_rl_gym_amd.utils.evaluator import EVAL_SOURCE, PolicyEvaluator  # noqa: E402
+from go2_rl_gym_amd.utils.evaluator import DEFAULT_PERTURBATIONS, EVAL_SOURCE, PolicyEvaluator  # noqa: E402
 from go2_rl_gym_amd.utils.helpers import class_to_dict  # noqa: E402
 
 
@@ -61,20 +63,34 @@ def main():
     p.add_argument("--task", default="go2_flat")
     p.add_argument("--reps", type=int, default=3)
     p.add_argument("--kernel_only", action="store_true")
+    p.add_argument("--robust", action="store_true")
     p.add_argument("--out", default=os.path.join(ROOT, "profiles", "eval_bench.json"))
     a = p.parse_args()
     env_cfg, train_cfg = task_registry.get_cfgs(a.task)
-    ev = PolicyEvaluator(env_cfg, class_to_dict(train_cfg.evaluation), task_class=task_registry.get_task_class(a.task), device="cuda:0")
+    ev_cfg = class_to_dict(train_cfg.evaluation)
+    if a.robust:
+        ev_cfg["perturbations"] = [[n, dict(f)] for n, f in DEFAULT_PERTURBATIONS]
+    ev = PolicyEvaluator(env_cfg, ev_cfg, task_class=task_registry.get_task_class(a.task), device="cuda:0")
     from go2_rl_gym_amd.rsl_rl.modules import ActorCritic
     torch.manual_seed(0)
     ac = ActorCritic(45, 263, 12, **{k: v for k, v in class_to_dict(train_cfg.policy).items() if k in ("actor_hidden_dims", "critic_hidden_dims", "activation", "init_noise_std")}).to("cuda:0")
-    out = {"task": a.task, "device": torch.cuda.get_device_name(0), "num_envs": ev.num_envs, "steps": ev.warmup_steps + ev.steps, "chunk": ev.chunk}
+    out = {"task": a.task, "device": torch.cuda.get_device_name(0), "num_envs": ev.num_envs, "steps": ev.warmup_steps + ev.steps, "chunk": ev.chunk,
+           "perturbations": [n for n, _ in ev.perturbations] if ev.perturbations else None}
     ev.evaluate(ac, use_graph=False)
     ein, st = ev._eval_in(), ev._stream()
     acc_fn = lambda: ev.nn.go2nn_eval_accumulate(C.byref(ein), C.c_void_p(ev.acc.data_ptr()), ev.num_envs, st)
     timed(acc_fn, 20)
     dev_us, wall_us = timed(acc_fn, 200)
     out["accumulate_kernel"] = {"device_us_per_launch_back_to_back": dev_us, "host_us_per_call": wall_us}
+    if a.robust:
+        rin = ev._robust_in()
+
+        def pair():
+            ev._robust(ev.nn.go2nn_robust_apply, "go2nn_robust_apply", rin)
+            ev._robust(ev.nn.go2nn_robust_accumulate, "go2nn_robust_accumulate", rin)
+        timed(pair, 20)
+        dev_us, wall_us = timed(pair, 200)
+        out["robust_apply_plus_accumulate"] = {"device_us_per_pair_back_to_back": dev_us, "host_us_per_pair": wall_us}
     if not a.kernel_only:
         walls = {"eager": [], "replayed": []}
         for _ in range(a.reps):
@@ -85,6 +101,7 @@ def main():
                 walls[mode].append((time.perf_counter() - t0) * 1e3)
                 assert res["mode"] == ("graph" if g else "eager")
         out["evaluate_wall_ms"] = {m: {"best": min(w), "median": statistics.median(w)} for m, w in walls.items()}
+    if not a.kernel_only and not a.robust:
         b, lim, acc = ev.env._buf, ev.dof_limits, torch.zeros_like(ev.acc)
         tm = lambda: torch_metrics(b, lim, acc)
         timed(tm, 5)
@@ -95,6 +112,7 @@ def main():
         timed(g.replay, 5)
         d_g, w_g = timed(g.replay, 50)
         out["torch_expressions_per_step"] = {"eager_device_us": d_e, "eager_host_us": w_e, "replayed_device_us": d_g, "replayed_host_us": w_g}
+    if not a.kernel_only:
         os.makedirs(os.path.dirname(a.out), exist_ok=True)
         with open(a.out, "w") as f:
             json.dump(out, f, indent=1)
