@@ -33,6 +33,13 @@ GO2NN_ROBUST_ACC_NUM = GO2NN_ROBUST_NUM - GO2NN_ROBUST_ACC_FIRST
 ROBUST_FIELDS = ("root_states", "commands", "base_lin_vel", "projected_gravity", "reset_buf", "time_out_buf", "motor_strengths", "p_gains_multiplier", "d_gains_multiplier",
                  "added_base_mass", "friction_coeffs")
 ROBUST_MASK = {"strength": 1, "kp_mul": 2, "kd_mul": 4, "added_mass": 8, "friction": 16}
+# the evaluator's terrain ladder: the rows of the table [GO2NN_LADDER_NUM, N], the columns of go2nn_ladder_reduce's output and the values of the STATE row, each in the
+# order of its enum GO2NN_LADDER_* of include/go2nn.h, and the buffers of Go2nnLadderIn in the struct's order
+LADDER_ROWS = ("step", "state", "x0", "y0", "max_d2", "clear_step")
+LADDER_OUT = ("n", "cleared", "fell", "timed_out", "clear_steps", "progress")
+LADDER_STATES = ("running", "cleared", "fell", "timed_out")
+GO2NN_LADDER_NUM, GO2NN_LADDER_OUT_NUM = len(LADDER_ROWS), len(LADDER_OUT)
+LADDER_FIELDS = ("root_states", "reset_buf", "time_out_buf")
 _cached = None
 
 
@@ -107,6 +114,10 @@ class Go2nnRobustIn(C.Structure):          # (within ABI 7)
     _fields_ = [(k, Go2nnEvalField) for k in ROBUST_FIELDS] + [("num_specs", C.c_int32), ("pad_", C.c_int32)]
 
 
+class Go2nnLadderIn(C.Structure):          # (within ABI 7)
+    _fields_ = [(k, Go2nnEvalField) for k in LADDER_FIELDS] + [("dist2_thr", C.c_float), ("pad_", C.c_int32)]
+
+
 def trace_env_ids(env_ids, num_envs):
     """the tracked robots of go2nn_trace_record as the kernel needs them -> int32 numpy [K], strictly increasing, each in [0, num_envs).  The kernel cannot report a bad
     index (it would read outside the buffers), so anything else raises here."""
@@ -176,6 +187,9 @@ def bind(path):
     lib.go2nn_robust_apply.argtypes = [C.POINTER(Go2nnRobustIn), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
     lib.go2nn_robust_accumulate.argtypes = [C.POINTER(Go2nnRobustIn), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
     lib.go2nn_robust_reduce.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.go2nn_ladder_begin.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
+    lib.go2nn_ladder_accumulate.argtypes = [C.POINTER(Go2nnLadderIn), C.c_void_p, C.c_int32, C.c_void_p]
+    lib.go2nn_ladder_reduce.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p]
     if lib.go2nn_abi_version() != GO2NN_ABI_VERSION:
         raise RuntimeError("%s: ABI version %d, expected %d" % (path, lib.go2nn_abi_version(), GO2NN_ABI_VERSION))
     return lib

@@ -283,6 +283,11 @@ class LeggedRobotCfgPPO(BaseConfig):
         push_window_s = 2.0     # ... and the time after a push over which fall, recovery and peaks are scored (<= the period)
         recover_thr = 0.3       # [m/s] recovered = the velocity error stays below this ...
         recover_hold_s = 0.2    # ... for this long
+        ladder = False          # True (--ladder): the robots stand on every row of `ladder_levels` instead of `terrain_level`, and each (terrain x level) cell reports the share that cleared it (terrain tasks only)
+        ladder_levels = None    # None: every row 0 .. num_rows-1
+        ladder_scenarios = [["forward_1.0", 1.0, 0.0, 0.0]]          # the ladder's own scenario list (name, vx, vy, yaw rate); the per-terrain summary is over the first
+        ladder_distance = None  # [m] cleared = further than this from where the robot stood at the first counted step.  None: terrain.terrain_length / 2, the simulator's own promotion rule
+        ladder_pass_share = 0.5 # level_cleared counts a level as passed when this share of its robots cleared it: a convention (the majority of a cell's robots), not a measurement
 
 
 class LeggedRobotCfgCTS(BaseConfig):
@@ -353,6 +358,11 @@ class LeggedRobotCfgCTS(BaseConfig):
         push_window_s = 2.0     # ... and the time after a push over which fall, recovery and peaks are scored (<= the period)
         recover_thr = 0.3       # [m/s] recovered = the velocity error stays below this ...
         recover_hold_s = 0.2    # ... for this long
+        ladder = False          # True (--ladder): the robots stand on every row of `ladder_levels` instead of `terrain_level`, and each (terrain x level) cell reports the share that cleared it (terrain tasks only)
+        ladder_levels = None    # None: every row 0 .. num_rows-1
+        ladder_scenarios = [["forward_1.0", 1.0, 0.0, 0.0]]          # the ladder's own scenario list (name, vx, vy, yaw rate); the per-terrain summary is over the first
+        ladder_distance = None  # [m] cleared = further than this from where the robot stood at the first counted step.  None: terrain.terrain_length / 2, the simulator's own promotion rule
+        ladder_pass_share = 0.5 # level_cleared counts a level as passed when this share of its robots cleared it: a convention (the majority of a cell's robots), not a measurement
 
 
 class LeggedRobotCfgMoECTS(LeggedRobotCfgCTS):

@@ -5,6 +5,9 @@ config's `evaluation` section sets robots, horizon and scenarios), prints the pe
 model_*.pt of the run and names the best one by --metric (lower is better for the error / effort metrics, higher for survival and speed_along_cmd).
 --robust also scores the default perturbations (pushes, payload, weak motors, soft gains, low friction: utils/evaluator.py DEFAULT_PERTURBATIONS); --metric then also
 takes push_falls, recovered, recovery_time_s, peak_lin_vel_err and peak_tilt.
+--ladder (terrain tasks) places the robots on every terrain level and adds the per-terrain table of the share that cleared each level; --metric then also takes
+mean_level_cleared and cleared (higher is better), so --all_checkpoints --ladder --metric mean_level_cleared names the checkpoint that gets furthest.  The whole curve goes to eval_results/ladder_<checkpoint number>.yaml
+in the run's directory.
 --record N also records N robots of every (terrain x scenario) group and writes eval_results/trace_<checkpoint number>.npz into the run's directory."""
 import json
 import os
@@ -13,11 +16,11 @@ from pathlib import Path
 
 from go2_rl_gym_amd.envs import *  # noqa: F401,F403
 from go2_rl_gym_amd.utils import get_args
-from go2_rl_gym_amd.utils.evaluator import PolicyEvaluator, format_table
+from go2_rl_gym_amd.utils.evaluator import PolicyEvaluator, format_table, results_dict
 from go2_rl_gym_amd.utils.helpers import _checkpoint_number, get_load_path
 from go2_rl_gym_amd.utils.task_registry import ROOT_DIR, task_registry
 
-HIGHER_IS_BETTER = ("survival", "speed_along_cmd", "recovered")
+HIGHER_IS_BETTER = ("survival", "speed_along_cmd", "recovered", "mean_level_cleared", "cleared")
 
 
 def _own_flags(argv):
@@ -37,13 +40,14 @@ def _own_flags(argv):
     return own, rest
 
 
-def evaluate(argv=None, log_root="default"):
+def evaluate(argv=None, log_root="default", env_kwargs=None, evaluator_kwargs=None):
+    """env_kwargs / evaluator_kwargs: extra arguments of the env / of PolicyEvaluator (tests hand in host libraries, as through runner.evaluator_kwargs)"""
     own, rest = _own_flags(list(sys.argv[1:] if argv is None else argv))
     args = get_args(rest)
     env_cfg, train_cfg = task_registry.get_cfgs(name=args.task)
     env_cfg.env.num_envs = min(env_cfg.env.num_envs, 64)          # the runner's own env only carries the model's shapes here; the evaluator brings its own simulator
     env_cfg.env.test = True
-    env, _ = task_registry.make_env(name=args.task, args=args, env_cfg=env_cfg)
+    env, _ = task_registry.make_env(name=args.task, args=args, env_cfg=env_cfg, **(env_kwargs or {}))
     train_cfg.runner.resume = True
     runner, train_cfg = task_registry.make_alg_runner(env=env, name=args.task, args=args, train_cfg=train_cfg, log_root=log_root)
     root = os.path.join(ROOT_DIR, "logs", train_cfg.runner.experiment_name) if log_root == "default" else log_root
@@ -52,7 +56,10 @@ def evaluate(argv=None, log_root="default"):
     ev_cfg = dict(runner.eval_cfg)
     if own["eval_envs"] is not None:
         ev_cfg["num_envs"] = own["eval_envs"]
-    ev = PolicyEvaluator(env.cfg, ev_cfg, task_class=type(env), sim_params=env.sim_params, device=env.sim_device, **runner.evaluator_kwargs)
+    kw = dict(runner.evaluator_kwargs, **(evaluator_kwargs or {}))
+    if env.lib.go2sim_is_device_library() != 1:
+        kw.setdefault("lib", env.lib)
+    ev = PolicyEvaluator(env.cfg, ev_cfg, task_class=type(env), sim_params=env.sim_params, device=env.sim_device, **kw)
     rows = []
     for p in paths:
         runner.load(str(p), load_optimizer=False)
@@ -61,6 +68,14 @@ def evaluate(argv=None, log_root="default"):
         rows.append({"checkpoint": p.name, "overall": res["overall"], "groups": res["groups"]})
         if res.get("perturbations") is not None:
             rows[-1]["perturbations"] = res["perturbations"]
+        if res.get("ladder_summary") is not None:
+            rows[-1]["ladder_summary"] = res["ladder_summary"]
+            import yaml
+            path = os.path.join(str(p.parent), "eval_results", "ladder_%s.yaml" % _checkpoint_number(p))
+            os.makedirs(os.path.dirname(path), exist_ok=True)
+            with open(path, "w") as f:
+                yaml.safe_dump(results_dict(res, _checkpoint_number(p)), f)
+            print("ladder: %s" % path)
         if res.get("trace") is not None:
             from go2_rl_gym_amd.utils.recorder import write_trace
             print("trace: %s" % write_trace(os.path.join(str(p.parent), "eval_results", "trace_%s.npz" % _checkpoint_number(p)), res["trace"]))

@@ -28,6 +28,16 @@ turn.  Every perturbation carries the push schedule (`dv` defaults to 0: a sham 
 `recover_hold_s`), `recovery_time_s` (push -> end of that hold, mean over the recovered pushes), `peak_lin_vel_err` / `peak_tilt` (largest value inside the window, mean
 over pushes).  With `perturbations = None` nothing of this is allocated or launched.
 
+How far up the terrain: with `evaluation.ladder` (--ladder; heightfield / trimesh tasks) the robots do not stand on ONE row of the terrain grid but on every row of
+`ladder_levels`, under the commands `ladder_scenarios`: within a terrain kind they take the (level, scenario) cells in turn, cell index = (terrain * L + level) * S +
+scenario — what every reduce kernel groups by —, and every fresh simulator gets `terrain_levels` / `env_origins` written per env.  A step is then
+    { policy, go2sim_step, write the commands, go2nn_eval_accumulate, go2nn_ladder_accumulate }
+— one more launch (csrc/go2nn_ladder.h; the rule is in include/go2nn.h), inside the captured chunk — and one more reduce at the end.  A robot has CLEARED its level when it
+has been further than `ladder_distance` (default: half a tile, the simulator's own promotion rule) from where it stood at the first counted step; the record is latched per
+robot on the device, so it survives the simulator's reset of a fallen robot.  Per cell: `cleared`, `fell`, `timed_out` (shares: what happened FIRST), `time_to_clear_s`,
+`progress` (largest distance reached / `ladder_distance`, capped at 1); per terrain kind `level_cleared` (the highest level up to which every level has cleared >=
+`ladder_pass_share`) and `mean_level_cleared` (the sum of `cleared` over the levels).  With `ladder = False` nothing of this is allocated or launched.
+
 Isolated: nothing of the training env, the model, the optimizer or torch's generators is written; policy state the evaluation needs (the CTS observation history, the
 recurrent memory's hidden state) lives in buffers of the evaluator."""
 import copy
@@ -40,7 +50,8 @@ import torch
 
 from .. import _abi
 from .._nn import (EVAL_FIELDS, EVAL_METRICS, GO2NN_EVAL_NUM, GO2NN_RNN_GRU, GO2NN_RNN_LSTM, GO2NN_ROBUST_ACC_NUM, GO2NN_ROBUST_MAX_SPECS, GO2NN_ROBUST_NUM, ROBUST_FIELDS, ROBUST_MASK,
-                   Go2nnEvalIn, Go2nnFwdJob, Go2nnMlpIO, Go2nnRnnCellJob, Go2nnRobustIn, Go2nnRobustSpec, PackedMlp)
+                   GO2NN_LADDER_NUM, GO2NN_LADDER_OUT_NUM, LADDER_FIELDS, LADDER_OUT, Go2nnEvalIn, Go2nnFwdJob, Go2nnLadderIn, Go2nnMlpIO, Go2nnRnnCellJob, Go2nnRobustIn,
+                   Go2nnRobustSpec, PackedMlp)
 from .helpers import class_to_dict
 
 DEFAULT_SCENARIOS = [["forward_1.0", 1.0, 0.0, 0.0], ["forward_2.0", 2.0, 0.0, 0.0], ["backward_1.0", -1.0, 0.0, 0.0], ["lateral_0.5", 0.0, 0.5, 0.0],
@@ -51,6 +62,9 @@ RESULT_KEYS = MEAN_METRICS + ("falls", "survival", "n_envs")
 DEFAULT_PERTURBATIONS = [["nominal", {}], ["push_front_1.0", {"dv": [1.0, 0.0, 0.0]}], ["push_side_1.0", {"dv": [0.0, 1.0, 0.0]}], ["payload_3kg", {"added_mass": 3.0}],
                          ["motor_0.8", {"strength": 0.8}], ["kp_0.8", {"kp_mul": 0.8}], ["friction_0.3", {"friction": 0.3}]]
 ROBUST_KEYS = ("pushes", "push_falls", "recovered", "recovery_time_s", "peak_lin_vel_err", "peak_tilt")
+DEFAULT_LADDER_SCENARIOS = [["forward_1.0", 1.0, 0.0, 0.0]]
+LADDER_KEYS = ("cleared", "fell", "timed_out", "time_to_clear_s", "progress")
+LADDER_SUMMARY_KEYS = ("level_cleared", "mean_level_cleared")
 MAX_CHUNK = 50
 # The accumulate kernel runs AFTER the env step, when the simulator has already rolled its action history (last_actions = this step's actions): the previous step's
 # actions — the kernel's `last_actions` input — are then in the simulator's last_last_actions buffer.
@@ -254,10 +268,14 @@ class PolicyEvaluator:
         self.step_callback, self.apply_callback = step_callback, apply_callback
         perts = _get(evaluation, "perturbations")
         self.perturbations = [[str(p[0]), dict(p[1] or {})] for p in perts] if perts else None
-        self.scenarios = [list(s) for s in (_get(evaluation, "scenarios") or DEFAULT_SCENARIOS)]
+        self.ladder = bool(_get(evaluation, "ladder", False))
+        if self.ladder:
+            self._init_ladder()
+        else:
+            self.scenarios = [list(s) for s in (_get(evaluation, "scenarios") or DEFAULT_SCENARIOS)]
         self.terrain_level = int(_get(evaluation, "terrain_level", 5))
         self.num_envs = self.cfg.env.num_envs
-        self.env = self._terrain = None
+        self.env = self._terrain = self.level_of_env = None
         self._make_env()
         self.device = self.env.device
         self.on_device = self.env.lib.go2sim_is_device_library() == 1
@@ -273,11 +291,15 @@ class PolicyEvaluator:
         g = math.gcd(self.warmup_steps, self.steps)
         self.chunk = max(d for d in range(1, min(g, MAX_CHUNK) + 1) if g % d == 0)
         self._build_groups()
+        if self.ladder:
+            self._place_on_levels()
         N = self.num_envs
         self.acc = torch.zeros(GO2NN_EVAL_NUM, N, device=self.device)
         self.out = torch.zeros(self.num_cells, GO2NN_EVAL_NUM + 2, dtype=torch.float64, device=self.device)
         if self.perturbations is not None:
             self._build_robust()
+        if self.ladder:
+            self._build_ladder()
         self.dof_limits = self.env.dof_pos_limits.contiguous().clone()
         self._policy, self._policy_of = None, None
         self.recorder = None
@@ -311,17 +333,63 @@ class PolicyEvaluator:
         kw = {} if self._lib is None else {"lib": self._lib}
         self.env = cls(cfg=self.cfg, sim_params=sp, physics_engine=1, sim_device=self.device_arg, headless=True, **kw)
         env = self.env
-        if env.custom_origins:          # every env at the evaluation's terrain level, in the column the simulator gave it
+        if self.ladder:                 # every env on its cell's level (known once the groups are built: __init__ places the first simulator's robots itself)
+            if self.level_of_env is not None:
+                self._place_on_levels()
+        elif env.custom_origins:        # every env at the evaluation's terrain level, in the column the simulator gave it
             lv = min(max(self.terrain_level, 0), self.cfg.terrain.num_rows - 1)
             env.terrain_levels.fill_(lv)
             env.env_origins.copy_(env.terrain_origins[lv, env.terrain_types])
 
+    def _init_ladder(self):
+        """the ladder's own settings, checked before anything is built: scenarios, levels, clearing distance, pass share"""
+        ev, t = self.ev, self.cfg.terrain
+        if t.mesh_type not in ("heightfield", "trimesh"):
+            raise ValueError("evaluation.ladder needs a task with terrain levels (terrain.mesh_type heightfield / trimesh), got mesh_type = %r" % (t.mesh_type,))
+        if self.perturbations is not None:
+            raise ValueError("evaluation.ladder and evaluation.perturbations cannot be combined: one evaluation splits the robots along ONE extra axis")
+        self.scenarios = [list(s) for s in (_get(ev, "ladder_scenarios") or DEFAULT_LADDER_SCENARIOS)]
+        levels = _get(ev, "ladder_levels")
+        self.levels = [int(l) for l in (range(int(t.num_rows)) if levels is None else levels)]
+        if not self.levels or sorted(set(self.levels)) != self.levels or self.levels[0] < 0 or self.levels[-1] >= int(t.num_rows):
+            raise ValueError("evaluation.ladder_levels: increasing rows of the terrain grid inside 0 .. %d, got %r" % (int(t.num_rows) - 1, levels))
+        dist = _get(ev, "ladder_distance")
+        self.ladder_distance = float(t.terrain_length) * 0.5 if dist is None else float(dist)
+        self.ladder_pass_share = float(_get(ev, "ladder_pass_share", 0.5))
+        if not self.ladder_distance > 0.0:
+            raise ValueError("evaluation.ladder_distance: a distance > 0 [m], got %r" % (dist,))
+        seconds = float(_get(ev, "seconds", 10.0))
+        for s in self.scenarios:
+            reach = math.hypot(float(s[1]), float(s[2])) * seconds
+            if reach <= self.ladder_distance:
+                print("[go2_rl_gym_amd] evaluation: ladder scenario %r covers at most %.2f m in %.1f s at its command and cannot clear the %.2f m of evaluation.ladder_distance; "
+                      "raise evaluation.seconds" % (s[0], reach, seconds, self.ladder_distance))
+
+    def _place_on_levels(self):
+        """the ladder's env placement on the current simulator: every env on its cell's row of the terrain grid, in the column the simulator gave it"""
+        env = self.env
+        lv = torch.from_numpy(self.level_of_env).to(env.terrain_levels.device)
+        env.terrain_levels.copy_(lv.to(env.terrain_levels.dtype))
+        env.env_origins.copy_(env.terrain_origins[lv.long(), env.terrain_types.long()])
+
+    def _build_ladder(self):
+        """the ladder's device side: the per-env table, the reduce output, the squared clearing distance as the kernel compares it"""
+        self.dist2_thr = float(np.float32(self.ladder_distance) * np.float32(self.ladder_distance))
+        self.ltable = torch.zeros(GO2NN_LADDER_NUM, self.num_envs, device=self.device)
+        self.lout = torch.zeros(self.num_cells, GO2NN_LADDER_OUT_NUM, dtype=torch.float64, device=self.device)
+        sizes = np.bincount(self.cell_host, minlength=self.num_cells)
+        if sizes.min() < 4:
+            print("[go2_rl_gym_amd] evaluation: %d of %d (terrain x level x scenario) cells have fewer than 4 robots (smallest: %d); raise evaluation.num_envs"
+                  % (int((sizes < 4).sum()), self.num_cells, int(sizes.min())))
+
     def _build_groups(self):
         """env -> (terrain kind x scenario) group, built once on the host: the kinds are those of the columns the envs stand in (one kind, 'plane', without a terrain mesh);
         within a kind the envs take the scenarios in turn, so the groups of a kind differ by at most one env.  With P perturbations they take the (scenario, perturbation)
-        CELLS in turn; cell index = (terrain * S + scenario) * P + perturbation — the kernels' group —, and a group is the union of its P cells (P = 1 without)"""
+        CELLS in turn; cell index = (terrain * S + scenario) * P + perturbation — the kernels' group —, and a group is the union of its P cells (P = 1 without).
+        With the ladder's L levels they take the (level, scenario) cells in turn; cell index = (terrain * L + level) * S + scenario, a group is the union of its L cells"""
         from .terrain import KIND_NAMES
         N, S, P = self.num_envs, len(self.scenarios), len(self.perturbations or [None])
+        L = len(self.levels) if self.ladder else 1
         if self.env.custom_origins:
             kind_of_env = self.env.terrain_cols2id.cpu().numpy()[self.env.terrain_types.cpu().numpy()]
             kinds = [int(k) for k in sorted(set(kind_of_env.tolist()))]
@@ -329,15 +397,22 @@ class PolicyEvaluator:
         else:
             kind_of_env, kinds, self.terrain_names = np.zeros(N, np.int64), [0], ["plane"]
         group = np.zeros(N, np.int32)
-        scen, pert = np.zeros(N, np.int64), np.zeros(N, np.int32)
+        scen, pert, level = np.zeros(N, np.int64), np.zeros(N, np.int32), np.zeros(N, np.int64)
         for ki, k in enumerate(kinds):
             ids = np.nonzero(kind_of_env == k)[0]
-            turn = np.arange(len(ids)) % (S * P)
-            scen[ids], pert[ids] = turn // P, turn % P
+            if self.ladder:
+                turn = np.arange(len(ids)) % (L * S)
+                level[ids], scen[ids] = turn // S, turn % S
+            else:
+                turn = np.arange(len(ids)) % (S * P)
+                scen[ids], pert[ids] = turn // P, turn % P
             group[ids] = ki * S + scen[ids]
         self.groups = [(t, s[0]) for t in self.terrain_names for s in self.scenarios]
         self.group_host, self.pert_host = group, pert
         self.cell_host, self.num_cells = group * P + pert, len(self.groups) * P
+        if self.ladder:          # level_index_host: index into self.levels;  level_of_env: the row of the terrain grid itself
+            self.level_index_host, self.level_of_env = level, np.asarray(self.levels, np.int64)[level]
+            self.cell_host, self.num_cells = (((group // S) * L + level) * S + scen).astype(np.int32), len(self.groups) * L
         self.group = torch.from_numpy(self.cell_host).to(self.device)          # what the reduce kernels group by
         cmd = np.zeros((N, 4), np.float32)
         cmd[:, :3] = np.asarray([s[1:4] for s in self.scenarios], np.float32)[scen]
@@ -398,6 +473,15 @@ class PolicyEvaluator:
     def _robust(self, fn, what, rin):
         self._check(fn(C.byref(rin), C.c_void_p(self.specs.data_ptr()), C.c_void_p(self.pert.data_ptr()), C.c_void_p(self.rtable.data_ptr()), self.num_envs, self._stream()), what)
 
+    def _ladder_in(self):
+        """the ladder kernel's view of the simulator's buffers (as _eval_in)"""
+        b, a = self.env._buf, Go2nnLadderIn()
+        for name in LADDER_FIELDS:
+            t, f = b[name], getattr(a, name)
+            f.p, f.env_stride, f.comp_stride = t.data_ptr(), t.stride(0), (t.stride(1) if t.dim() > 1 else 0)
+        a.dist2_thr = self.dist2_thr
+        return a
+
     def _eval_in(self):
         """the accumulate kernel's view of the simulator's buffers: (pointer, env stride, component stride) in elements from the torch views' own strides"""
         env, a = self.env, Go2nnEvalIn()
@@ -411,8 +495,9 @@ class PolicyEvaluator:
         return a
 
     # ------------------------------------------------------------------ one env step of the evaluation (pure enqueue)
-    def _step(self, pol, ein, rin=None, k=None):
-        """rin: the perturbation kernels' input (None without perturbations);  k: the step's index in an eager run (None inside a capture: no callback there)"""
+    def _step(self, pol, ein, rin=None, k=None, lin=None):
+        """rin: the perturbation kernels' input (None without perturbations);  k: the step's index in an eager run (None inside a capture: no callback there);
+        lin: the ladder kernel's input (None without the ladder)"""
         env = self.env
         actions = pol.act(env.obs_buf)
         if rin is not None:
@@ -424,6 +509,8 @@ class PolicyEvaluator:
         self._check(self.nn.go2nn_eval_accumulate(C.byref(ein), C.c_void_p(self.acc.data_ptr()), self.num_envs, self._stream()), "go2nn_eval_accumulate")
         if rin is not None:
             self._robust(self.nn.go2nn_robust_accumulate, "go2nn_robust_accumulate", rin)
+        if lin is not None:
+            self._check(self.nn.go2nn_ladder_accumulate(C.byref(lin), C.c_void_p(self.ltable.data_ptr()), self.num_envs, self._stream()), "go2nn_ladder_accumulate")
         if self.recorder is not None:
             self.recorder.record()
         pol.after_step(env.obs_buf, env._buf["reset_buf"])
@@ -433,15 +520,15 @@ class PolicyEvaluator:
         if self.recorder is not None:
             self.recorder.clear()
 
-    def _run_eager(self, pol, ein, rin):
+    def _run_eager(self, pol, ein, rin, lin=None):
         for k in range(self.warmup_steps + self.steps):
             if k == self.warmup_steps:
                 self._clear()
-            self._step(pol, ein, rin, k)
+            self._step(pol, ein, rin, k, lin)
             if self.step_callback is not None:
                 self.step_callback(self, k, k >= self.warmup_steps)
 
-    def _run_graph(self, pol, ein, rin):
+    def _run_graph(self, pol, ein, rin, lin=None):
         """capture `chunk` steps on this evaluation's simulator, replay them for the whole horizon -> False if the capture failed (nothing has run then)"""
         from ..rsl_rl.algorithms._graph import no_gc, strict_graphs
         torch.cuda.synchronize(self.device)
@@ -449,7 +536,7 @@ class PolicyEvaluator:
         try:
             with no_gc(), torch.cuda.graph(g):
                 for _ in range(self.chunk):
-                    self._step(pol, ein, rin)
+                    self._step(pol, ein, rin, lin=lin)
         except Exception as e:      # noqa: BLE001
             if strict_graphs():
                 raise RuntimeError("HIP-graph capture of the evaluation failed (%s: %s)" % (type(e).__name__, e)) from e
@@ -467,6 +554,8 @@ class PolicyEvaluator:
     # ------------------------------------------------------------------ the public call
     def evaluate(self, actor_critic, use_graph=None):
         """-> {"overall": {...}, "groups": {terrain: {scenario: {...}}}, "terrain_names", "scenarios", "steps", "dt", "mode"}; every leaf dict has RESULT_KEYS.
+        With `evaluation.ladder` also "ladder": {terrain: {level: {scenario: {RESULT_KEYS + LADDER_KEYS}}}}, "ladder_summary": {terrain: {LADDER_SUMMARY_KEYS}}, "levels",
+        "ladder_table" (go2nn_ladder_reduce's raw output per cell) and "ladder_distance"; "overall" gains `cleared` and `mean_level_cleared`.
         With `evaluation.record` also "trace": TrajectoryRecorder.fetch() of the counted steps plus "group_of_robot" (index into terrain_names x scenarios, terrain-major,
         per tracked robot), "terrain_names" and "scenarios".
         use_graph: None = eager, or with `evaluation.replay` eager the first time and a captured chunk afterwards (on the GPU); True / False force it."""
@@ -489,11 +578,15 @@ class PolicyEvaluator:
             if self.perturbations is not None:          # the table's step counter starts at -warmup_steps: nothing is pushed or counted before step 0, no clear at the boundary
                 rin = self._robust_in()
                 self._check(self.nn.go2nn_robust_begin(C.c_void_p(self.rtable.data_ptr()), self.num_envs, -self.warmup_steps, self._stream()), "go2nn_robust_begin")
+            lin = None
+            if self.ladder:          # as above: the table's step counter starts at -warmup_steps, the origin of the distance is taken at step 0 by the kernel itself
+                lin = self._ladder_in()
+                self._check(self.nn.go2nn_ladder_begin(C.c_void_p(self.ltable.data_ptr()), self.num_envs, -self.warmup_steps, self._stream()), "go2nn_ladder_begin")
             replay = bool(_get(self.ev, "replay", False))
             graph = (replay and self.on_device and self.evaluations > 0 and self.step_callback is None) if use_graph is None else bool(use_graph and self.on_device)
-            done = graph and self._run_graph(pol, ein, rin)
+            done = graph and self._run_graph(pol, ein, rin, lin)
             if not done:
-                self._run_eager(pol, ein, rin)
+                self._run_eager(pol, ein, rin, lin)
             self.last_mode = "graph" if done else "eager"
             self._check(self.nn.go2nn_eval_reduce(C.c_void_p(self.acc.data_ptr()), C.c_void_p(self.group.data_ptr()), self.num_envs, self.num_cells,
                                                   C.c_void_p(self.out.data_ptr()), self._stream()), "go2nn_eval_reduce")
@@ -502,13 +595,20 @@ class PolicyEvaluator:
                 self._check(self.nn.go2nn_robust_reduce(C.c_void_p(self.rtable.data_ptr()), C.c_void_p(self.group.data_ptr()), self.num_envs, self.num_cells,
                                                         C.c_void_p(self.rout.data_ptr()), self._stream()), "go2nn_robust_reduce")
                 rtable = self.rout.cpu().numpy().copy()
+            ltable = None
+            if lin is not None:
+                self._check(self.nn.go2nn_ladder_reduce(C.c_void_p(self.ltable.data_ptr()), C.c_void_p(self.group.data_ptr()), self.num_envs, self.num_cells, self.dist2_thr,
+                                                        C.c_void_p(self.lout.data_ptr()), self._stream()), "go2nn_ladder_reduce")
+                ltable = self.lout.cpu().numpy().copy()
             table = self.out.cpu().numpy().copy()          # the device -> host copy (and synchronisation) of an evaluation
             trace = self.recorder.fetch() if self.recorder is not None else None
             self._graph = None
             self.evaluations += 1
-        res = self._results(table, rtable)
+        res = self._results(table, rtable, ltable)
         if trace is not None:
             trace.update(group_of_robot=self.group_host[trace["env_ids"]].copy(), terrain_names=list(self.terrain_names), scenarios=[s[0] for s in self.scenarios])
+            if self.ladder:
+                trace.update(levels=list(self.levels), level_of_robot=self.level_of_env[trace["env_ids"]].copy())
             if self.perturbations is not None:          # push_steps: the counted steps (= frame indices) whose go2nn_robust_apply pushed; the frame holds the state AFTER that step
                 trace.update(perturbations=[p[0] for p in self.perturbations], pert_of_robot=self.pert_host[trace["env_ids"]].copy(), push_steps=self.push_steps.copy())
             res["trace"] = trace
@@ -531,10 +631,43 @@ class PolicyEvaluator:
         return {"pushes": int(pushes), "push_falls": per_push(r[1]), "recovered": per_push(r[2]), "recovery_time_s": float(r[3]) / rec * self.dt if rec > 0 else float("nan"),
                 "peak_lin_vel_err": per_push(r[4]), "peak_tilt": per_push(r[5])}
 
-    def _results(self, cells, rcells=None):
-        """cells: the eval reduce table per (terrain, scenario, perturbation) cell; rcells: the robust one (None without perturbations: a cell is a group then)"""
+    def _ladder_row(self, r):
+        """one row of go2nn_ladder_reduce (LADDER_OUT) -> the cell's shares; an empty cell reports NaN, and so does time_to_clear_s without a cleared robot"""
+        n, cleared = float(r[LADDER_OUT.index("n")]), float(r[LADDER_OUT.index("cleared")])
+        share = lambda k: float(r[LADDER_OUT.index(k)]) / n if n > 0 else float("nan")
+        return {"cleared": share("cleared"), "fell": share("fell"), "timed_out": share("timed_out"),
+                "time_to_clear_s": float(r[LADDER_OUT.index("clear_steps")]) / cleared * self.dt if cleared > 0 else float("nan"), "progress": share("progress")}
+
+    def _ladder_results(self, res, cells, lcells):
+        """cells / lcells: the eval / ladder reduce tables per (terrain, level, scenario) cell -> the ladder's entries of the result"""
+        T, L, S = len(self.terrain_names), len(self.levels), len(self.scenarios)
+        c4, l4 = cells.reshape(T, L, S, -1), lcells.reshape(T, L, S, -1)
+        res["ladder"] = {t: {lv: {s[0]: dict(self._row(c4[ti, li, si]), **self._ladder_row(l4[ti, li, si])) for si, s in enumerate(self.scenarios)}
+                             for li, lv in enumerate(self.levels)} for ti, t in enumerate(self.terrain_names)}
+        first = self.scenarios[0][0]
+        summary = {}
+        for t in self.terrain_names:          # over the FIRST ladder scenario; an empty cell (cleared = NaN) has cleared nothing
+            curve = [res["ladder"][t][lv][first]["cleared"] for lv in self.levels]
+            curve = [0.0 if math.isnan(c) else c for c in curve]
+            top = -1
+            for lv, c in zip(self.levels, curve):
+                if c < self.ladder_pass_share:
+                    break
+                top = lv
+            summary[t] = {"level_cleared": int(top), "mean_level_cleared": float(sum(curve))}
+        res["ladder_summary"] = summary
+        whole = lcells.sum(0)
+        res["overall"].update(cleared=self._ladder_row(whole)["cleared"], mean_level_cleared=float(np.mean([v["mean_level_cleared"] for v in summary.values()])))
+        res.update(levels=list(self.levels), ladder_table=lcells, ladder_cell_table=cells, ladder_distance=self.ladder_distance, ladder_pass_share=self.ladder_pass_share)
+
+    def _results(self, cells, rcells=None, lcells=None):
+        """cells: the eval reduce table per (terrain, scenario, perturbation) cell; rcells: the robust one (None without perturbations: a cell is a group then);
+        lcells: the ladder's (None without the ladder), cells being per (terrain, level, scenario) then"""
         S, P = len(self.scenarios), len(self.perturbations or [None])
-        table = cells.reshape(len(self.groups), P, -1).sum(1)          # P = 1: the cells' rows themselves
+        if lcells is not None:
+            table = cells.reshape(len(self.terrain_names), len(self.levels), S, -1).sum(1).reshape(len(self.groups), -1)
+        else:
+            table = cells.reshape(len(self.groups), P, -1).sum(1)          # P = 1: the cells' rows themselves
         groups = {t: {s[0]: self._row(table[ti * S + si]) for si, s in enumerate(self.scenarios)} for ti, t in enumerate(self.terrain_names)}
         res = {"overall": self._row(table.sum(0)), "groups": groups, "terrain_names": list(self.terrain_names), "scenarios": [s[0] for s in self.scenarios],
                "steps": self.steps, "dt": self.dt, "mode": self.last_mode, "table": table}
@@ -548,6 +681,8 @@ class PolicyEvaluator:
             res["overall"].update(self._robust_row(rcells.sum(0)))
             res.update(perturbation_names=names, cell_table=cells, robust_table=rcells, push_steps=self.push_steps.tolist(),
                        push={"first": self.push_first, "period": self.push_period, "window": self.push_window, "hold": self.push_hold, "count": self.push_count})
+        if lcells is not None:
+            self._ladder_results(res, cells, lcells)
         return res
 
     def close(self):
@@ -558,13 +693,18 @@ class PolicyEvaluator:
 
 # ---------------------------------------------------------------------------------------------------------------------------------------------------------------
 def scalars(res):
-    """[(tag, value)]: 'Eval/<metric>' for the overall figures, 'Eval/<terrain>/<scenario>/<metric>' per group and, with perturbations, 'Eval/robust/<name>/<metric>'"""
+    """[(tag, value)]: 'Eval/<metric>' for the overall figures, 'Eval/<terrain>/<scenario>/<metric>' per group, with perturbations 'Eval/robust/<name>/<metric>' and, with
+    the ladder, 'Eval/ladder/<terrain>/{level_cleared,mean_level_cleared}' and 'Eval/ladder/mean_level_cleared'"""
     out = [("Eval/" + k, res["overall"][k]) for k in RESULT_KEYS]
     for t, per in res["groups"].items():
         for s, d in per.items():
             out += [("Eval/%s/%s/%s" % (t, s, k), d[k]) for k in RESULT_KEYS]
     for n, d in (res.get("perturbations") or {}).items():
         out += [("Eval/robust/%s/%s" % (n, k), d[k]) for k in RESULT_KEYS + ROBUST_KEYS]
+    if res.get("ladder_summary") is not None:
+        for t, d in res["ladder_summary"].items():
+            out += [("Eval/ladder/%s/%s" % (t, k), d[k]) for k in LADDER_SUMMARY_KEYS]
+        out.append(("Eval/ladder/mean_level_cleared", res["overall"]["mean_level_cleared"]))
     return out
 
 
@@ -574,6 +714,10 @@ def results_dict(res, it=None):
     if res.get("perturbations") is not None:
         d["perturbations"] = {n: dict(v) for n, v in res["perturbations"].items()}
         d["push"] = dict(res["push"])
+    if res.get("ladder") is not None:          # the full curve, and what it comes to per terrain kind
+        d["ladder"] = {t: {int(lv): {s: dict(v) for s, v in per.items()} for lv, per in levels.items()} for t, levels in res["ladder"].items()}
+        d["ladder_summary"] = {t: dict(v) for t, v in res["ladder_summary"].items()}
+        d["ladder_levels"], d["ladder_distance"], d["ladder_pass_share"] = [int(l) for l in res["levels"]], float(res["ladder_distance"]), float(res["ladder_pass_share"])
     return d
 
 
@@ -589,6 +733,14 @@ def format_table(res):
         lines += ["", "%-20s " % "perturbation" + " ".join("%16s" % c for c in cols)]
         for n, d in list(res["perturbations"].items()) + [("all", res["overall"])]:
             lines.append("%-20s " % n + " ".join("%16d" % d[c] if c in whole else "%16.4f" % d[c] for c in cols))
+    if res.get("ladder") is not None:          # the third block: one line per terrain kind, the share of robots that cleared each level under the first ladder scenario
+        first = res["scenarios"][0]
+        lines += ["", "%-16s %-14s " % ("terrain", "cleared @ level") + " ".join("%6d" % lv for lv in res["levels"]) + " %14s %19s" % LADDER_SUMMARY_KEYS]
+        for t, levels in res["ladder"].items():
+            sm = res["ladder_summary"][t]
+            lines.append("%-16s %-14s " % (t, first) + " ".join("%6.2f" % levels[lv][first]["cleared"] for lv in res["levels"])
+                         + " %14d %19.3f" % (sm["level_cleared"], sm["mean_level_cleared"]))
+        lines.append("%-16s %-14s " % ("all", first) + " ".join("%6s" % "" for _ in res["levels"]) + " %14s %19.3f" % ("", res["overall"]["mean_level_cleared"]))
     return "\n".join(lines)
 
 

@@ -423,6 +423,41 @@ int go2nn_robust_accumulate(const Go2nnRobustIn* in, const Go2nnRobustSpec* spec
  * function) of go2nn_eval_reduce: fixed order, bit-equal outputs for equal inputs, group ids outside [0, G) ignored, an empty group gives zeros.  1 <= G <= 65535. */
 int go2nn_robust_reduce(const float* table, const int32_t* group, int32_t N, int32_t G, double* out, void* stream);
 
+/* ---- the evaluator's terrain-difficulty ladder: how far does a robot get from where it stood (go2_rl_gym_amd/utils/evaluator.py, `evaluation.ladder`).
+ * ADDED WITHIN ABI 7: three new entry points, nothing existing changes, GO2NN_ABI_VERSION stays 7.
+ * A ladder evaluation step is { policy, go2sim_step, go2nn_eval_accumulate, go2nn_ladder_accumulate }: one more plain launch per step (capturable; one lane per env, no
+ * atomics), and one go2nn_ladder_reduce at the end.  The record of a robot survives the simulator's reset of a fallen robot: it is latched in the table.
+ * The table: fp32 [GO2NN_LADDER_NUM, N], row-major by row of the first enum below, column e = env e.
+ * go2nn_ladder_begin: table = 0, then STEP[e] = start for every e (the evaluator passes -warmup_steps).
+ * go2nn_ladder_accumulate (AFTER the step), per env, with s = STEP[e], in this order:
+ *   1. s < 0:   nothing but step 4 (a fall before the first counted step leaves no trace);
+ *   2. s == 0:  X0, Y0 = root_states[e, 0:2] (bit copies), MAX_D2 = 0, STATE = RUNNING;
+ *   3. STATE == RUNNING:  reset_buf and not time_out_buf:  STATE = FELL;     reset_buf and time_out_buf:  STATE = TIMED_OUT;
+ *                         otherwise d2 = (x - X0)^2 + (y - Y0)^2,  MAX_D2 = max(MAX_D2, d2),  and if d2 > dist2_thr:  STATE = CLEARED, CLEAR_STEP = s + 1;
+ *   4. STEP = s + 1.
+ * On a reset root_states already holds the post-reset pose, so the flags are looked at BEFORE the position (a step with a reset never contributes a distance).  A latched
+ * state (CLEARED, FELL, TIMED_OUT) is never left: a robot that clears and falls afterwards stays CLEARED, and only the first fall or time-out is seen.  Distances are compared
+ * squared; no square root is taken per step.  CLEAR_STEP is the number of counted steps the robot took to clear (1 = at the first counted step's end).
+ * go2nn_ladder_reduce: out [G, GO2NN_LADDER_OUT_NUM] (fp64), per group the columns of the second enum: its envs, those CLEARED / FELL / TIMED_OUT, the sum of CLEAR_STEP
+ * over the CLEARED ones, and the sum of progress = min(sqrt(MAX_D2 / dist2_thr), 1) (fp64) over all of them — the summation scheme (and the device function) of
+ * go2nn_eval_reduce: fixed order, bit-equal outputs for equal inputs, group ids outside [0, G) ignored, an empty group gives zeros.  It takes dist2_thr as an argument (the
+ * table does not hold it): pass the value go2nn_ladder_accumulate ran with. */
+enum { GO2NN_LADDER_STEP = 0, GO2NN_LADDER_STATE, GO2NN_LADDER_X0, GO2NN_LADDER_Y0, GO2NN_LADDER_MAX_D2, GO2NN_LADDER_CLEAR_STEP, GO2NN_LADDER_NUM };
+enum { GO2NN_LADDER_OUT_N = 0, GO2NN_LADDER_OUT_CLEARED, GO2NN_LADDER_OUT_FELL, GO2NN_LADDER_OUT_TIMED_OUT, GO2NN_LADDER_OUT_CLEAR_STEPS, GO2NN_LADDER_OUT_PROGRESS, GO2NN_LADDER_OUT_NUM };
+enum { GO2NN_LADDER_RUNNING = 0, GO2NN_LADDER_CLEARED = 1, GO2NN_LADDER_FELL = 2, GO2NN_LADDER_TIMED_OUT = 3 };          /* the values of the STATE row */
+/* The buffers as (pointer, env stride, component stride) in ELEMENTS like Go2nnEvalIn's: root_states [N,13] (only columns 0 and 1 are read), reset_buf / time_out_buf uint8
+ * (comp_stride unused, may be 0).  dist2_thr: the SQUARED clearing distance [m^2], > 0.  Nothing but the table is written. */
+typedef struct Go2nnLadderIn {
+  Go2nnEvalField root_states, reset_buf, time_out_buf;
+  float dist2_thr;
+  int32_t pad_;
+} Go2nnLadderIn;
+int go2nn_ladder_begin(float* table, int32_t N, int32_t start, void* stream);
+/* GO2NN_EINVAL for null pointers, N < 1, an env stride < 1, a component stride of root_states < 1, dist2_thr <= 0 (or NaN). */
+int go2nn_ladder_accumulate(const Go2nnLadderIn* in, float* table, int32_t N, void* stream);
+/* GO2NN_EINVAL for null pointers, N < 1, G outside 1 .. 65535, dist2_thr <= 0 (or NaN). */
+int go2nn_ladder_reduce(const float* table, const int32_t* group, int32_t N, int32_t G, float dist2_thr, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

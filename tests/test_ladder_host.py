@@ -1,0 +1,525 @@
+"""The evaluator's terrain-difficulty ladder on the CPU: the host build of the go2nn_ladder_* kernels (include/go2nn.h) against a float64 restatement written here over a
+scripted sequence in which the envs meet every branch, the reduce against math.fsum, the argument checks, the struct layout, and PolicyEvaluator with `ladder` on the
+oracle + the host build: placement on the levels, the whole ladder table recomputed from the recorded root states, reproducibility, the results' shape, and the CLI."""
+import contextlib
+import copy
+import ctypes as C
+import io
+import json
+import math
+import os
+import subprocess
+
+import numpy as np
+import pytest
+import torch
+import yaml
+
+from helpers import ROOT, load_nn_emu, load_oracle
+import test_eval_host as th
+from test_robust_host import HostMemory, store
+from go2_rl_gym_amd import _nn
+from go2_rl_gym_amd._nn import GO2NN_LADDER_NUM, GO2NN_LADDER_OUT_NUM, LADDER_FIELDS, LADDER_OUT, LADDER_ROWS, LADDER_STATES, Go2nnLadderIn
+from go2_rl_gym_amd.envs import task_registry
+from go2_rl_gym_amd.utils import get_args
+
+U = 2.0 ** -24
+R = {n: i for i, n in enumerate(LADDER_ROWS)}
+O = {n: i for i, n in enumerate(LADDER_OUT)}
+RUNNING, CLEARED, FELL, TIMED_OUT = range(4)
+EXACT_ROWS = ("step", "state", "clear_step", "x0", "y0")
+START, CALLS = -3, 30
+DIST2_THR = 0.25          # (0.5 m)^2, exact in fp32
+MARGIN = 1e-3             # the scripts keep every |d2 - dist2_thr| >= MARGIN * dist2_thr, asserted on the float64 reference: no decision can flip on rounding
+EINVAL = -22
+
+
+def radius(kind, s):
+    """the scripted distance [m] of a robot of pattern `kind` from where it stood at step 0, after counted step s >= 0 (while it is still running)"""
+    if kind in (1, 3):
+        return 0.06 * s                                   # 0.48 at s = 8 (d2 0.2304), 0.54 at s = 9 (0.2916): clears at s = 9, CLEAR_STEP = 10
+    if kind == 2:
+        return (0.0, 0.1, 0.2, 0.3, 0.2)[min(s, 4)]       # out to 0.3 and back: MAX_D2 is not the last d2; falls at s = 5
+    if kind == 4:
+        return 0.05 * s                                   # 0.3 at s = 6, where it times out
+    return 0.0
+
+
+def scripted_step(rng, N, s, base, phi):
+    """what the simulator shows after step s, by the env's pattern e % 6:  0 never moves;  1 clears at s = 9;  2 falls at s = 5 before clearing (and is shown far away from
+    then on: the post-reset pose);  3 clears at s = 9 and falls at s = 15 (stays cleared);  4 times out at s = 6 before clearing;  5 falls exactly at s = 0 (and walks off
+    afterwards).  While s < 0 every robot is somewhere else and patterns 0 and 1 fall at s = -2: no trace.  -> {field: array}"""
+    e = np.arange(N)
+    k = e % 6
+    root = rng.normal(0, 1, (N, 13))
+    if s < 0:
+        root[:, :2] = base + rng.uniform(-3, 3, (N, 2))
+        reset = (s == -2) & (k <= 1)
+        timeout = np.zeros(N, bool)
+    else:
+        r = np.asarray([radius(int(kk), s) for kk in k])
+        root[:, 0], root[:, 1] = base[:, 0] + r * np.cos(phi), base[:, 1] + r * np.sin(phi)
+        gone = ((k == 2) & (s >= 5)) | ((k == 3) & (s >= 15)) | ((k == 4) & (s >= 6)) | ((k == 5) & (s >= 1))
+        root[gone, :2] = base[gone] + 10.0 + 0.5 * s          # far beyond the clearing distance: a latched state must not look at it
+        reset = ((k == 2) & (s == 5)) | ((k == 3) & (s == 15)) | ((k == 4) & (s == 6)) | ((k == 5) & (s == 0)) | ((k == 2) & (s == 20))
+        timeout = (k == 4) & (s == 6)
+    return {"root_states": root.astype(np.float32), "reset_buf": reset.astype(np.uint8), "time_out_buf": timeout.astype(np.uint8)}
+
+
+class Reference:
+    """the rule of include/go2nn.h in float64, one env at a time; `closest` is the smallest |d2 - thr| / thr it ever compared"""
+
+    def __init__(self, N, start, dist2_thr):
+        self.N, self.thr = N, float(dist2_thr)
+        self.t = np.zeros((GO2NN_LADDER_NUM, N))
+        self.t[R["step"]] = start
+        self.closest = float("inf")
+
+    def accumulate(self, root, reset, timeout):
+        root = np.asarray(root, np.float64)
+        for e in range(self.N):
+            t = self.t[:, e]
+            s = t[R["step"]]
+            if s >= 0:
+                x, y = root[e, 0], root[e, 1]
+                if s == 0:
+                    t[R["x0"]], t[R["y0"]], t[R["max_d2"]], t[R["state"]] = x, y, 0.0, RUNNING
+                if t[R["state"]] == RUNNING:
+                    if reset[e]:
+                        t[R["state"]] = TIMED_OUT if timeout[e] else FELL
+                    else:
+                        d2 = (x - t[R["x0"]]) ** 2 + (y - t[R["y0"]]) ** 2
+                        self.closest = min(self.closest, abs(d2 - self.thr) / self.thr)
+                        t[R["max_d2"]] = max(t[R["max_d2"]], d2)
+                        if d2 > self.thr:
+                            t[R["state"]], t[R["clear_step"]] = CLEARED, s + 1
+            t[R["step"]] = s + 1
+
+    def reduce(self, group, G):
+        """-> (out [G, OUT_NUM] with math.fsum, sum|terms| [G, OUT_NUM])"""
+        return reduce_reference(self.t, group, G, self.thr)
+
+
+def reduce_reference(table, group, G, thr):
+    out, mag = np.zeros((G, GO2NN_LADDER_OUT_NUM)), np.zeros((G, GO2NN_LADDER_OUT_NUM))
+    for g in range(G):
+        ids = np.nonzero(group == g)[0]
+        st = table[R["state"], ids]
+        terms = {"n": np.ones(len(ids)), "cleared": st == CLEARED, "fell": st == FELL, "timed_out": st == TIMED_OUT,
+                 "clear_steps": np.where(st == CLEARED, table[R["clear_step"], ids].astype(np.float64), 0.0),
+                 "progress": np.minimum(np.sqrt(table[R["max_d2"], ids].astype(np.float64) / float(thr)), 1.0)}
+        for k, v in terms.items():
+            out[g, O[k]] = math.fsum(float(x) for x in v)
+            mag[g, O[k]] = math.fsum(abs(float(x)) for x in v)
+    return out, mag
+
+
+def ladder_in(mem, handles, strides, dist2_thr=DIST2_THR):
+    a = Go2nnLadderIn()
+    for k in LADDER_FIELDS:
+        f = getattr(a, k)
+        f.p, (f.env_stride, f.comp_stride) = mem.ptr(handles[k]), strides[k]
+    a.dist2_thr = dist2_thr
+    return a
+
+
+def run_script(lib, mem, N, layout, seed=0):
+    """the scripted sequence on `lib` with its buffers in `mem` -> (table fp32 [NUM, N], Reference)"""
+    rng = np.random.default_rng(seed + N)
+    base, phi = rng.uniform(-50, 50, (N, 2)), rng.uniform(-np.pi, np.pi, N)
+    ref = Reference(N, START, DIST2_THR)
+    first = scripted_step(rng, N, START, base, phi)
+    h, strides = {}, {}
+    for k in LADDER_FIELDS:
+        flat, es, cs = store(first[k], layout)
+        h[k], strides[k] = mem.put(flat), (es, cs)
+    a = ladder_in(mem, h, strides)
+    table = mem.put(np.full((GO2NN_LADDER_NUM, N), 7.0, np.float32))
+    assert lib.go2nn_ladder_begin(C.c_void_p(mem.ptr(table)), N, START, mem.stream) == 0, lib.go2nn_last_error()
+    got = mem.get(table).reshape(GO2NN_LADDER_NUM, N)
+    assert (got[0] == START).all() and not got[1:].any()
+    for call in range(CALLS):
+        d = first if call == 0 else scripted_step(rng, N, START + call, base, phi)
+        for k in LADDER_FIELDS:
+            mem.set(h[k], store(d[k], layout)[0])
+        ref.accumulate(d["root_states"], d["reset_buf"], d["time_out_buf"])
+        assert lib.go2nn_ladder_accumulate(C.byref(a), C.c_void_p(mem.ptr(table)), N, mem.stream) == 0, lib.go2nn_last_error()
+    return mem.get(table).reshape(GO2NN_LADDER_NUM, N), ref
+
+
+def check_table(table, ref, N, what):
+    assert ref.closest >= MARGIN, ref.closest          # the condition under which the rows below must be EXACTLY equal
+    t, r = table.astype(np.float64), ref.t
+    for row in EXACT_ROWS:
+        np.testing.assert_array_equal(t[R[row]], r[R[row]], err_msg=row)
+    assert (r[R["step"]] == START + CALLS).all()
+    e = np.arange(N)
+    want = {0: (RUNNING, 0), 1: (CLEARED, 10), 2: (FELL, 0), 3: (CLEARED, 10), 4: (TIMED_OUT, 0), 5: (FELL, 0)}          # every branch occurred, with the scripted outcome
+    for k, (state, clear_step) in want.items():
+        ids = e % 6 == k
+        assert (r[R["state"], ids] == state).all() and (r[R["clear_step"], ids] == clear_step).all(), k
+    if N > 2:
+        assert np.allclose(r[R["max_d2"], e % 6 == 2], 0.09, rtol=1e-4) and (r[R["max_d2"], e % 6 == 0] == 0).all()
+    # MAX_D2: two differences, two products and a sum, each rounded at most once, with or without contraction: 4 * 2^-24 relative
+    gap, bound = np.abs(t[R["max_d2"]] - r[R["max_d2"]]), 4 * U * np.abs(r[R["max_d2"]])
+    print("%s: closest |d2 - thr| / thr %.4f, largest MAX_D2 gap / bound %.3f" % (what, ref.closest, float((gap / np.maximum(bound, 1e-300)).max())))
+    assert (gap <= bound).all()
+
+
+@pytest.fixture(scope="module")
+def emu():
+    return load_nn_emu()
+
+
+@pytest.mark.parametrize("layout", [0, 1])
+@pytest.mark.parametrize("N", [1, 17, 300])
+def test_accumulate_against_float64(emu, N, layout):
+    table, ref = run_script(emu, HostMemory(), N, layout)
+    check_table(table, ref, N, "host N=%d layout=%d" % (N, layout))
+
+
+def reduce_case(N, G, seed=11):
+    rng = np.random.default_rng(seed + N)
+    table = np.zeros((GO2NN_LADDER_NUM, N), np.float32)
+    table[R["state"]] = rng.integers(0, 4, N)
+    table[R["max_d2"]] = (DIST2_THR * np.exp(rng.normal(-1, 2, N))).astype(np.float32)          # on both sides of the threshold: the cap at 1 occurs
+    table[R["clear_step"]] = rng.integers(1, 500, N)          # (also in rows that never cleared: the reduce must not add them)
+    table[R["x0"]], table[R["y0"]], table[R["step"]] = rng.normal(0, 50, N), rng.normal(0, 50, N), 500
+    group = rng.integers(-2, G + 2, N).astype(np.int32)          # ids outside [0, G) are ignored
+    group[group == 1] = 0                                        # group 1 stays empty
+    return table, group
+
+
+def check_reduce(out, table, group, G, N, what):
+    """the four counts exactly; the fp64 sums to N roundings of the running sum; a progress term is a division and a square root in fp64, at most 2 ulp each -> (N + 4)"""
+    want, mag = reduce_reference(table, group, G, DIST2_THR)
+    for k in ("n", "cleared", "fell", "timed_out"):
+        np.testing.assert_array_equal(out[:, O[k]], want[:, O[k]], err_msg=k)
+    worst = 0.0
+    for k, roundings in (("clear_steps", N), ("progress", N + 4)):
+        gap, bound = np.abs(out[:, O[k]] - want[:, O[k]]), roundings * 2.0 ** -53 * mag[:, O[k]]
+        assert (gap <= bound).all(), (k, gap, bound)
+        worst = max(worst, float((gap / np.maximum(bound, 1e-300)).max()))
+    assert (out[1] == 0).all() and (group == 1).sum() == 0
+    if N >= 17:          # both sides of the cap at 1 occur
+        ratio = table[R["max_d2"]].astype(np.float64) / DIST2_THR
+        assert (ratio > 1).any() and (ratio < 1).any() and (want[:, O["progress"]] < want[:, O["n"]]).any()
+    print("%s: largest reduce gap / bound %.3f" % (what, worst))
+
+
+@pytest.mark.parametrize("N,G", [(1, 3), (17, 3), (300, 5), (4096, 7)])
+def test_reduce_against_fsum(emu, N, G):
+    table, group = reduce_case(N, G)
+    outs = []
+    for _ in range(2):
+        out = np.full((G, GO2NN_LADDER_OUT_NUM), -1.0)
+        assert emu.go2nn_ladder_reduce(C.c_void_p(table.ctypes.data), C.c_void_p(group.ctypes.data), N, G, DIST2_THR, C.c_void_p(out.ctypes.data), None) == 0
+        outs.append(out)
+    assert outs[0].tobytes() == outs[1].tobytes()
+    check_reduce(outs[0], table, group, G, N, "host N=%d" % N)
+
+
+def test_argument_checks(emu):
+    N = 4
+    bufs = {"root_states": np.zeros((N, 13), np.float32), "reset_buf": np.zeros(N, np.uint8), "time_out_buf": np.zeros(N, np.uint8)}
+    table, group, out = np.zeros((GO2NN_LADDER_NUM, N), np.float32), np.zeros(N, np.int32), np.zeros((2, GO2NN_LADDER_OUT_NUM))
+    p = lambda x: C.c_void_p(x.ctypes.data)
+
+    def make_in():
+        a = Go2nnLadderIn()
+        for k, (es, cs) in (("root_states", (13, 1)), ("reset_buf", (1, 0)), ("time_out_buf", (1, 0))):
+            f = getattr(a, k)
+            f.p, f.env_stride, f.comp_stride = bufs[k].ctypes.data, es, cs
+        a.dist2_thr = DIST2_THR
+        return a
+
+    def broken(edit):
+        a = make_in()
+        edit(a)
+        return emu.go2nn_ladder_accumulate(C.byref(a), p(table), N, None)
+    assert emu.go2nn_ladder_accumulate(C.byref(make_in()), p(table), N, None) == 0, emu.go2nn_last_error()
+    assert emu.go2nn_ladder_accumulate(None, p(table), N, None) == EINVAL and emu.go2nn_last_error()
+    assert emu.go2nn_ladder_accumulate(C.byref(make_in()), None, N, None) == EINVAL
+    for n in (0, -1):
+        assert emu.go2nn_ladder_accumulate(C.byref(make_in()), p(table), n, None) == EINVAL
+    for field in LADDER_FIELDS:
+        assert broken(lambda a: setattr(getattr(a, field), "p", None)) == EINVAL and b"null" in emu.go2nn_last_error(), field
+        assert broken(lambda a: setattr(getattr(a, field), "env_stride", 0)) == EINVAL and b"stride" in emu.go2nn_last_error(), field
+    assert broken(lambda a: setattr(a.root_states, "comp_stride", 0)) == EINVAL and b"stride" in emu.go2nn_last_error()
+    assert broken(lambda a: setattr(a.reset_buf, "comp_stride", -1)) == EINVAL and b"stride" in emu.go2nn_last_error()
+    for thr in (0.0, -1.0, float("nan")):
+        assert broken(lambda a: setattr(a, "dist2_thr", thr)) == EINVAL and b"dist2_thr" in emu.go2nn_last_error(), thr
+    assert emu.go2nn_ladder_begin(None, N, 0, None) == EINVAL and emu.go2nn_ladder_begin(p(table), 0, 0, None) == EINVAL and emu.go2nn_last_error()
+    assert emu.go2nn_ladder_begin(p(table), N, -2, None) == 0
+    assert emu.go2nn_ladder_reduce(p(table), p(group), N, 2, DIST2_THR, p(out), None) == 0
+    for args in ((None, p(group), N, 2, DIST2_THR, p(out)), (p(table), None, N, 2, DIST2_THR, p(out)), (p(table), p(group), N, 2, DIST2_THR, None),
+                 (p(table), p(group), 0, 2, DIST2_THR, p(out)), (p(table), p(group), N, 0, DIST2_THR, p(out)), (p(table), p(group), N, 65536, DIST2_THR, p(out)),
+                 (p(table), p(group), N, 2, 0.0, p(out)), (p(table), p(group), N, 2, -0.25, p(out))):
+        assert emu.go2nn_ladder_reduce(*args, None) == EINVAL and emu.go2nn_last_error(), args[2:5]
+
+
+def test_ladder_symbols_and_struct_within_abi_7(emu, tmp_path):
+    assert emu.go2nn_abi_version() == 7 and _nn.GO2NN_ABI_VERSION == 7
+    libs = [os.path.join(ROOT, "tests", "emu", "libgo2nn_emu.so")] + [p for p in [_nn.NN_LIB] if os.path.exists(p)]
+    for path in libs:
+        syms = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
+        for f in ("go2nn_ladder_begin", "go2nn_ladder_accumulate", "go2nn_ladder_reduce"):
+            assert (" T " + f + "\n") in syms, (path, f)
+    names = [n for n, _ in Go2nnLadderIn._fields_]
+    src = tmp_path / "s.c"
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "go2nn.h"\nint main(void) { printf("%zu %d %d %d %d %d %d", sizeof(Go2nnLadderIn), GO2NN_LADDER_NUM, '
+                   'GO2NN_LADDER_OUT_NUM, GO2NN_LADDER_RUNNING, GO2NN_LADDER_CLEARED, GO2NN_LADDER_FELL, GO2NN_LADDER_TIMED_OUT);\n'
+                   + "".join('printf(" %%zu", offsetof(Go2nnLadderIn, %s));\n' % n for n in names) + "return 0; }\n")
+    exe = tmp_path / "s"
+    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), "-o", str(exe), str(src)], check=True)
+    got = [int(x) for x in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
+    assert got[:7] == [C.sizeof(Go2nnLadderIn), len(LADDER_ROWS), len(LADDER_OUT)] + [LADDER_STATES.index(s) for s in ("running", "cleared", "fell", "timed_out")]
+    assert got[7:] == [getattr(Go2nnLadderIn, n).offset for n in names]
+    hdr = open(os.path.join(ROOT, "include", "go2nn.h")).read()
+    for first, last, prefix, mirror in (("GO2NN_LADDER_STEP = 0", "GO2NN_LADDER_NUM }", "GO2NN_LADDER_", LADDER_ROWS),
+                                        ("GO2NN_LADDER_OUT_N = 0", "GO2NN_LADDER_OUT_NUM }", "GO2NN_LADDER_OUT_", LADDER_OUT)):
+        enum = hdr[hdr.index(first):hdr.index(last)]
+        assert [e.strip().split(" ")[0].replace(prefix, "").lower() for e in enum.split(",") if e.strip()] == list(mirror)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------------------------------
+SCENARIOS = [["forward_1.0", 1.0, 0.0, 0.0], ["stand", 0.0, 0.0, 0.0]]          # `stand` cannot cover any distance: the evaluator must say so
+DISTANCES = (0.05, 0.1, 0.02, 0.15, 0.03, 0.07, 0.2)          # [m] the fixed list the evaluator tests take their clearing distance from: the first the float64 reference is not within MARGIN of
+LADDER = dict(num_envs=160, seconds=0.5, warmup_s=0.1, ladder=True, ladder_scenarios=SCENARIOS)
+
+
+def recompute(rec, ev, dist=None):
+    """the whole ladder table from the recorded buffers, in float64, with the fp32 threshold the kernel compares with -> Reference"""
+    thr = np.float32(ev.dist2_thr) if dist is None else np.float32(dist) * np.float32(dist)
+    ref = Reference(ev.num_envs, -ev.warmup_steps, thr)
+    for d in rec:
+        ref.accumulate(d["root_states"], d["reset_buf"], d["time_out_buf"])
+    return ref
+
+
+def recorded_run(emu, ac, dist):
+    rec, text = [], io.StringIO()
+
+    def cb(ev, k, counted):
+        b = ev.env._buf
+        rec.append({n: b[n].detach().clone().numpy() for n in ("root_states", "reset_buf", "time_out_buf", "commands")})
+    with contextlib.redirect_stdout(text):
+        ev = th.make_evaluator(emu, task="go2", cb=cb, ladder_distance=dist, **LADDER)
+    env = ev.env
+    placed = [(env.terrain_levels.clone().numpy(), env.env_origins.clone().numpy(), env.terrain_origins.clone().numpy(), env.terrain_types.clone().numpy())]
+    res = ev.evaluate(ac)
+    placed.append((ev.env.terrain_levels.clone().numpy(), ev.env.env_origins.clone().numpy()))
+    return dict(ev=ev, res=res, rec=rec, placed=placed, dist=dist, printed=text.getvalue(), ltable=ev.ltable.clone().numpy())
+
+
+@pytest.fixture(scope="module")
+def ladder_run(emu):
+    """ONE evaluation of task go2 with the ladder on and the per-step buffers recorded.  The robots' motion does not depend on the clearing distance (the ladder only reads),
+    so the distance is chosen on the first run's recording, by the float64 reference alone; a second evaluator is built only if that is not the list's first entry"""
+    ac = th.small_actor_critic()
+    run = recorded_run(emu, ac, DISTANCES[0])
+    tried = [(d, recompute(run["rec"], run["ev"], d).closest) for d in DISTANCES]
+    chosen = [d for d, closest in tried if closest >= MARGIN][:1]
+    if chosen and chosen[0] != DISTANCES[0]:
+        run["ev"].close()
+        run = recorded_run(emu, ac, chosen[0])
+    run.update(ac=ac, tried=tried, chosen=chosen, ref=recompute(run["rec"], run["ev"]))
+    yield run
+    run["ev"].close()
+
+
+def test_a_clearing_distance_away_from_every_robot_was_found(ladder_run):
+    print("ladder_distance candidates (distance, closest |d2 - thr| / thr): %s -> %s" % (["%.2f: %.2e" % t for t in ladder_run["tried"]], ladder_run["chosen"]))
+    assert ladder_run["chosen"] == [ladder_run["dist"]] and ladder_run["ref"].closest >= MARGIN, ladder_run["tried"]
+
+
+def test_evaluator_places_the_robots_on_their_levels(ladder_run):
+    ev, rec = ladder_run["ev"], ladder_run["rec"]
+    T, L, S, N = len(ev.terrain_names), 10, len(SCENARIOS), ev.num_envs
+    assert ev.levels == list(range(10)) and ev.num_cells == T * L * S and T > 1 and ev.ladder_distance == ladder_run["dist"]
+    levels0, origins0, terrain_origins, types = ladder_run["placed"][0]
+    kinds = ev.env.terrain_cols2id[ev.env.terrain_types].numpy()
+    for ki, k in enumerate(sorted(set(kinds.tolist()))):          # within a kind the (level, scenario) cells are taken in turn: sizes within one of each other
+        ids = kinds == k
+        local = ev.cell_host[ids] - ki * L * S
+        assert local.min() >= 0 and local.max() < L * S
+        sizes = np.bincount(local, minlength=L * S)
+        assert sizes.max() - sizes.min() <= 1 and sizes.sum() == ids.sum()
+        assert (ev.cell_host[ids] == (ki * L + ev.level_index_host[ids]) * S + ev.group_host[ids] % S).all() and (ev.group_host[ids] // S == ki).all()
+    assert len(set(ev.level_of_env.tolist())) == L
+    for levels, origins in (ladder_run["placed"][0][:2], ladder_run["placed"][1]):          # before and after evaluate
+        np.testing.assert_array_equal(levels, ev.level_of_env)
+        np.testing.assert_array_equal(origins, terrain_origins[ev.level_of_env, types])
+    # the robots were reset onto those origins (rows are terrain_length = 8 m apart), and the scenario's command holds at every step
+    assert np.abs(rec[0]["root_states"][:, :2] - origins0[:, :2]).max() < 4.0
+    want = np.asarray([s[1:4] for s in SCENARIOS], np.float32)[ev.group_host % S]
+    for d in rec:
+        np.testing.assert_array_equal(d["commands"][:, :3], want)
+    assert len(rec) == ev.warmup_steps + ev.steps == 5 + 25
+
+
+def test_evaluator_ladder_table_against_float64(ladder_run):
+    from go2_rl_gym_amd.utils.evaluator import LADDER_KEYS, RESULT_KEYS
+    ev, res, ref = ladder_run["ev"], ladder_run["res"], ladder_run["ref"]
+    N, G = ev.num_envs, ev.num_cells
+    # the per-env table itself, then the reduce: the counts exactly, the progress to the bound of MAX_D2 (4 * 2^-24 relative; a square root halves it) plus the fp64 sum's
+    t = ladder_run["ltable"].astype(np.float64)
+    for row in EXACT_ROWS:
+        np.testing.assert_array_equal(t[R[row]], ref.t[R[row]], err_msg=row)
+    assert (np.abs(t[R["max_d2"]] - ref.t[R["max_d2"]]) <= 4 * U * ref.t[R["max_d2"]]).all()
+    want, mag = ref.reduce(ev.cell_host, G)
+    got = res["ladder_table"]
+    assert got.shape == (G, GO2NN_LADDER_OUT_NUM) and got[:, O["n"]].sum() == N
+    for k in ("n", "cleared", "fell", "timed_out", "clear_steps"):
+        np.testing.assert_array_equal(got[:, O[k]], want[:, O[k]], err_msg=k)
+    assert (np.abs(got[:, O["progress"]] - want[:, O["progress"]]) <= (2 * U + (N + 4) * 2.0 ** -53) * mag[:, O["progress"]]).all()
+    states = np.bincount(ref.t[R["state"]].astype(int), minlength=4)
+    print("ladder_distance %.2f m: %d running, %d cleared, %d fell, %d timed out; overall %s" % (ladder_run["dist"], *states, {k: res["overall"][k] for k in ("cleared", "mean_level_cleared")}))
+    assert states[CLEARED] > 0 and len(set(ref.t[R["clear_step"], ref.t[R["state"]] == CLEARED].tolist())) > 3          # (robots latch at different steps)
+    # the reported figures are those counts
+    T, L, S = len(ev.terrain_names), len(ev.levels), len(SCENARIOS)
+    w4 = want.reshape(T, L, S, -1)
+    for ti, tname in enumerate(ev.terrain_names):
+        for li, lv in enumerate(ev.levels):
+            for si, s in enumerate(SCENARIOS):
+                cell, w = res["ladder"][tname][lv][s[0]], w4[ti, li, si]
+                assert set(cell) == set(RESULT_KEYS) | set(LADDER_KEYS) and cell["n_envs"] == w[O["n"]]
+                if w[O["n"]] > 0:
+                    assert (cell["cleared"], cell["fell"], cell["timed_out"]) == tuple(w[O[k]] / w[O["n"]] for k in ("cleared", "fell", "timed_out"))
+                    assert cell["cleared"] + cell["fell"] + cell["timed_out"] <= 1 and 0 <= cell["progress"] <= 1
+                    assert cell["time_to_clear_s"] == w[O["clear_steps"]] / w[O["cleared"]] * ev.dt if w[O["cleared"]] > 0 else math.isnan(cell["time_to_clear_s"])
+                else:
+                    assert all(math.isnan(cell[k]) for k in LADDER_KEYS)
+        curve = [w4[ti, li, 0, O["cleared"]] / w4[ti, li, 0, O["n"]] if w4[ti, li, 0, O["n"]] > 0 else 0.0 for li in range(L)]
+        top = -1
+        for lv, c in zip(ev.levels, curve):
+            if c < 0.5:
+                break
+            top = lv
+        assert res["ladder_summary"][tname] == {"level_cleared": top, "mean_level_cleared": float(sum(curve))}
+    assert res["overall"]["cleared"] == want[:, O["cleared"]].sum() / N
+    assert res["overall"]["mean_level_cleared"] == float(np.mean([v["mean_level_cleared"] for v in res["ladder_summary"].values()]))
+    assert res["levels"] == ev.levels and res["ladder_distance"] == ladder_run["dist"]
+    # res["groups"] / res["table"] keep their shape: a (terrain, scenario) pair is the sum of its level cells
+    assert res["table"].shape == (T * S, 12) and res["ladder_cell_table"].shape == (G, 12)
+    np.testing.assert_array_equal(res["table"], res["ladder_cell_table"].reshape(T, L, S, -1).sum(1).reshape(T * S, -1))
+    for ti, tname in enumerate(ev.terrain_names):
+        for s in SCENARIOS:
+            assert set(res["groups"][tname][s[0]]) == set(RESULT_KEYS)
+            assert res["groups"][tname][s[0]]["n_envs"] == sum(res["ladder"][tname][lv][s[0]]["n_envs"] for lv in ev.levels)
+    assert res["overall"]["n_envs"] == N
+
+
+def test_evaluator_warnings_and_outputs(ladder_run):
+    from go2_rl_gym_amd.utils.evaluator import LADDER_KEYS, RESULT_KEYS, format_table, results_dict, scalars
+    ev, res, printed = ladder_run["ev"], ladder_run["res"], ladder_run["printed"]
+    assert "ladder scenario 'stand'" in printed and "cannot clear" in printed and "forward_1.0" not in printed
+    assert "(terrain x level x scenario) cells have fewer than 4 robots" in printed
+    tags = dict(scalars(res))
+    for t in ev.terrain_names:
+        assert tags["Eval/ladder/%s/level_cleared" % t] == res["ladder_summary"][t]["level_cleared"]
+        assert tags["Eval/ladder/%s/mean_level_cleared" % t] == res["ladder_summary"][t]["mean_level_cleared"]
+    assert tags["Eval/ladder/mean_level_cleared"] == res["overall"]["mean_level_cleared"] and "Eval/lin_vel_err" in tags and "Eval/flat/stand/tilt" in tags
+    rd = yaml.safe_load(yaml.safe_dump(results_dict(res, 3)))
+    assert set(rd["ladder"]) == set(ev.terrain_names) == set(rd["ladder_summary"]) and sorted(rd["ladder"]["flat"]) == ev.levels == rd["ladder_levels"]
+    assert set(rd["ladder"]["flat"][0]["forward_1.0"]) == set(RESULT_KEYS) | set(LADDER_KEYS) and set(rd["ladder_summary"]["flat"]) == {"level_cleared", "mean_level_cleared"}
+    assert rd["ladder_distance"] == ladder_run["dist"] and rd["ladder_pass_share"] == 0.5
+    text = format_table(res)
+    print(text)
+    assert "cleared @ level" in text and "level_cleared" in text and "mean_level_cleared" in text
+    block = text.split("\n\n")[-1].splitlines()
+    assert len(block) == 1 + len(ev.terrain_names) + 1 and [l.split()[0] for l in block[1:-1]] == ev.terrain_names
+
+
+def test_evaluator_is_reproducible(emu, ladder_run):
+    """(after the tests that look at the first evaluation's simulator) the same weights: byte-identical tables; other weights: another result"""
+    ev, res, ac = ladder_run["ev"], ladder_run["res"], ladder_run["ac"]
+    again = ev.evaluate(ac)
+    assert again["table"].tobytes() == res["table"].tobytes() and again["ladder_table"].tobytes() == res["ladder_table"].tobytes() and str(again["ladder"]) == str(res["ladder"])
+    np.testing.assert_array_equal(ev.env.terrain_levels.numpy(), ev.level_of_env)          # the fresh simulator's robots stand on their levels too
+    other = ev.evaluate(th.small_actor_critic(1))
+    assert other["table"].tobytes() != res["table"].tobytes() and other["ladder_table"].tobytes() != res["ladder_table"].tobytes()
+    assert other["ladder_table"][:, :1].tobytes() == res["ladder_table"][:, :1].tobytes()          # (the cells themselves do not depend on the weights)
+
+
+def test_ladder_off_changes_nothing(emu):
+    """ladder = False: no ladder key in the result, nothing allocated, and the table of an evaluator whose config never heard of the ladder, byte for byte"""
+    ac = th.small_actor_critic()
+    plain = th.make_evaluator(emu)
+    assert not any(k.startswith("ladder") for k in th.EVAL)
+    res0 = plain.evaluate(ac)
+    plain.close()
+    off = th.make_evaluator(emu, ladder=False, ladder_levels=[0, 1], ladder_scenarios=SCENARIOS, ladder_distance=0.1, ladder_pass_share=0.9)
+    res1 = off.evaluate(ac)
+    assert res1["table"].tobytes() == res0["table"].tobytes() and str(res1["groups"]) == str(res0["groups"]) and str(res1["overall"]) == str(res0["overall"])
+    assert set(res1) == set(res0) and not any("ladder" in k or k == "levels" for k in res1) and "cleared" not in res1["overall"]
+    assert not hasattr(off, "ltable") and not hasattr(off, "lout") and off.ladder is False
+    off.close()
+    _, fresh = task_registry.get_cfgs("go2_cts")
+    e = fresh.evaluation
+    assert (e.ladder, e.ladder_levels, e.ladder_scenarios, e.ladder_distance, e.ladder_pass_share) == (False, None, [["forward_1.0", 1.0, 0.0, 0.0]], None, 0.5)
+    _, fresh = task_registry.get_cfgs("go2")
+    assert fresh.evaluation.ladder is False and fresh.evaluation.ladder_pass_share == 0.5
+
+
+def test_ladder_configuration_errors(emu):
+    with pytest.raises(ValueError, match="terrain levels"):
+        th.make_evaluator(emu, task="go2_flat", ladder=True)
+    with pytest.raises(ValueError, match="perturbations"):
+        th.make_evaluator(emu, task="go2", ladder=True, perturbations=[["nominal", {}]])
+    for bad in ([], [3, 2], [0, 10], [-1, 0], [1, 1]):
+        with pytest.raises(ValueError, match="ladder_levels"):
+            th.make_evaluator(emu, task="go2", ladder=True, ladder_levels=bad)
+    with pytest.raises(ValueError, match="ladder_distance"):
+        th.make_evaluator(emu, task="go2", ladder=True, ladder_distance=0.0)
+    args = get_args(["--task", "go2", "--ladder"])
+    assert args.ladder is True and get_args(["--task", "go2"]).ladder is False
+
+
+def test_unreachable_scenario_warning_with_the_default_distance(emu, capsys, monkeypatch):
+    """the default clearing distance is half a tile (terrain_length / 2 = 4 m): forward_1.0 covers 1 m in the 1 s of th.EVAL and is warned about, 3-4-5 m/s is not"""
+    from go2_rl_gym_amd.utils import evaluator as E
+
+    class Configured(Exception):
+        pass
+
+    def no_simulator(self):          # the settings are checked and reported before the first simulator is built: stop there
+        raise Configured()
+    monkeypatch.setattr(E.PolicyEvaluator, "_make_env", no_simulator)
+    capsys.readouterr()
+    with pytest.raises(Configured):
+        th.make_evaluator(emu, task="go2", ladder=True, ladder_scenarios=[["forward_1.0", 1.0, 0.0, 0.0], ["diag", 3.0, 4.0, 0.0]])
+    out = capsys.readouterr().out
+    assert "ladder scenario 'forward_1.0' covers at most 1.00 m in 1.0 s" in out and "4.00 m" in out and "diag" not in out
+
+
+def test_cli_names_the_checkpoint_that_gets_furthest(emu, tmp_path, capsys, monkeypatch):
+    """a tiny go2 run on the oracle (a terrain of 3 rows x 7 columns, two checkpoints), then scripts/evaluate.py --all_checkpoints --ladder --metric mean_level_cleared"""
+    from go2_rl_gym_amd.scripts.evaluate import HIGHER_IS_BETTER, evaluate
+    assert "mean_level_cleared" in HIGHER_IS_BETTER and "cleared" in HIGHER_IS_BETTER
+    env_cfg, train_cfg = copy.deepcopy(task_registry.env_cfgs["go2"]), copy.deepcopy(task_registry.train_cfgs["go2"])
+    env_cfg.terrain.num_rows, env_cfg.terrain.num_cols, env_cfg.terrain.max_init_terrain_level = 3, 7, 2
+    train_cfg.runner.save_interval = 1
+    e = train_cfg.evaluation
+    e.num_envs, e.seconds, e.warmup_s, e.ladder_distance = 84, 0.4, 0.1, 0.05
+    monkeypatch.setitem(task_registry.env_cfgs, "go2", env_cfg)
+    monkeypatch.setitem(task_registry.train_cfgs, "go2", train_cfg)
+    base = ["--task", "go2", "--num_envs", "16", "--headless", "--sim_device", "cpu", "--rl_device", "cpu", "--seed", "5"]
+    args = get_args(base)
+    env, _ = task_registry.make_env("go2", args, lib=load_oracle())
+    runner, _ = task_registry.make_alg_runner(env, "go2", args, log_root=str(tmp_path))
+    runner.learn(1)
+    env.close()
+    assert not os.path.exists(os.path.join(runner.log_dir, "eval_results"))
+    capsys.readouterr()
+    out = evaluate(base + ["--ladder", "--all_checkpoints", "--metric", "mean_level_cleared"], log_root=str(tmp_path), env_kwargs={"lib": load_oracle()},
+                   evaluator_kwargs={"nn_lib": emu})
+    names = [r["checkpoint"] for r in out["checkpoints"]]
+    assert names == ["model_0.pt", "model_1.pt"] and out["metric"] == "mean_level_cleared" and out["best"] in names
+    assert out["best_value"] == max(r["overall"]["mean_level_cleared"] for r in out["checkpoints"]) and 0 <= out["best_value"] <= 3
+    for r in out["checkpoints"]:
+        assert set(r["ladder_summary"]) == set(r["groups"]) and all(-1 <= v["level_cleared"] <= 2 for v in r["ladder_summary"].values())
+    text = capsys.readouterr().out
+    assert "cleared @ level" in text and json.loads([l for l in text.splitlines() if l.startswith("{")][-1])["best"] == out["best"]
+    d = yaml.safe_load(open(os.path.join(runner.log_dir, "eval_results", "ladder_1.yaml")))
+    assert d["iteration"] == 1 and d["ladder_levels"] == [0, 1, 2] and set(d["ladder_summary"]) == set(out["checkpoints"][1]["ladder_summary"])
