@@ -40,6 +40,14 @@ LADDER_OUT = ("n", "cleared", "fell", "timed_out", "clear_steps", "progress")
 LADDER_STATES = ("running", "cleared", "fell", "timed_out")
 GO2NN_LADDER_NUM, GO2NN_LADDER_OUT_NUM = len(LADDER_ROWS), len(LADDER_OUT)
 LADDER_FIELDS = ("root_states", "reset_buf", "time_out_buf")
+# the evaluator's command maneuvers: the rows of the table [GO2NN_MANEUVER_NUM, N] in the order of the enum GO2NN_MANEUVER_* of include/go2nn.h (per-env state first, then
+# the accumulators go2nn_maneuver_reduce sums; its output columns are those plus "n"), and the buffers of Go2nnManeuverIn in the struct's order
+MANEUVER_ROWS = ("step", "open", "ok_run", "is_settled", "is_fell", "peak_tilt", "switches", "switch_falls", "settled", "settle_steps", "win_steps", "win_lin_err",
+                 "win_ang_err", "peak_tilt_sum")
+GO2NN_MANEUVER_NUM, GO2NN_MANEUVER_ACC_FIRST, GO2NN_MANEUVER_MAX_SPECS, GO2NN_MANEUVER_MAX_SEGS = len(MANEUVER_ROWS), MANEUVER_ROWS.index("switches"), 64, 8
+GO2NN_MANEUVER_ACC_NUM = GO2NN_MANEUVER_NUM - GO2NN_MANEUVER_ACC_FIRST
+MANEUVER_OUT = MANEUVER_ROWS[GO2NN_MANEUVER_ACC_FIRST:] + ("n",)
+MANEUVER_FIELDS = ("commands", "base_lin_vel", "base_ang_vel", "projected_gravity", "reset_buf", "time_out_buf")
 _cached = None
 
 
@@ -118,6 +126,15 @@ class Go2nnLadderIn(C.Structure):          # (within ABI 7)
     _fields_ = [(k, Go2nnEvalField) for k in LADDER_FIELDS] + [("dist2_thr", C.c_float), ("pad_", C.c_int32)]
 
 
+class Go2nnManeuverSpec(C.Structure):          # (within ABI 7)
+    _fields_ = [("count", C.c_int32), ("window", C.c_int32), ("hold", C.c_int32), ("thr_lin", C.c_float), ("thr_ang", C.c_float),
+                ("start", C.c_int32 * GO2NN_MANEUVER_MAX_SEGS), ("cmd", (C.c_float * 3) * GO2NN_MANEUVER_MAX_SEGS)]
+
+
+class Go2nnManeuverIn(C.Structure):          # (within ABI 7)
+    _fields_ = [(k, Go2nnEvalField) for k in MANEUVER_FIELDS] + [("num_specs", C.c_int32), ("num_commands", C.c_int32)]
+
+
 def trace_env_ids(env_ids, num_envs):
     """the tracked robots of go2nn_trace_record as the kernel needs them -> int32 numpy [K], strictly increasing, each in [0, num_envs).  The kernel cannot report a bad
     index (it would read outside the buffers), so anything else raises here."""
@@ -190,6 +207,11 @@ def bind(path):
     lib.go2nn_ladder_begin.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
     lib.go2nn_ladder_accumulate.argtypes = [C.POINTER(Go2nnLadderIn), C.c_void_p, C.c_int32, C.c_void_p]
     lib.go2nn_ladder_reduce.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p]
+    lib.go2nn_maneuver_check_specs.argtypes = [C.c_void_p, C.c_int32]
+    lib.go2nn_maneuver_begin.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
+    lib.go2nn_maneuver_apply.argtypes = [C.POINTER(Go2nnManeuverIn), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+    lib.go2nn_maneuver_accumulate.argtypes = [C.POINTER(Go2nnManeuverIn), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+    lib.go2nn_maneuver_reduce.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
     if lib.go2nn_abi_version() != GO2NN_ABI_VERSION:
         raise RuntimeError("%s: ABI version %d, expected %d" % (path, lib.go2nn_abi_version(), GO2NN_ABI_VERSION))
     return lib

@@ -288,6 +288,11 @@ class LeggedRobotCfgPPO(BaseConfig):
         ladder_scenarios = [["forward_1.0", 1.0, 0.0, 0.0]]          # the ladder's own scenario list (name, vx, vy, yaw rate); the per-terrain summary is over the first
         ladder_distance = None  # [m] cleared = further than this from where the robot stood at the first counted step.  None: terrain.terrain_length / 2, the simulator's own promotion rule
         ladder_pass_share = 0.5 # level_cleared counts a level as passed when this share of its robots cleared it: a convention (the majority of a cell's robots), not a measurement
+        maneuvers = None        # None: commands that never change.  A list of [name, [[seconds, vx, vy, yaw rate], ...]] (first segment at 0 s, at most 8, the last runs to the horizon's end) that takes the scenarios' place; --maneuvers: utils/evaluator.py DEFAULT_MANEUVERS
+        maneuver_window_s = 3.0 # the time after a command switch over which fall, settling, tracking errors and peak tilt are scored (inside the segment and the horizon)
+        maneuver_hold_s = 0.3   # settled = both errors stay below their thresholds for this long (the settle time includes it)
+        maneuver_thr_lin = 0.3  # [m/s] ... the linear velocity error (recover_thr's convention, not a measurement)
+        maneuver_thr_ang = 0.3  # [rad/s] ... and the yaw rate error
 
 
 class LeggedRobotCfgCTS(BaseConfig):
@@ -363,6 +368,11 @@ class LeggedRobotCfgCTS(BaseConfig):
         ladder_scenarios = [["forward_1.0", 1.0, 0.0, 0.0]]          # the ladder's own scenario list (name, vx, vy, yaw rate); the per-terrain summary is over the first
         ladder_distance = None  # [m] cleared = further than this from where the robot stood at the first counted step.  None: terrain.terrain_length / 2, the simulator's own promotion rule
         ladder_pass_share = 0.5 # level_cleared counts a level as passed when this share of its robots cleared it: a convention (the majority of a cell's robots), not a measurement
+        maneuvers = None        # None: commands that never change.  A list of [name, [[seconds, vx, vy, yaw rate], ...]] (first segment at 0 s, at most 8, the last runs to the horizon's end) that takes the scenarios' place; --maneuvers: utils/evaluator.py DEFAULT_MANEUVERS
+        maneuver_window_s = 3.0 # the time after a command switch over which fall, settling, tracking errors and peak tilt are scored (inside the segment and the horizon)
+        maneuver_hold_s = 0.3   # settled = both errors stay below their thresholds for this long (the settle time includes it)
+        maneuver_thr_lin = 0.3  # [m/s] ... the linear velocity error (recover_thr's convention, not a measurement)
+        maneuver_thr_ang = 0.3  # [rad/s] ... and the yaw rate error
 
 
 class LeggedRobotCfgMoECTS(LeggedRobotCfgCTS):

@@ -8,8 +8,11 @@ takes push_falls, recovered, recovery_time_s, peak_lin_vel_err and peak_tilt.
 --ladder (terrain tasks) places the robots on every terrain level and adds the per-terrain table of the share that cleared each level; --metric then also takes
 mean_level_cleared and cleared (higher is better), so --all_checkpoints --ladder --metric mean_level_cleared names the checkpoint that gets furthest.  The whole curve goes to eval_results/ladder_<checkpoint number>.yaml
 in the run's directory.
+--maneuvers scores scripted command changes (start, brake, reverse, turn: utils/evaluator.py DEFAULT_MANEUVERS) in the scenarios' place; --metric then also takes
+switch_falls, settle_time_s, window_lin_vel_err, window_ang_vel_err (lower is better) and settled (higher is better).
 --record N also records N robots of every (terrain x scenario) group and writes eval_results/trace_<checkpoint number>.npz into the run's directory."""
 import json
+import math
 import os
 import sys
 from pathlib import Path
@@ -20,7 +23,7 @@ from go2_rl_gym_amd.utils.evaluator import PolicyEvaluator, format_table, result
 from go2_rl_gym_amd.utils.helpers import _checkpoint_number, get_load_path
 from go2_rl_gym_amd.utils.task_registry import ROOT_DIR, task_registry
 
-HIGHER_IS_BETTER = ("survival", "speed_along_cmd", "recovered", "mean_level_cleared", "cleared")
+HIGHER_IS_BETTER = ("survival", "speed_along_cmd", "recovered", "mean_level_cleared", "cleared", "settled")
 
 
 def _own_flags(argv):
@@ -38,6 +41,16 @@ def _own_flags(argv):
             rest.append(a)
         k += 1
     return own, rest
+
+
+def best_checkpoint(rows, metric):
+    """the row with the best overall `metric`.  A figure that does not exist (NaN: settle_time_s without a settled switch, recovery_time_s without a recovered push) ranks
+    last, whatever the order of the rows"""
+    higher = metric in HIGHER_IS_BETTER
+    worst = float("-inf") if higher else float("inf")
+    value = lambda r: r["overall"][metric]
+    rank = lambda r: worst if isinstance(value(r), float) and math.isnan(value(r)) else value(r)
+    return (max if higher else min)(rows, key=rank)
 
 
 def evaluate(argv=None, log_root="default", env_kwargs=None, evaluator_kwargs=None):
@@ -68,6 +81,8 @@ def evaluate(argv=None, log_root="default", env_kwargs=None, evaluator_kwargs=No
         rows.append({"checkpoint": p.name, "overall": res["overall"], "groups": res["groups"]})
         if res.get("perturbations") is not None:
             rows[-1]["perturbations"] = res["perturbations"]
+        if res.get("maneuvers") is not None:
+            rows[-1]["maneuvers"] = res["maneuvers"]
         if res.get("ladder_summary") is not None:
             rows[-1]["ladder_summary"] = res["ladder_summary"]
             import yaml
@@ -81,7 +96,7 @@ def evaluate(argv=None, log_root="default", env_kwargs=None, evaluator_kwargs=No
             print("trace: %s" % write_trace(os.path.join(str(p.parent), "eval_results", "trace_%s.npz" % _checkpoint_number(p)), res["trace"]))
     metric = own["metric"]
     key = lambda r: r["overall"][metric]
-    best = (max if metric in HIGHER_IS_BETTER else min)(rows, key=key)
+    best = best_checkpoint(rows, metric)
     out = {"task": args.task, "metric": metric, "best": best["checkpoint"], "best_value": key(best), "checkpoints": rows}
     print(json.dumps(out))
     ev.close()

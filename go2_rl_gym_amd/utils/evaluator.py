@@ -38,6 +38,16 @@ robot on the device, so it survives the simulator's reset of a fallen robot.  Pe
 `progress` (largest distance reached / `ladder_distance`, capped at 1); per terrain kind `level_cleared` (the highest level up to which every level has cleared >=
 `ladder_pass_share`) and `mean_level_cleared` (the sum of `cleared` over the levels).  With `ladder = False` nothing of this is allocated or launched.
 
+Commands that change: with `evaluation.maneuvers` (--maneuvers selects DEFAULT_MANEUVERS; a list of [name, [[seconds, vx, vy, yaw rate], ...]]) the maneuvers take the
+scenarios' place: within a terrain kind the robots take the maneuvers in turn, cell index = terrain * M + maneuver.  The schedule of every maneuver lives on the device
+(at most 8 segments in counted steps, the first at step 0 — it also covers the warm-up —, the last to the horizon's end), and a step is
+    { policy, go2nn_maneuver_apply, go2sim_step, go2nn_maneuver_accumulate, go2nn_eval_accumulate }
+— two more launches (csrc/go2nn_maneuver.h; the rule and the switch convention are in include/go2nn.h), inside the captured chunk, both writing the command row, so the
+copy of the commands is not issued — and one more reduce at the end.  Per command switch, over the `maneuver_window_s` after it: `switch_falls` (share of switches after
+which the robot fell inside the window), `settled` (share after which both velocity errors stayed below `maneuver_thr_lin` / `maneuver_thr_ang` for `maneuver_hold_s`),
+`settle_time_s` (switch -> end of that hold, mean over the settled switches), `window_lin_vel_err` / `window_ang_vel_err` (means over the window's steps), `peak_tilt`
+(largest value inside the window, mean over switches).  With `maneuvers = None` nothing of this is allocated or launched.
+
 Isolated: nothing of the training env, the model, the optimizer or torch's generators is written; policy state the evaluation needs (the CTS observation history, the
 recurrent memory's hidden state) lives in buffers of the evaluator."""
 import copy
@@ -50,7 +60,8 @@ import torch
 
 from .. import _abi
 from .._nn import (EVAL_FIELDS, EVAL_METRICS, GO2NN_EVAL_NUM, GO2NN_RNN_GRU, GO2NN_RNN_LSTM, GO2NN_ROBUST_ACC_NUM, GO2NN_ROBUST_MAX_SPECS, GO2NN_ROBUST_NUM, ROBUST_FIELDS, ROBUST_MASK,
-                   GO2NN_LADDER_NUM, GO2NN_LADDER_OUT_NUM, LADDER_FIELDS, LADDER_OUT, Go2nnEvalIn, Go2nnFwdJob, Go2nnLadderIn, Go2nnMlpIO, Go2nnRnnCellJob, Go2nnRobustIn,
+                   GO2NN_LADDER_NUM, GO2NN_LADDER_OUT_NUM, LADDER_FIELDS, LADDER_OUT, GO2NN_MANEUVER_ACC_NUM, GO2NN_MANEUVER_MAX_SEGS, GO2NN_MANEUVER_MAX_SPECS, GO2NN_MANEUVER_NUM,
+                   MANEUVER_FIELDS, MANEUVER_OUT, Go2nnEvalIn, Go2nnFwdJob, Go2nnLadderIn, Go2nnManeuverIn, Go2nnManeuverSpec, Go2nnMlpIO, Go2nnRnnCellJob, Go2nnRobustIn,
                    Go2nnRobustSpec, PackedMlp)
 from .helpers import class_to_dict
 
@@ -65,6 +76,12 @@ ROBUST_KEYS = ("pushes", "push_falls", "recovered", "recovery_time_s", "peak_lin
 DEFAULT_LADDER_SCENARIOS = [["forward_1.0", 1.0, 0.0, 0.0]]
 LADDER_KEYS = ("cleared", "fell", "timed_out", "time_to_clear_s", "progress")
 LADDER_SUMMARY_KEYS = ("level_cleared", "mean_level_cleared")
+# name, [[seconds, vx, vy, yaw rate], ...]: segment k holds from its time (counted; the first is 0 and also covers the warm-up) to the next one's; for the 10 s horizon
+DEFAULT_MANEUVERS = [["start_1.0", [[0.0, 0.0, 0.0, 0.0], [5.0, 1.0, 0.0, 0.0]]], ["brake_1.0", [[0.0, 1.0, 0.0, 0.0], [5.0, 0.0, 0.0, 0.0]]],
+                     ["brake_2.0", [[0.0, 2.0, 0.0, 0.0], [5.0, 0.0, 0.0, 0.0]]], ["reverse_1.0", [[0.0, 1.0, 0.0, 0.0], [5.0, -1.0, 0.0, 0.0]]],
+                     ["sidestep_flip_0.5", [[0.0, 0.0, 0.5, 0.0], [5.0, 0.0, -0.5, 0.0]]], ["turn_flip_1.0", [[0.0, 0.0, 0.0, 1.0], [5.0, 0.0, 0.0, -1.0]]],
+                     ["walk_into_turn_1.0", [[0.0, 1.0, 0.0, 0.0], [5.0, 1.0, 0.0, 1.0]]]]
+MANEUVER_KEYS = ("switches", "switch_falls", "settled", "settle_time_s", "window_lin_vel_err", "window_ang_vel_err", "peak_tilt")
 MAX_CHUNK = 50
 # The accumulate kernel runs AFTER the env step, when the simulator has already rolled its action history (last_actions = this step's actions): the previous step's
 # actions — the kernel's `last_actions` input — are then in the simulator's last_last_actions buffer.
@@ -258,7 +275,8 @@ class PolicyEvaluator:
         """env_cfg: the task's env config (copied, never modified);  evaluation: the train config's `evaluation` section (class or dict).
         lib / nn_lib: the go2sim / go2nn libraries — tests hand in the CPU oracle and the host build; the product passes neither and runs on the HIP libraries or not at all.
         step_callback(evaluator, step, counted): called after every eager step with the buffers the accumulate kernel has just read (tests record them).
-        apply_callback(evaluator, step, counted): with perturbations, called in every eager step right after go2nn_robust_apply, before the simulator steps."""
+        apply_callback(evaluator, step, counted): with perturbations / maneuvers, called in every eager step right after go2nn_robust_apply / go2nn_maneuver_apply, before the
+        simulator steps."""
         from ..envs.base.legged_robot import LeggedRobot
         self.ev = evaluation
         self.cfg = evaluation_env_cfg(env_cfg, evaluation)
@@ -269,8 +287,14 @@ class PolicyEvaluator:
         perts = _get(evaluation, "perturbations")
         self.perturbations = [[str(p[0]), dict(p[1] or {})] for p in perts] if perts else None
         self.ladder = bool(_get(evaluation, "ladder", False))
+        mans = _get(evaluation, "maneuvers")
+        self.maneuvers = [[str(m[0]), [[float(x) for x in seg] for seg in m[1]]] for m in mans] if mans else None
+        if self.maneuvers is not None and (self.ladder or self.perturbations is not None):
+            raise ValueError("evaluation.maneuvers cannot be combined with evaluation.ladder or evaluation.perturbations: one evaluation splits the robots along ONE extra axis")
         if self.ladder:
             self._init_ladder()
+        elif self.maneuvers is not None:          # the maneuvers take the scenarios' place: a "scenario" per maneuver, its command that of the first segment
+            self._init_maneuvers()
         else:
             self.scenarios = [list(s) for s in (_get(evaluation, "scenarios") or DEFAULT_SCENARIOS)]
         self.terrain_level = int(_get(evaluation, "terrain_level", 5))
@@ -300,6 +324,8 @@ class PolicyEvaluator:
             self._build_robust()
         if self.ladder:
             self._build_ladder()
+        if self.maneuvers is not None:
+            self._build_maneuvers()
         self.dof_limits = self.env.dof_pos_limits.contiguous().clone()
         self._policy, self._policy_of = None, None
         self.recorder = None
@@ -364,6 +390,61 @@ class PolicyEvaluator:
             if reach <= self.ladder_distance:
                 print("[go2_rl_gym_amd] evaluation: ladder scenario %r covers at most %.2f m in %.1f s at its command and cannot clear the %.2f m of evaluation.ladder_distance; "
                       "raise evaluation.seconds" % (s[0], reach, seconds, self.ladder_distance))
+
+    def _init_maneuvers(self):
+        """the maneuvers' shape, checked before anything is built (the schedule in steps needs the simulator's dt: _build_maneuvers)"""
+        mans = self.maneuvers
+        names = [m[0] for m in mans]
+        if len(mans) > GO2NN_MANEUVER_MAX_SPECS:
+            raise ValueError("evaluation.maneuvers: at most %d maneuvers, got %d" % (GO2NN_MANEUVER_MAX_SPECS, len(mans)))
+        if len(set(names)) != len(names):
+            raise ValueError("evaluation.maneuvers: the maneuvers need distinct names, got %r" % (names,))
+        for name, segs in mans:
+            if not 1 <= len(segs) <= GO2NN_MANEUVER_MAX_SEGS or any(len(seg) != 4 for seg in segs):
+                raise ValueError("maneuver %r: 1 .. %d segments [seconds, vx, vy, yaw rate], got %r" % (name, GO2NN_MANEUVER_MAX_SEGS, segs))
+            if segs[0][0] != 0.0:
+                raise ValueError("maneuver %r: the first segment starts at 0 s, got %r" % (name, segs[0][0]))
+        self.scenarios = [[name] + segs[0][1:4] for name, segs in mans]
+
+    def _build_maneuvers(self):
+        """the maneuvers as the kernels read them: M specs and the env -> maneuver map in device memory, the per-env table and the reduce output"""
+        ev, mans, M = self.ev, self.maneuvers, len(self.maneuvers)
+        steps_of = lambda seconds: int(round(float(seconds) / self.dt))
+        window, hold = max(1, steps_of(_get(ev, "maneuver_window_s", 3.0))), max(1, steps_of(_get(ev, "maneuver_hold_s", 0.3)))
+        thr_lin, thr_ang = float(_get(ev, "maneuver_thr_lin", 0.3)), float(_get(ev, "maneuver_thr_ang", 0.3))
+        if window < hold or not (thr_lin > 0.0 and thr_ang > 0.0):
+            raise ValueError("evaluation: maneuver_window_s (%d steps) must not be shorter than maneuver_hold_s (%d steps), and maneuver_thr_lin = %r, maneuver_thr_ang = %r "
+                             "must be > 0" % (window, hold, thr_lin, thr_ang))
+        specs = (Go2nnManeuverSpec * M)()
+        self.switch_steps = {}
+        for sp, (name, segs) in zip(specs, mans):
+            starts = [steps_of(seg[0]) for seg in segs]
+            if any(b <= a for a, b in zip(starts, starts[1:])):
+                raise ValueError("maneuver %r: the segments' times must increase by at least one step of %.3f s, got %r" % (name, self.dt, [seg[0] for seg in segs]))
+            # the window of the switch at step s ends with the accumulate call of step s + window - 1: inside its segment and inside the horizon
+            for k in range(1, len(starts)):
+                end = starts[k + 1] if k + 1 < len(starts) else self.steps
+                if starts[k] + window > end:
+                    raise ValueError("maneuver %r: the %.2f s window of the switch at %.2f s does not close before %s at %.2f s; shorten evaluation.maneuver_window_s, move the "
+                                     "switch or raise evaluation.seconds" % (name, window * self.dt, segs[k][0], "the next switch" if k + 1 < len(starts) else "the horizon's end",
+                                                                             end * self.dt))
+            sp.count, sp.window, sp.hold, sp.thr_lin, sp.thr_ang = len(segs), window, hold, thr_lin, thr_ang
+            for k, seg in enumerate(segs):
+                sp.start[k] = starts[k]
+                sp.cmd[k][:] = seg[1:4]
+            self.switch_steps[name] = starts[1:]
+        self._check(self.nn.go2nn_maneuver_check_specs(C.cast(specs, C.c_void_p), M), "go2nn_maneuver_check_specs")
+        self.maneuver_window, self.maneuver_hold, self.maneuver_thr = window, hold, (thr_lin, thr_ang)
+        self.mspecs_host = specs
+        self.mspecs = torch.from_numpy(np.frombuffer(bytes(specs), np.uint8).copy()).to(self.device)
+        self.man_host = (self.group_host % M).astype(np.int32)
+        self.man = torch.from_numpy(self.man_host).to(self.device)
+        self.mtable = torch.zeros(GO2NN_MANEUVER_NUM, self.num_envs, device=self.device)
+        self.mout = torch.zeros(self.num_cells, GO2NN_MANEUVER_ACC_NUM + 1, dtype=torch.float64, device=self.device)
+        sizes = np.bincount(self.cell_host, minlength=self.num_cells)
+        if sizes.min() < 4:
+            print("[go2_rl_gym_amd] evaluation: %d of %d (terrain x maneuver) cells have fewer than 4 robots (smallest: %d); raise evaluation.num_envs"
+                  % (int((sizes < 4).sum()), self.num_cells, int(sizes.min())))
 
     def _place_on_levels(self):
         """the ladder's env placement on the current simulator: every env on its cell's row of the terrain grid, in the column the simulator gave it"""
@@ -482,6 +563,18 @@ class PolicyEvaluator:
         a.dist2_thr = self.dist2_thr
         return a
 
+    def _maneuver_in(self):
+        """the maneuver kernels' view of the simulator's buffers (as _eval_in)"""
+        b, a = self.env._buf, Go2nnManeuverIn()
+        for name in MANEUVER_FIELDS:
+            t, f = b[name], getattr(a, name)
+            f.p, f.env_stride, f.comp_stride = t.data_ptr(), t.stride(0), (t.stride(1) if t.dim() > 1 else 0)
+        a.num_specs, a.num_commands = len(self.maneuvers), b["commands"].shape[1]
+        return a
+
+    def _maneuver(self, fn, what, min_):
+        self._check(fn(C.byref(min_), C.c_void_p(self.mspecs.data_ptr()), C.c_void_p(self.man.data_ptr()), C.c_void_p(self.mtable.data_ptr()), self.num_envs, self._stream()), what)
+
     def _eval_in(self):
         """the accumulate kernel's view of the simulator's buffers: (pointer, env stride, component stride) in elements from the torch views' own strides"""
         env, a = self.env, Go2nnEvalIn()
@@ -495,17 +588,24 @@ class PolicyEvaluator:
         return a
 
     # ------------------------------------------------------------------ one env step of the evaluation (pure enqueue)
-    def _step(self, pol, ein, rin=None, k=None, lin=None):
+    def _step(self, pol, ein, rin=None, k=None, lin=None, min_=None):
         """rin: the perturbation kernels' input (None without perturbations);  k: the step's index in an eager run (None inside a capture: no callback there);
-        lin: the ladder kernel's input (None without the ladder)"""
+        lin: the ladder kernel's input (None without the ladder);  min_: the maneuver kernels' input (None without maneuvers)"""
         env = self.env
         actions = pol.act(env.obs_buf)
+        if min_ is not None:
+            self._maneuver(self.nn.go2nn_maneuver_apply, "go2nn_maneuver_apply", min_)
+            if k is not None and self.apply_callback is not None:
+                self.apply_callback(self, k, k >= self.warmup_steps)
         if rin is not None:
             self._robust(self.nn.go2nn_robust_apply, "go2nn_robust_apply", rin)
             if k is not None and self.apply_callback is not None:
                 self.apply_callback(self, k, k >= self.warmup_steps)
         _abi.check(env.lib, env.lib.go2sim_step(env.handle, C.c_void_p(actions.data_ptr()), self._stream()), "go2sim_step")
-        env.commands.copy_(self.commands)          # a robot that fell was reset by the step and drew a new command: the scenario's command holds
+        if min_ is not None:          # (it rewrites the command row itself: the maneuver's command at this step)
+            self._maneuver(self.nn.go2nn_maneuver_accumulate, "go2nn_maneuver_accumulate", min_)
+        else:
+            env.commands.copy_(self.commands)          # a robot that fell was reset by the step and drew a new command: the scenario's command holds
         self._check(self.nn.go2nn_eval_accumulate(C.byref(ein), C.c_void_p(self.acc.data_ptr()), self.num_envs, self._stream()), "go2nn_eval_accumulate")
         if rin is not None:
             self._robust(self.nn.go2nn_robust_accumulate, "go2nn_robust_accumulate", rin)
@@ -520,15 +620,15 @@ class PolicyEvaluator:
         if self.recorder is not None:
             self.recorder.clear()
 
-    def _run_eager(self, pol, ein, rin, lin=None):
+    def _run_eager(self, pol, ein, rin, lin=None, min_=None):
         for k in range(self.warmup_steps + self.steps):
             if k == self.warmup_steps:
                 self._clear()
-            self._step(pol, ein, rin, k, lin)
+            self._step(pol, ein, rin, k, lin, min_)
             if self.step_callback is not None:
                 self.step_callback(self, k, k >= self.warmup_steps)
 
-    def _run_graph(self, pol, ein, rin, lin=None):
+    def _run_graph(self, pol, ein, rin, lin=None, min_=None):
         """capture `chunk` steps on this evaluation's simulator, replay them for the whole horizon -> False if the capture failed (nothing has run then)"""
         from ..rsl_rl.algorithms._graph import no_gc, strict_graphs
         torch.cuda.synchronize(self.device)
@@ -536,7 +636,7 @@ class PolicyEvaluator:
         try:
             with no_gc(), torch.cuda.graph(g):
                 for _ in range(self.chunk):
-                    self._step(pol, ein, rin, lin=lin)
+                    self._step(pol, ein, rin, lin=lin, min_=min_)
         except Exception as e:      # noqa: BLE001
             if strict_graphs():
                 raise RuntimeError("HIP-graph capture of the evaluation failed (%s: %s)" % (type(e).__name__, e)) from e
@@ -556,6 +656,9 @@ class PolicyEvaluator:
         """-> {"overall": {...}, "groups": {terrain: {scenario: {...}}}, "terrain_names", "scenarios", "steps", "dt", "mode"}; every leaf dict has RESULT_KEYS.
         With `evaluation.ladder` also "ladder": {terrain: {level: {scenario: {RESULT_KEYS + LADDER_KEYS}}}}, "ladder_summary": {terrain: {LADDER_SUMMARY_KEYS}}, "levels",
         "ladder_table" (go2nn_ladder_reduce's raw output per cell) and "ladder_distance"; "overall" gains `cleared` and `mean_level_cleared`.
+        With `evaluation.maneuvers` every leaf of "groups" (a "scenario" being a maneuver) and "overall" gain MANEUVER_KEYS; also "maneuvers": {name: {RESULT_KEYS +
+        MANEUVER_KEYS}} over the terrains, "maneuver_table" (go2nn_maneuver_reduce's raw output per cell) "switch_steps": {name: [counted steps]}, "maneuver_schedule": {name: [[step, vx, vy, yaw rate], ...]} and "maneuver_rule" (window and hold in steps, the thresholds).
+        A trace gains "maneuvers", "maneuver_of_robot" and "switch_steps" (int32 [M, 7], padded with -1).
         With `evaluation.record` also "trace": TrajectoryRecorder.fetch() of the counted steps plus "group_of_robot" (index into terrain_names x scenarios, terrain-major,
         per tracked robot), "terrain_names" and "scenarios".
         use_graph: None = eager, or with `evaluation.replay` eager the first time and a captured chunk afterwards (on the GPU); True / False force it."""
@@ -582,11 +685,15 @@ class PolicyEvaluator:
             if self.ladder:          # as above: the table's step counter starts at -warmup_steps, the origin of the distance is taken at step 0 by the kernel itself
                 lin = self._ladder_in()
                 self._check(self.nn.go2nn_ladder_begin(C.c_void_p(self.ltable.data_ptr()), self.num_envs, -self.warmup_steps, self._stream()), "go2nn_ladder_begin")
+            min_ = None
+            if self.maneuvers is not None:          # as above; segment 0 of every maneuver also covers the warm-up, so the kernels run from the first warm-up step on
+                min_ = self._maneuver_in()
+                self._check(self.nn.go2nn_maneuver_begin(C.c_void_p(self.mtable.data_ptr()), self.num_envs, -self.warmup_steps, self._stream()), "go2nn_maneuver_begin")
             replay = bool(_get(self.ev, "replay", False))
             graph = (replay and self.on_device and self.evaluations > 0 and self.step_callback is None) if use_graph is None else bool(use_graph and self.on_device)
-            done = graph and self._run_graph(pol, ein, rin, lin)
+            done = graph and self._run_graph(pol, ein, rin, lin, min_)
             if not done:
-                self._run_eager(pol, ein, rin, lin)
+                self._run_eager(pol, ein, rin, lin, min_)
             self.last_mode = "graph" if done else "eager"
             self._check(self.nn.go2nn_eval_reduce(C.c_void_p(self.acc.data_ptr()), C.c_void_p(self.group.data_ptr()), self.num_envs, self.num_cells,
                                                   C.c_void_p(self.out.data_ptr()), self._stream()), "go2nn_eval_reduce")
@@ -600,17 +707,29 @@ class PolicyEvaluator:
                 self._check(self.nn.go2nn_ladder_reduce(C.c_void_p(self.ltable.data_ptr()), C.c_void_p(self.group.data_ptr()), self.num_envs, self.num_cells, self.dist2_thr,
                                                         C.c_void_p(self.lout.data_ptr()), self._stream()), "go2nn_ladder_reduce")
                 ltable = self.lout.cpu().numpy().copy()
+            mtable = None
+            if min_ is not None:
+                self._check(self.nn.go2nn_maneuver_reduce(C.c_void_p(self.mtable.data_ptr()), C.c_void_p(self.group.data_ptr()), self.num_envs, self.num_cells,
+                                                          C.c_void_p(self.mout.data_ptr()), self._stream()), "go2nn_maneuver_reduce")
+                mtable = self.mout.cpu().numpy().copy()
             table = self.out.cpu().numpy().copy()          # the device -> host copy (and synchronisation) of an evaluation
             trace = self.recorder.fetch() if self.recorder is not None else None
             self._graph = None
             self.evaluations += 1
-        res = self._results(table, rtable, ltable)
+        res = self._results(table, rtable, ltable, mtable)
         if trace is not None:
             trace.update(group_of_robot=self.group_host[trace["env_ids"]].copy(), terrain_names=list(self.terrain_names), scenarios=[s[0] for s in self.scenarios])
             if self.ladder:
                 trace.update(levels=list(self.levels), level_of_robot=self.level_of_env[trace["env_ids"]].copy())
             if self.perturbations is not None:          # push_steps: the counted steps (= frame indices) whose go2nn_robust_apply pushed; the frame holds the state AFTER that step
                 trace.update(perturbations=[p[0] for p in self.perturbations], pert_of_robot=self.pert_host[trace["env_ids"]].copy(), push_steps=self.push_steps.copy())
+            if self.maneuvers is not None:
+                # switch_steps [M, GO2NN_MANEUVER_MAX_SEGS - 1] int32: per maneuver the counted steps (= frame indices) at which a new segment begins — that frame carries the
+                # new command —, padded with -1 (a rectangular array: maneuvers differ in their number of switches, and the trace goes to an .npz)
+                steps = np.full((len(self.maneuvers), GO2NN_MANEUVER_MAX_SEGS - 1), -1, np.int32)
+                for mi, m in enumerate(self.maneuvers):
+                    steps[mi, :len(self.switch_steps[m[0]])] = self.switch_steps[m[0]]
+                trace.update(maneuvers=[m[0] for m in self.maneuvers], maneuver_of_robot=self.man_host[trace["env_ids"]].copy(), switch_steps=steps)
             res["trace"] = trace
         return res
 
@@ -630,6 +749,14 @@ class PolicyEvaluator:
         per_push = lambda x: float(x) / pushes if pushes > 0 else float("nan")
         return {"pushes": int(pushes), "push_falls": per_push(r[1]), "recovered": per_push(r[2]), "recovery_time_s": float(r[3]) / rec * self.dt if rec > 0 else float("nan"),
                 "peak_lin_vel_err": per_push(r[4]), "peak_tilt": per_push(r[5])}
+
+    def _maneuver_row(self, r):
+        """one row of go2nn_maneuver_reduce (MANEUVER_OUT) -> the per-switch figures; NaN without a switch, without a settled switch (settle_time_s), without a window step"""
+        v = {k: float(r[i]) for i, k in enumerate(MANEUVER_OUT)}
+        sw, settled, steps = v["switches"], v["settled"], v["win_steps"]
+        per = lambda x, n: x / n if n > 0 else float("nan")
+        return {"switches": int(sw), "switch_falls": per(v["switch_falls"], sw), "settled": per(settled, sw), "settle_time_s": per(v["settle_steps"], settled) * self.dt,
+                "window_lin_vel_err": per(v["win_lin_err"], steps), "window_ang_vel_err": per(v["win_ang_err"], steps), "peak_tilt": per(v["peak_tilt_sum"], sw)}
 
     def _ladder_row(self, r):
         """one row of go2nn_ladder_reduce (LADDER_OUT) -> the cell's shares; an empty cell reports NaN, and so does time_to_clear_s without a cleared robot"""
@@ -660,9 +787,10 @@ class PolicyEvaluator:
         res["overall"].update(cleared=self._ladder_row(whole)["cleared"], mean_level_cleared=float(np.mean([v["mean_level_cleared"] for v in summary.values()])))
         res.update(levels=list(self.levels), ladder_table=lcells, ladder_cell_table=cells, ladder_distance=self.ladder_distance, ladder_pass_share=self.ladder_pass_share)
 
-    def _results(self, cells, rcells=None, lcells=None):
+    def _results(self, cells, rcells=None, lcells=None, mcells=None):
         """cells: the eval reduce table per (terrain, scenario, perturbation) cell; rcells: the robust one (None without perturbations: a cell is a group then);
-        lcells: the ladder's (None without the ladder), cells being per (terrain, level, scenario) then"""
+        lcells: the ladder's (None without the ladder), cells being per (terrain, level, scenario) then;  mcells: the maneuvers' (None without maneuvers), per
+        (terrain, maneuver) cell = group"""
         S, P = len(self.scenarios), len(self.perturbations or [None])
         if lcells is not None:
             table = cells.reshape(len(self.terrain_names), len(self.levels), S, -1).sum(1).reshape(len(self.groups), -1)
@@ -683,6 +811,18 @@ class PolicyEvaluator:
                        push={"first": self.push_first, "period": self.push_period, "window": self.push_window, "hold": self.push_hold, "count": self.push_count})
         if lcells is not None:
             self._ladder_results(res, cells, lcells)
+        if mcells is not None:
+            T, M = len(self.terrain_names), len(self.maneuvers)
+            names = [m[0] for m in self.maneuvers]
+            for ti, t in enumerate(self.terrain_names):
+                for mi, n in enumerate(names):
+                    groups[t][n].update(self._maneuver_row(mcells[ti * M + mi]))
+            c3, m3 = table.reshape(T, M, -1), mcells.reshape(T, M, -1)
+            res["maneuvers"] = {n: dict(self._row(c3[:, mi].sum(0)), **self._maneuver_row(m3[:, mi].sum(0))) for mi, n in enumerate(names)}
+            res["overall"].update(self._maneuver_row(mcells.sum(0)))
+            res.update(maneuver_table=mcells, switch_steps={n: list(self.switch_steps[n]) for n in names},
+                       maneuver_rule={"window": self.maneuver_window, "hold": self.maneuver_hold, "thr_lin": self.maneuver_thr[0], "thr_ang": self.maneuver_thr[1]},
+                       maneuver_schedule={n: [[int(s)] + [float(x) for x in seg[1:4]] for s, seg in zip([0] + list(self.switch_steps[n]), segs)] for n, segs in self.maneuvers})
         return res
 
     def close(self):
@@ -693,14 +833,16 @@ class PolicyEvaluator:
 
 # ---------------------------------------------------------------------------------------------------------------------------------------------------------------
 def scalars(res):
-    """[(tag, value)]: 'Eval/<metric>' for the overall figures, 'Eval/<terrain>/<scenario>/<metric>' per group, with perturbations 'Eval/robust/<name>/<metric>' and, with
-    the ladder, 'Eval/ladder/<terrain>/{level_cleared,mean_level_cleared}' and 'Eval/ladder/mean_level_cleared'"""
+    """[(tag, value)]: 'Eval/<metric>' for the overall figures, 'Eval/<terrain>/<scenario>/<metric>' per group, with perturbations 'Eval/robust/<name>/<metric>', with
+    maneuvers 'Eval/maneuver/<name>/<metric>' and, with the ladder, 'Eval/ladder/<terrain>/{level_cleared,mean_level_cleared}' and 'Eval/ladder/mean_level_cleared'"""
     out = [("Eval/" + k, res["overall"][k]) for k in RESULT_KEYS]
     for t, per in res["groups"].items():
         for s, d in per.items():
             out += [("Eval/%s/%s/%s" % (t, s, k), d[k]) for k in RESULT_KEYS]
     for n, d in (res.get("perturbations") or {}).items():
         out += [("Eval/robust/%s/%s" % (n, k), d[k]) for k in RESULT_KEYS + ROBUST_KEYS]
+    for n, d in (res.get("maneuvers") or {}).items():
+        out += [("Eval/maneuver/%s/%s" % (n, k), d[k]) for k in RESULT_KEYS + MANEUVER_KEYS]
     if res.get("ladder_summary") is not None:
         for t, d in res["ladder_summary"].items():
             out += [("Eval/ladder/%s/%s" % (t, k), d[k]) for k in LADDER_SUMMARY_KEYS]
@@ -714,6 +856,10 @@ def results_dict(res, it=None):
     if res.get("perturbations") is not None:
         d["perturbations"] = {n: dict(v) for n, v in res["perturbations"].items()}
         d["push"] = dict(res["push"])
+    if res.get("maneuvers") is not None:          # per maneuver over the terrains, the settling rule and the schedule [counted step, vx, vy, yaw rate] per segment
+        d["maneuvers"] = {n: dict(v) for n, v in res["maneuvers"].items()}
+        d["maneuver_rule"] = dict(res["maneuver_rule"])
+        d["maneuver_schedule"] = {n: [list(seg) for seg in segs] for n, segs in res["maneuver_schedule"].items()}
     if res.get("ladder") is not None:          # the full curve, and what it comes to per terrain kind
         d["ladder"] = {t: {int(lv): {s: dict(v) for s, v in per.items()} for lv, per in levels.items()} for t, levels in res["ladder"].items()}
         d["ladder_summary"] = {t: dict(v) for t, v in res["ladder_summary"].items()}
@@ -741,6 +887,12 @@ def format_table(res):
             lines.append("%-16s %-14s " % (t, first) + " ".join("%6.2f" % levels[lv][first]["cleared"] for lv in res["levels"])
                          + " %14d %19.3f" % (sm["level_cleared"], sm["mean_level_cleared"]))
         lines.append("%-16s %-14s " % ("all", first) + " ".join("%6s" % "" for _ in res["levels"]) + " %14s %19.3f" % ("", res["overall"]["mean_level_cleared"]))
+    if res.get("maneuvers") is not None:          # the fourth block: one line per maneuver, over every terrain
+        cols = ("lin_vel_err", "ang_vel_err", "falls", "survival") + MANEUVER_KEYS + ("n_envs",)
+        whole = ("switches", "n_envs")
+        lines += ["", "%-20s " % "maneuver" + " ".join("%18s" % c for c in cols)]
+        for n, d in list(res["maneuvers"].items()) + [("all", res["overall"])]:
+            lines.append("%-20s " % n + " ".join("%18d" % d[c] if c in whole else "%18.4f" % d[c] for c in cols))
     return "\n".join(lines)
 
 

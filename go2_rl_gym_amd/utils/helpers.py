@@ -93,7 +93,7 @@ _RUNNER_OVERRIDES = ("max_iterations", "experiment_name", "run_name", "load_run"
 def update_cfg_from_args(env_cfg, cfg_train, args):
     """Command-line overrides onto the config objects (legged_gym/utils/helpers.py update_cfg_from_args): --num_envs onto the env config;
     --seed, --resume and the runner fields above onto the train config; the RoboGauge switches when the train config has that section (parsed and ignored: the service is
-    out of scope), and next to them --evaluate / --eval_interval / --record / --robust / --ladder onto the `evaluation` section."""
+    out of scope), and next to them --evaluate / --eval_interval / --record / --robust / --ladder / --maneuvers onto the `evaluation` section."""
     if env_cfg is not None and args.num_envs is not None:
         env_cfg.env.num_envs = args.num_envs
     if cfg_train is None:
@@ -125,6 +125,9 @@ def update_cfg_from_args(env_cfg, cfg_train, args):
             ev.perturbations = [[n, dict(f)] for n, f in DEFAULT_PERTURBATIONS]
         if getattr(args, "ladder", False):
             ev.ladder = True
+        if getattr(args, "maneuvers", False):
+            from .evaluator import DEFAULT_MANEUVERS
+            ev.maneuvers = [[n, [list(seg) for seg in segs]] for n, segs in DEFAULT_MANEUVERS]
     return env_cfg, cfg_train
 
 
@@ -151,6 +154,8 @@ def get_args(argv=None):
                    "evaluation.perturbations = utils/evaluator.py DEFAULT_PERTURBATIONS")
     p.add_argument("--ladder", action="store_true", default=False, help="evaluate on every terrain level and report the difficulty the policy gets through "
                    "(terrain tasks): evaluation.ladder = True")
+    p.add_argument("--maneuvers", action="store_true", default=False, help="evaluate scripted command changes (start, brake, reverse, turn) instead of commands that hold: "
+                   "evaluation.maneuvers = utils/evaluator.py DEFAULT_MANEUVERS")
     p.add_argument("--record_steps", type=int, default=500, help="play.py --record: the last S steps of the rollout are kept")
     # flags contributed by isaacgym.gymutil.parse_arguments in the reference
     p.add_argument("--sim_device", type=str, default="cuda:0")

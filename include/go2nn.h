@@ -458,6 +458,72 @@ int go2nn_ladder_accumulate(const Go2nnLadderIn* in, float* table, int32_t N, vo
 /* GO2NN_EINVAL for null pointers, N < 1, G outside 1 .. 65535, dist2_thr <= 0 (or NaN). */
 int go2nn_ladder_reduce(const float* table, const int32_t* group, int32_t N, int32_t G, float dist2_thr, double* out, void* stream);
 
+/* ---- the evaluator's scripted command maneuvers: start, brake, reverse, turn — and how the robot answers (go2_rl_gym_amd/utils/evaluator.py, `evaluation.maneuvers`).
+ * ADDED WITHIN ABI 7: five new entry points, nothing existing changes, GO2NN_ABI_VERSION stays 7.
+ * A maneuver evaluation step is { policy, go2nn_maneuver_apply, go2sim_step, go2nn_maneuver_accumulate, go2nn_eval_accumulate }: two more plain launches per step
+ * (capturable; one lane per env, no atomics), and one go2nn_maneuver_reduce at the end.  Every env e belongs to one maneuver man_of_env[e] in [0, M), M <= 64; an env with
+ * man_of_env[e] outside [0, M) is left alone (only its step counter runs).
+ * A maneuver is one Go2nnManeuverSpec (an array of M of them in the buffers' memory space):
+ *   count                  1 .. GO2NN_MANEUVER_MAX_SEGS segments
+ *   start[k], cmd[k][3]    segment k begins at counted step start[k] (start[0] = 0, strictly increasing) and commands (vx, vy, yaw rate)
+ *   window W, hold H       the settling rule (below), in steps;  thr_lin [m/s], thr_ang [rad/s] its thresholds
+ * The command in force at step s is a pure function c_m(s): that of the segment with the largest start <= max(s, 0) — segment 0 also covers the warm-up.  A SWITCH is the
+ * start of a segment k >= 1.
+ * THE CONVENTION: the switch at counted step s takes effect in the go2nn_maneuver_apply BEFORE that step's go2sim_step.  The step's physics runs on an action chosen from an
+ * observation that still carries the old command; the observation it produces, and the metrics of step s, carry the new one.  This is the simulator's own resampling order
+ * (_post_physics_step_callback runs before the rewards and the observations).
+ * The table: fp32 [GO2NN_MANEUVER_NUM, N], row-major by row of the enum below, column e = env e.
+ * go2nn_maneuver_begin: table = 0, then STEP[e] = start for every e (the evaluator passes -warmup_steps).
+ * go2nn_maneuver_apply (BEFORE go2sim_step), per env with a maneuver: commands[e, 0:3] = c_m(STEP[e]), commands[e, 3:num_commands] = 0.  Nothing else is written (the table
+ *   is const here); calling it twice is calling it once.
+ * go2nn_maneuver_accumulate (AFTER the step, before go2nn_eval_accumulate), per env with a maneuver, with s = STEP[e], in this order:
+ *   1. commands[e] = c_m(s) as above (a robot that fell was reset inside the step and drew a command: go2nn_eval_accumulate and the recorder see the maneuver's);
+ *   2. s == start[k] for a k >= 1:  OPEN = 1, OK_RUN = IS_SETTLED = IS_FELL = PEAK_TILT = 0, SWITCHES += 1;
+ *   3. OPEN > 0 (a window is open, this being its OPEN-th step):  err_lin = |cmd_xy - v_xy|_2, err_ang = |cmd_yaw - w_z|, tilt = |g_xy|_2 (as LIN_VEL_ERR, ANG_VEL_ERR and
+ *      TILT above), fall = reset_buf and not time_out_buf.  The flags come first: on a reset the buffers already hold the post-reset state.
+ *        not IS_FELL and fall:     SWITCH_FALLS += 1, IS_FELL = 1
+ *        not IS_FELL and no fall:  WIN_STEPS += 1, WIN_LIN_ERR += err_lin, WIN_ANG_ERR += err_ang, PEAK_TILT = max(PEAK_TILT, tilt);
+ *                                  not IS_SETTLED and err_lin < thr_lin and err_ang < thr_ang:  OK_RUN += 1; at OK_RUN == H:  SETTLED += 1, SETTLE_STEPS += OPEN, IS_SETTLED = 1
+ *                                  not IS_SETTLED otherwise:                                    OK_RUN = 0
+ *        OPEN == W:  PEAK_TILT_SUM += PEAK_TILT, OPEN = 0 (closed);  otherwise OPEN += 1
+ *   4. STEP = s + 1 (every env) — the step counter lives in the table, so a captured launch advances on every replay.
+ * The scores are per SWITCH: SETTLE_STEPS counts from the switch to the END of the hold; a robot that falls after its window has closed, or outside any window, counts
+ * in the evaluator's FALLS only; a robot that settles and falls later inside the same window counts in SETTLED and in SWITCH_FALLS. */
+enum {
+  GO2NN_MANEUVER_STEP = 0, GO2NN_MANEUVER_OPEN, GO2NN_MANEUVER_OK_RUN, GO2NN_MANEUVER_IS_SETTLED, GO2NN_MANEUVER_IS_FELL, GO2NN_MANEUVER_PEAK_TILT,
+  GO2NN_MANEUVER_SWITCHES, GO2NN_MANEUVER_SWITCH_FALLS, GO2NN_MANEUVER_SETTLED, GO2NN_MANEUVER_SETTLE_STEPS, GO2NN_MANEUVER_WIN_STEPS, GO2NN_MANEUVER_WIN_LIN_ERR,
+  GO2NN_MANEUVER_WIN_ANG_ERR, GO2NN_MANEUVER_PEAK_TILT_SUM, GO2NN_MANEUVER_NUM
+};
+#define GO2NN_MANEUVER_ACC_FIRST GO2NN_MANEUVER_SWITCHES                    /* rows below it are per-env state, rows from it on are accumulators */
+#define GO2NN_MANEUVER_ACC_NUM (GO2NN_MANEUVER_NUM - GO2NN_MANEUVER_ACC_FIRST)
+#define GO2NN_MANEUVER_MAX_SPECS 64
+#define GO2NN_MANEUVER_MAX_SEGS 8
+typedef struct Go2nnManeuverSpec {
+  int32_t count;
+  int32_t window, hold;
+  float thr_lin, thr_ang;
+  int32_t start[GO2NN_MANEUVER_MAX_SEGS];
+  float cmd[GO2NN_MANEUVER_MAX_SEGS][3];
+} Go2nnManeuverSpec;
+/* The buffers as (pointer, env stride, component stride) in ELEMENTS like Go2nnEvalIn's.  commands [N, num_commands] (WRITTEN by both calls; num_commands >= 3),
+ * base_lin_vel, base_ang_vel, projected_gravity [N,3]; reset_buf / time_out_buf uint8 (comp_stride unused, may be 0).  num_specs = M. */
+typedef struct Go2nnManeuverIn {
+  Go2nnEvalField commands, base_lin_vel, base_ang_vel, projected_gravity, reset_buf, time_out_buf;
+  int32_t num_specs;
+  int32_t num_commands;
+} Go2nnManeuverIn;
+/* Host-side check of M specs in HOST memory, before they are copied to the buffers' memory space (the launches cannot read them back): GO2NN_EINVAL with a message for
+ * M outside [1, 64], a null pointer, count outside [1, 8], start[0] != 0, starts not strictly increasing, hold < 1, window < hold, a window longer than the gap between
+ * two switches (windows never overlap), a threshold <= 0 (or NaN). */
+int go2nn_maneuver_check_specs(const Go2nnManeuverSpec* host_specs, int32_t M);
+int go2nn_maneuver_begin(float* table, int32_t N, int32_t start, void* stream);
+/* GO2NN_EINVAL for null pointers, N < 1, num_specs outside [1, 64], num_commands < 3, an env stride < 1 or (vector fields) a component stride < 1. */
+int go2nn_maneuver_apply(const Go2nnManeuverIn* in, const Go2nnManeuverSpec* specs, const int32_t* man_of_env, const float* table, int32_t N, void* stream);
+int go2nn_maneuver_accumulate(const Go2nnManeuverIn* in, const Go2nnManeuverSpec* specs, const int32_t* man_of_env, float* table, int32_t N, void* stream);
+/* out [G, GO2NN_MANEUVER_ACC_NUM + 1] (fp64): per group the sums of the accumulator rows over its envs, then the number of its envs — the summation scheme (and the device
+ * function) of go2nn_eval_reduce: fixed order, bit-equal outputs for equal inputs, group ids outside [0, G) ignored, an empty group gives zeros.  1 <= G <= 65535. */
+int go2nn_maneuver_reduce(const float* table, const int32_t* group, int32_t N, int32_t G, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,6 +1,6 @@
 """What one policy evaluation costs (utils/evaluator.py), and what the metric kernel saves over torch expressions.
 
-    python tools/eval_bench.py [--task go2_flat] [--reps 3] [--robust] [--ladder] [--out profiles/eval_bench.json]
+    python tools/eval_bench.py [--task go2_flat] [--reps 3] [--robust] [--ladder] [--maneuvers] [--out profiles/eval_bench.json]
 
 Measures, on cuda:0, with the task's default `evaluation` section (1024 robots, 1 s + 10 s):
   * wall time of evaluate() run eagerly and with the captured chunk of steps replayed (simulator re-creation, capture and the final host copy included: it is what
@@ -11,6 +11,8 @@ Measures, on cuda:0, with the task's default `evaluation` section (1024 robots, 
 --robust: the same with the default perturbations on (evaluation.perturbations = DEFAULT_PERTURBATIONS), plus go2nn_robust_apply + go2nn_robust_accumulate per pair of
 back-to-back launches; the torch-expression comparison is left out.
 --ladder (a terrain task, e.g. --task go2): the same with evaluation.ladder on, plus go2nn_ladder_accumulate per back-to-back launch; again without the torch expressions.
+--maneuvers: the same with the default maneuvers in the scenarios' place (evaluation.maneuvers = DEFAULT_MANEUVERS), plus go2nn_maneuver_apply + go2nn_maneuver_accumulate per
+pair of back-to-back launches; again without the torch expressions.
 Writes one JSON file and prints it."""
 import argparse
 import ctypes as C
@@ -26,7 +28,7 @@ sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 
 from go2_rl_gym_amd.envs import task_registry  # noqa: E402
-from go2_rl_gym_amd.utils.evaluator import DEFAULT_PERTURBATIONS, EVAL_SOURCE, PolicyEvaluator  # noqa: E402
+from go2_rl_gym_amd.utils.evaluator import DEFAULT_MANEUVERS, DEFAULT_PERTURBATIONS, EVAL_SOURCE, PolicyEvaluator  # noqa: E402
 from go2_rl_gym_amd.utils.helpers import class_to_dict  # noqa: E402
 
 
@@ -66,6 +68,7 @@ def main():
     p.add_argument("--kernel_only", action="store_true")
     p.add_argument("--robust", action="store_true")
     p.add_argument("--ladder", action="store_true")
+    p.add_argument("--maneuvers", action="store_true")
     p.add_argument("--out", default=os.path.join(ROOT, "profiles", "eval_bench.json"))
     a = p.parse_args()
     env_cfg, train_cfg = task_registry.get_cfgs(a.task)
@@ -74,12 +77,15 @@ def main():
         ev_cfg["perturbations"] = [[n, dict(f)] for n, f in DEFAULT_PERTURBATIONS]
     if a.ladder:
         ev_cfg["ladder"] = True
+    if a.maneuvers:
+        ev_cfg["maneuvers"] = [[n, [list(seg) for seg in segs]] for n, segs in DEFAULT_MANEUVERS]
     ev = PolicyEvaluator(env_cfg, ev_cfg, task_class=task_registry.get_task_class(a.task), device="cuda:0")
     from go2_rl_gym_amd.rsl_rl.modules import ActorCritic
     torch.manual_seed(0)
     ac = ActorCritic(45, 263, 12, **{k: v for k, v in class_to_dict(train_cfg.policy).items() if k in ("actor_hidden_dims", "critic_hidden_dims", "activation", "init_noise_std")}).to("cuda:0")
     out = {"task": a.task, "device": torch.cuda.get_device_name(0), "num_envs": ev.num_envs, "steps": ev.warmup_steps + ev.steps, "chunk": ev.chunk,
-           "perturbations": [n for n, _ in ev.perturbations] if ev.perturbations else None, "ladder_levels": list(ev.levels) if ev.ladder else None}
+           "perturbations": [n for n, _ in ev.perturbations] if ev.perturbations else None, "ladder_levels": list(ev.levels) if ev.ladder else None,
+           "maneuvers": [m[0] for m in ev.maneuvers] if ev.maneuvers else None}
     ev.evaluate(ac, use_graph=False)
     ein, st = ev._eval_in(), ev._stream()
     acc_fn = lambda: ev.nn.go2nn_eval_accumulate(C.byref(ein), C.c_void_p(ev.acc.data_ptr()), ev.num_envs, st)
@@ -101,6 +107,15 @@ def main():
         timed(lad_fn, 20)
         dev_us, wall_us = timed(lad_fn, 200)
         out["ladder_accumulate_kernel"] = {"device_us_per_launch_back_to_back": dev_us, "host_us_per_call": wall_us}
+    if a.maneuvers:
+        min_ = ev._maneuver_in()
+
+        def man_pair():
+            ev._maneuver(ev.nn.go2nn_maneuver_apply, "go2nn_maneuver_apply", min_)
+            ev._maneuver(ev.nn.go2nn_maneuver_accumulate, "go2nn_maneuver_accumulate", min_)
+        timed(man_pair, 20)
+        dev_us, wall_us = timed(man_pair, 200)
+        out["maneuver_apply_plus_accumulate"] = {"device_us_per_pair_back_to_back": dev_us, "host_us_per_pair": wall_us}
     if not a.kernel_only:
         walls = {"eager": [], "replayed": []}
         for _ in range(a.reps):
@@ -111,7 +126,7 @@ def main():
                 walls[mode].append((time.perf_counter() - t0) * 1e3)
                 assert res["mode"] == ("graph" if g else "eager")
         out["evaluate_wall_ms"] = {m: {"best": min(w), "median": statistics.median(w)} for m, w in walls.items()}
-    if not a.kernel_only and not a.robust and not a.ladder:
+    if not a.kernel_only and not a.robust and not a.ladder and not a.maneuvers:
         b, lim, acc = ev.env._buf, ev.dof_limits, torch.zeros_like(ev.acc)
         tm = lambda: torch_metrics(b, lim, acc)
         timed(tm, 5)
