@@ -53,6 +53,20 @@ def test_cts_policy_kernel_on_gpu(kind, N, full):
     cts_policy_kernel_vs_modules(_nn.load_nn(), "cuda:0", kind, N, full, atol=6e-6)          # (hipBLASLt sums in another order: a few ulp of the activations' scale, as above)
 
 
+from test_policy_kernel import cts_rollout_latent_vs_float64  # noqa: E402
+
+
+@pytest.mark.parametrize("N,full", [(5, False), (203, False), (1000, True)])
+@pytest.mark.parametrize("kind", ["MoECTS", "MoENGCTS"])
+def test_cts_rollout_latent_on_gpu(kind, N, full):
+    """CTS.act / CTS._rollout_latent of the MoE students on the MI355X, through the algorithm (not a hand-built PolicyKernelCTS), against float64: the go2nn_moe_mix_forward
+    arm (MoECTS) and the torch-modules arm (MoENGCTS: split weight images of the no-goal encoder, GroupedHeads' padded narrow batched product, index_copy_ into the latent
+    buffer).  N = 5 / 203 with every 4th env a student: a ragged last workgroup, 2 : 3 and 51 : 152 rows; N = 1000 at the tasks' widths and expert count.  Also: the
+    latent follows student weights changed in place once parameters_changed() was called (a stale image in _img_cache would show), and is bit-reproducible."""
+    from helpers import load_hip
+    assert cts_rollout_latent_vs_float64(load_hip(), _nn.load_nn(), "cuda:0", kind, N, full)
+
+
 @pytest.mark.parametrize("dims,kernel", [((45, 512, 256, 128, 12), "planes"), ((263, 512, 256, 128, 1), "planes"), ((77, 100, 50, 7), "planes"), ((17, 33), "planes"),
                                          ((300, 512, 512, 12), "fp32"), ((512, 512), "fp32")])
 def test_split_operand_policy_kernel_is_as_close_to_float64_as_fp32(dims, kernel):

@@ -131,10 +131,15 @@ class DeviceScriptedEnv(tc.ScriptedEnv):
 
 
 @pytest.mark.parametrize("mode", ["eager", "graphs"])
-@pytest.mark.parametrize("kind,fixture", [("CTS", "cts_iteration.npz"), ("MoECTS", "moe_cts_iteration.npz")])
+@pytest.mark.parametrize("kind,fixture", [("CTS", "cts_iteration.npz"), ("MoECTS", "moe_cts_iteration.npz"), ("MoENGCTS", "moe_ng_cts_iteration.npz"),
+                                          ("ACMoECTS", "ac_moe_cts_iteration.npz"), ("DualMoECTS", "dual_moe_cts_iteration.npz"),
+                                          ("MCPCTS", "mcp_cts_iteration.npz")])
 def test_cts_iteration_golden_on_gpu(kind, fixture, mode, monkeypatch):
     """One full OnPolicyRunnerCTS iteration of the reference (rollout with the history ring, GAE, 2 x 2 policy steps, 2 x 2 student steps)
-    through the GPU product path."""
+    through the GPU product path, for all six algorithms of the family (the host twin: tests/test_cts_golden.py).  Which formulation each
+    kind takes on the device is asserted, so that a silent fall-back cannot pass: CTS / MoE-CTS / MoE-NG-CTS the no-autograd mini-batch
+    (modules/fused_cts.py) and the policy kernel, AC-MoE / Dual-MoE / MCP the autograd formulation (graph mode: one CapturedStep per
+    mini-batch slot), MCP-CTS — a state-dependent std — off the fused loss / rollout heads."""
     import torch
     from go2_rl_gym_amd.rsl_rl.modules import ActorCriticCTS, fused
     from go2_rl_gym_amd.rsl_rl.runners import OnPolicyRunnerCTS
@@ -145,7 +150,14 @@ def test_cts_iteration_golden_on_gpu(kind, fixture, mode, monkeypatch):
     runner = OnPolicyRunnerCTS(env, tc._train_cfg(kind, T), log_dir=None, device=DEV, use_graphs=(mode == "graphs"))
     alg, model = runner.alg, runner.alg.model
     env.alg = alg
-    assert runner.use_graphs == alg.use_graphs == (mode == "graphs") and alg.fused_loss and alg.fused_rollout
+    assert runner.use_graphs == alg.use_graphs == (mode == "graphs") and fused._LIB is hip
+    if kind == "MCPCTS":        # CTS.__init__: one std per action dimension is what the fused heads assume; the model has no `std` parameter at all
+        assert model.state_dependent_std and alg.fused_loss is False and alg.fused_rollout is False and not hasattr(model, "std")
+    else:
+        assert alg.fused_loss and alg.fused_rollout
+    own = kind in ("CTS", "MoECTS", "MoENGCTS")
+    assert (alg._own_plan() is not None) == own and alg._own_student() == (kind == "CTS")
+    assert (alg._policy_kernel() is not None) == own
     np.testing.assert_array_equal(alg.teacher_env_idxs.cpu().numpy(), g["teacher_env_idxs"])
     sd0 = {k[3:]: torch.as_tensor(v, device=DEV) for k, v in g.items() if k.startswith("w0_")}
     model.load_state_dict(sd0)
@@ -164,12 +176,16 @@ def test_cts_iteration_golden_on_gpu(kind, fixture, mode, monkeypatch):
 
     alg.update = update
     if mode == "graphs":
-        for _ in range(3):          # rollout: 2 eager + capture; update slots: captured at their 4th / 2nd call
+        # rollout: 2 eager + capture.  Update, own plan: each phase is one CapturedStep with warmup 1 (captured in the 2nd update).  Update, no plan (AC-MoE, Dual-MoE,
+        # MCP): one CapturedStep per mini-batch slot, warmup 3 for slot 0 and 1 for slot 1, called once per epoch (2 per update): slot 0 is captured at its 4th call
+        # (2nd update, 2nd epoch), slot 1 at its 2nd (1st update, 2nd epoch).  Three iterations cover both.
+        for _ in range(3):
             runner.history.zero_()
             runner.learn(1, init_at_random_ep_len=False)
         torch.cuda.synchronize()
         assert runner._rollout_graph is not None, "HIP-graph capture of the rollout degraded to eager"
         assert all(s.graph is not None for grp in alg._steps for s in grp), "HIP-graph capture of a CTS update step degraded to eager"
+        assert alg.graphs_captured() and len(alg._steps[0]) == len(alg._steps[1]) == (1 if own else 2)
         model.load_state_dict(sd0)
         _reset_adam(alg.optimizer1); _reset_adam(alg.optimizer2)
         alg.learning_rate = 1e-3

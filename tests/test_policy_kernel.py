@@ -169,6 +169,131 @@ def test_cts_policy_kernel_matches_modules(kind, N, full):
     cts_policy_kernel_vs_modules(load_nn_emu(), "cpu", kind, N, full)
 
 
+NO_GOAL_MASK = [True] * 6 + [False] * 3 + [True] * 36          # the observation without its three command entries (envs/go2/go2_config.py)
+
+
+def cts_rollout_latent_vs_float64(sim_lib, nn_lib, device, kind="MoECTS", N=203, full=False):
+    """CTS.act / CTS._rollout_latent of the two MoE students AT ALGORITHM LEVEL (which arm the algorithm picks, which buffers it hands over, when it rebuilds the split
+    weight images) against the same model copied to float64: teacher rows of the env-ordered latent = teacher_encoder(priv[ti]) (its last module is the L2 normaliser),
+    student rows = student_latent(hist[si])[0]; mu / values / actions = policy_mean / evaluate_joint / mu + std * eps on that latent.
+      MoECTS   -> the soft mixture's tail as ONE launch (go2nn_moe_mix_forward) behind the experts / gate as torch modules under own_forward;
+      MoENGCTS -> PolicyKernelCTS.moe_mix_ok is false (it asks for ActorCriticMoECTS.student_moe_parts): model.student_latent as torch modules under own_forward
+                  (split images of the no-goal encoder, GroupedHeads' padded narrow batched product on cuda) + index_copy_ into the latent buffer.
+    Bound — the project's rule for device arithmetic against float64 (tests/test_gpu_recurrent.py, test_split_operand_policy_kernel_is_as_close_to_float64_as_fp32): the error
+    is at most 4 x the error of the same modules evaluated by torch in fp32 on the same device, + 2e-7; errors in units of max(1, largest |float64 value|) of the tensor
+    (fp32 rounding is relative: the 2e-7 floor is ~2 ulp of the tensor's scale; the latent is normalised, |.| <= 1, and taken absolutely).
+    -> [(what, error, fp32 torch error)] of every comparison made"""
+    import copy
+    from go2_rl_gym_amd.rsl_rl.algorithms import MoECTS, MoENGCTS
+    from go2_rl_gym_amd.rsl_rl.modules import ActorCriticCTS, ActorCriticMoECTS, ActorCriticMoENGCTS, fused
+    torch.manual_seed(7)
+    E = 8 if full else 4          # (full: the widths and the expert count of go2_moe_cts / go2_moe_ng_cts)
+    dims = (dict(actor_hidden_dims=[512, 256, 128], critic_hidden_dims=[512, 256, 128], teacher_encoder_hidden_dims=[512, 256], student_encoder_hidden_dims=[512, 256], latent_dim=32) if full else
+            dict(actor_hidden_dims=[40, 24], critic_hidden_dims=[40, 24], teacher_encoder_hidden_dims=[48, 20], student_encoder_hidden_dims=[36, 28], latent_dim=8))
+    if kind == "MoECTS":
+        dims.update(student_encoder_hidden_dims=dims["student_encoder_hidden_dims"] + [256 if full else 16], expert_num=E)
+    else:
+        dims.update(student_expert_num=E, obs_no_goal_mask=NO_GOAL_MASK)
+    n_priv, T = (263 if full else 61), 2
+    model = (ActorCriticMoECTS if kind == "MoECTS" else ActorCriticMoENGCTS)(45, n_priv, 12, N, 5, init_noise_std=1.0, **dims).to(device)
+    with torch.no_grad():
+        model.std.copy_(torch.rand(12) * 0.8 + 0.3)
+    g = torch.Generator().manual_seed(2)
+    r = lambda *s: torch.randn(*s, generator=g).to(device)
+    obs, priv, hist, eps = r(N, 45), r(N, n_priv) * 2, r(N, 225), r(N, 12)
+    ids = torch.arange(N, device=device)
+    ti, si = ids[ids % 4 != 0], ids[ids % 4 == 0]          # (what CTS.__init__ must arrive at for teacher_env_ratio 0.75: computed here on its own)
+
+    def modules(dt):
+        """-> latent, mu, values, actions of the CURRENT parameters, by the modules in dtype dt (plain torch: no gradient and outside own_forward, FusedSequential runs as nn.Sequential)"""
+        m = copy.deepcopy(model).to(dt)
+        o, p, h = obs.to(dt), priv.to(dt), hist.to(dt)
+        with torch.no_grad():
+            lat = torch.empty(N, dims["latent_dim"], device=device, dtype=dt)
+            lat[ti] = m.teacher_encoder(p[ti]); lat[si] = m.student_latent(h[si])[0]
+            mu, v = m.policy_mean(lat, o), m.evaluate_joint(p, lat, o).view(-1)
+            return {"latent": lat.double(), "mu": mu.double(), "values": v.double(), "actions": (mu + m.std * eps.to(dt)).double()}
+
+    report = []
+
+    def check(tag, got):
+        r64, r32 = modules(torch.float64), modules(torch.float32)
+        for k in ("latent", "mu", "values", "actions"):
+            if k in got:
+                scale = max(1.0, float(r64[k].abs().max()))
+                e, e32 = float((got[k].double() - r64[k]).abs().max()) / scale, float((r32[k] - r64[k]).abs().max()) / scale
+                print("[rollout latent %s N=%d full=%s] %s %s: error %.3g (torch fp32 %.3g)" % (kind, N, full, tag, k, e, e32))
+                report.append((tag + " " + k, e, e32))
+                assert e <= 4 * e32 + 2e-7, (tag, k, e, e32)
+        return r64
+
+    def perturb(seed, params):
+        gp = torch.Generator().manual_seed(seed)
+        with torch.no_grad():          # an optimizer step's worth and more, IN PLACE: same addresses (what the image cache is keyed by), new values
+            for p in params:
+                p.add_((torch.randn(p.shape, generator=gp) * 0.5 * float(p.abs().mean())).to(device))
+
+    saved, saved_noise = (fused._LIB, fused._NN), ActorCriticCTS._noise
+    try:
+        if device == "cpu":
+            fused._LIB, fused._NN = sim_lib, nn_lib
+        alg = (MoECTS if kind == "MoECTS" else MoENGCTS)(model, N, 5, device=device, lib=sim_lib, use_graphs=False, fused_loss=True, fused_rollout=True)
+        if device == "cpu":
+            alg.nn_lib = nn_lib
+        alg.init_storage(N, T, [45], [n_priv], [12])
+        assert torch.equal(alg.teacher_env_idxs, ti) and torch.equal(alg.student_env_idxs, si) and alg.fused_rollout
+        ActorCriticCTS._noise = lambda self, like: eps          # (the algorithm asks a module whose _noise is replaced per step: _RolloutHeads._rollout_noise)
+        pk = alg._policy_kernel()
+        assert pk is not None and pk.enc_s is None and pk.moe_mix_ok(model) == (kind == "MoECTS")          # which arm of CTS._rollout_latent runs
+        st = alg.storage
+
+        def act(s):
+            st.step = s
+            a = alg.act(obs, priv, hist)
+            assert alg._pk_packed and a.shape == (N, 12)
+            return {"latent": alg._latent_buf.clone(), "mu": st.mu[s].clone(), "values": st.values[s].view(-1).clone(), "actions": a.clone()}
+
+        first = act(0)
+        check("act", first)
+        assert torch.equal(first["actions"], st.actions[0]) and torch.equal(first["actions"], first["mu"] + model.std.detach() * eps)
+        # the latent alone, twice on the same inputs: the same bits (no atomics, no uninitialised padding read, nothing left over in the buffer)
+        alg._latent_buf.fill_(9.0)
+        l1 = alg._rollout_latent(pk, priv, hist).clone()
+        alg._latent_buf.fill_(-9.0)
+        l2 = alg._rollout_latent(pk, priv, hist).clone()
+        assert torch.equal(l1, l2) and torch.equal(l1, first["latent"])
+        # new student weights at the same addresses: the next rollout (step 0: act packs and empties the image cache itself) ...
+        perturb(11, model.student_parameters())
+        alg.parameters_changed()
+        second = act(0)
+        check("act after a weight change, step 0", second)
+        assert float((second["latent"][si] - first["latent"][si]).abs().max()) > 1e-2, "the perturbation did not move the student latent: the check above would be empty"
+        assert torch.equal(second["latent"][ti], first["latent"][ti])          # (the teacher encoder's weights did not change)
+        # ... and in the middle of a rollout (a checkpoint loaded at step 1, OnPolicyRunnerCTS.load): only parameters_changed() tells act() that the packed weights and
+        # the split images beside them are stale (every network changes there: the packed teacher encoder / actor / critic too)
+        perturb(12, [p for n, p in model.named_parameters() if n != "std"])
+        alg.parameters_changed()
+        third = act(1)
+        check("act after a weight change, step 1", third)
+        assert float((third["latent"][si] - second["latent"][si]).abs().max()) > 1e-2
+        # ... and _rollout_latent on its own (compute_returns calls it after the last step)
+        perturb(13, model.student_parameters())
+        alg.parameters_changed()
+        check("_rollout_latent after a weight change", {"latent": alg._rollout_latent(pk, priv, hist).clone()})
+    finally:
+        fused._LIB, fused._NN = saved
+        ActorCriticCTS._noise = saved_noise
+    return report
+
+
+@pytest.mark.parametrize("N", [5, 203])
+@pytest.mark.parametrize("kind", ["MoECTS", "MoENGCTS"])
+def test_cts_rollout_latent_matches_float64(kind, N):
+    """host twin of tests/test_gpu_policy_kernel.py::test_cts_rollout_latent_on_gpu (the host builds of both libraries)"""
+    from helpers import load_oracle
+    cts_rollout_latent_vs_float64(load_oracle(), load_nn_emu(), "cpu", kind, N)
+
+
 def test_forward_rows_refuses_bad_descriptions():
     import ctypes as C
     lib = load_nn_emu()
