@@ -1,6 +1,8 @@
 """The recurrent actor-critic on the MI355X: the memory kernels (include/go2nn.h ABI 7) at the rollout's and the update's sizes against float64, with the rule of
 test_split_operand_policy_kernel_is_as_close_to_float64_as_fp32 (error <= 4 x the fp32 torch evaluation's + 2e-7), split-operand and fp32-MFMA products; the two
-golden iterations on the GPU; task go2_flat_rnn at 4096 envs (rollout and update replayed from HIP graphs, 30 iterations, play + export).  Run with -m gpu."""
+golden iterations on the GPU; task go2_flat_rnn at 4096 envs (rollout and update replayed from HIP graphs, 30 iterations, play + export) and its GRU / 2-layer
+variants through the replayed update graph; the cell kernels called directly and the memory at small, ragged and stacked shapes (the checks of
+tests/test_recurrent_host.py on the HIP kernels).  Run with -m gpu."""
 import os
 
 import numpy as np
@@ -197,31 +199,32 @@ def test_go2_flat_rnn_trains_in_graph_mode_and_plays(kernels, tmp_path):
     assert out.shape == (1, 12) and torch.isfinite(out).all()
 
 
-def test_go2_flat_rnn_graph_update_equals_eager_update(kernels, monkeypatch):
-    """task go2_flat_rnn at 4096 envs, 2 iterations on identical rollouts (same env seed, the same injected sampling noise), clip far away and a fixed rate: the
-    update replayed from a HIP graph (fused clip + Adam) against the eager update (autograd over the same kernels, torch's clip and Adam), held as the CTS twin
-    (tests/test_gpu_parity.py:test_cts_training_graph_vs_eager_on_gpu) holds them.  After iteration 1 the two arms have seen the same data: the median gap of every
-    parameter tensor within 2e-6 (a dropped, doubled or mis-fed launch moves its tensor by ~1e-3 per Adam step), single elements within 2e-3 (Adam turns the sign of a
-    near-zero gradient into a full 1e-3 step).  After iteration 2 (the graph arm's update replayed; the rounding differences have been through 24 env steps) the
-    per-tensor median within 1e-3, an order of magnitude under what a stale replay does."""
+def _graph_and_eager_snapshots(monkeypatch, N, rnn_type=None, layers=None, ITERS=2):
+    """task go2_flat_rnn (rnn_type / layers: its GRU / stacked variants, set as tests/test_recurrent_host.py:test_runner_builds_the_recurrent_policy sets them) trained
+    ITERS iterations on identical rollouts, eager and with the update replayed from a HIP graph -> {use_graphs: [parameters after each iteration]}"""
     from go2_rl_gym_amd.envs import task_registry
     from go2_rl_gym_amd.rsl_rl.modules import ActorCritic
     from go2_rl_gym_amd.utils import get_args
-    N, ITERS = 4096, 2
     out = {}
     for mode in (False, True):
         args = get_args(["--task", "go2_flat_rnn", "--num_envs", str(N), "--headless", "--seed", "3"])
         env, _ = task_registry.make_env("go2_flat_rnn", args)
         torch.manual_seed(3)
         _, train_cfg = task_registry.get_cfgs("go2_flat_rnn")
-        sched0, clip0 = train_cfg.algorithm.schedule, train_cfg.algorithm.clip_param
+        sched0, clip0, type0, layers0 = train_cfg.algorithm.schedule, train_cfg.algorithm.clip_param, train_cfg.policy.rnn_type, train_cfg.policy.rnn_num_layers
         train_cfg.algorithm.schedule, train_cfg.algorithm.clip_param = "fixed", 1.0e6
+        if rnn_type is not None:
+            train_cfg.policy.rnn_type, train_cfg.policy.rnn_num_layers = rnn_type, layers
         try:
             runner, _ = task_registry.make_alg_runner(env, "go2_flat_rnn", args, train_cfg=train_cfg, log_root=None, use_graphs=mode)
         finally:
             train_cfg.algorithm.schedule, train_cfg.algorithm.clip_param = sched0, clip0
+            train_cfg.policy.rnn_type, train_cfg.policy.rnn_num_layers = type0, layers0
         alg = runner.alg
         assert alg.use_graphs == mode and alg.clip_param == 1.0e6 and alg._rnn_memory() is not None
+        if rnn_type is not None:
+            rnn = alg.actor_critic.memory_a.rnn
+            assert isinstance(rnn, nn.LSTM if rnn_type == "lstm" else nn.GRU) and rnn.num_layers == layers == alg.actor_critic.memory_c.rnn.num_layers
         T, A = alg.storage.num_transitions_per_env, alg.storage.actions.shape[-1]
         gen, buf, calls = torch.Generator().manual_seed(17), torch.zeros(T, N, A, device=alg.device), [0]
 
@@ -238,12 +241,124 @@ def test_go2_flat_rnn_graph_update_equals_eager_update(kernels, monkeypatch):
         assert alg.graphs_captured() == mode
         out[mode] = snaps
         env.close()
-    for it, (med_bound, max_bound) in enumerate(((2e-6, 2e-3), (1e-3, None))):
+    return out
+
+
+def _graph_vs_eager_gaps(out, label, bounds):
+    """bounds: per iteration (largest per-tensor median gap or None, largest element gap or None) -> the largest per-tensor median gap of every iteration"""
+    meds = []
+    for it, (med_bound, max_bound) in enumerate(bounds):
         g, e = out[True][it], out[False][it]
         med = {n: float(np.median(np.abs(g[n] - e[n]))) for n in g}
         big = {n: float(np.abs(g[n] - e[n]).max()) for n in g}
-        print("[graph vs eager go2_flat_rnn] after iteration %d: largest per-tensor median gap %.1e (%s), largest element gap %.1e (%s)"
-              % (it + 1, max(med.values()), max(med, key=med.get), max(big.values()), max(big, key=big.get)))
-        assert all(np.isfinite(v).all() for v in g.values())
-        assert max(med.values()) <= med_bound, med
+        print("[graph vs eager %s] after iteration %d: largest per-tensor median gap %.1e (%s), largest element gap %.1e (%s)"
+              % (label, it + 1, max(med.values()), max(med, key=med.get), max(big.values()), max(big, key=big.get)))
+        assert all(np.isfinite(v).all() for v in g.values()) and all(np.isfinite(v).all() for v in e.values())
+        assert med_bound is None or max(med.values()) <= med_bound, med
         assert max_bound is None or max(big.values()) <= max_bound, big
+        meds.append(max(med.values()))
+    return meds
+
+
+def test_go2_flat_rnn_graph_update_equals_eager_update(kernels, monkeypatch):
+    """task go2_flat_rnn at 4096 envs, 2 iterations on identical rollouts (same env seed, the same injected sampling noise), clip far away and a fixed rate: the
+    update replayed from a HIP graph (fused clip + Adam) against the eager update (autograd over the same kernels, torch's clip and Adam), held as the CTS twin
+    (tests/test_gpu_parity.py:test_cts_training_graph_vs_eager_on_gpu) holds them.  After iteration 1 the two arms have seen the same data: the median gap of every
+    parameter tensor within 2e-6 (a dropped, doubled or mis-fed launch moves its tensor by ~1e-3 per Adam step), single elements within 2e-3 (Adam turns the sign of a
+    near-zero gradient into a full 1e-3 step).  After iteration 2 (the graph arm's update replayed; the rounding differences have been through 24 env steps) the
+    per-tensor median within 1e-3, an order of magnitude under what a stale replay does."""
+    out = _graph_and_eager_snapshots(monkeypatch, 4096)
+    _graph_vs_eager_gaps(out, "go2_flat_rnn", ((2e-6, 2e-3), (1e-3, None)))
+
+
+# After iteration 2 the parent's 1e-3 holds a variant only where its measured gap is under a third of it.  Measured on an MI355X at 256 envs (largest per-tensor
+# median gap after iteration 2): GRU x 1 8.5e-5, LSTM x 2 1.5e-7, GRU x 2 2.8e-6 — all three under 3.3e-4, so all three are held; None would mean finiteness only.
+IT2_MEDIAN_BOUND = {("gru", 1): 1e-3, ("lstm", 2): 1e-3, ("gru", 2): 1e-3}
+
+
+@pytest.mark.parametrize("rnn_type,layers", [("gru", 1), ("lstm", 2), ("gru", 2)])
+def test_gru_and_stacked_graph_update_equals_eager_update(kernels, monkeypatch, rnn_type, layers):
+    """the GRU and the 2-layer memories through the replayed update graph, at 256 envs: after iteration 1 (both arms have seen the same data) the bounds of
+    test_go2_flat_rnn_graph_update_equals_eager_update, for the reason given there; after iteration 2 finite parameters, the gap printed, and the parent's 1e-3
+    where IT2_MEDIAN_BOUND says the variant's measured gap leaves a factor of three"""
+    out = _graph_and_eager_snapshots(monkeypatch, 256, rnn_type, layers)
+    _graph_vs_eager_gaps(out, "go2_flat_rnn %s x %d, 256 envs" % (rnn_type, layers), ((2e-6, 2e-3), (IT2_MEDIAN_BOUND[(rnn_type, layers)], None)))
+
+
+# ---- the memory at small, ragged and stacked shapes: the checks of tests/test_recurrent_host.py (there on the host build) on the HIP kernels -----------------
+# What only the __global__ functions of csrc/go2nn_rnn.h contain — the flat index split k / H, k % H, the reset's row (k / H) % B over L > 1 layers, the grid sized by
+# the larger of two jobs with the smaller job's guard, the k < B H tail of the last workgroup — at 255 / 256 / 257 elements, H odd and up to 512, unequal job pairs.
+from test_recurrent_host import (CELL_SHAPES, RESET_SHAPES, ROLLOUT_CASES, TWO_JOBS, UPDATE_CASES, check_cell_backward, check_cell_forward,  # noqa: E402
+                                 check_cell_two_jobs, check_refusals, check_reset, check_shape_refusal, rollout_steps, update_sequence)
+
+DEV = "cuda:0"
+
+
+def _nn_lib():
+    from go2_rl_gym_amd.rsl_rl.modules import fused
+    assert fused._NN.go2nn_is_device_library() == 1
+    return fused._NN
+
+
+@pytest.mark.parametrize("typ", ["lstm", "gru"])
+@pytest.mark.parametrize("B,H", CELL_SHAPES)
+def test_cell_forward_on_gpu(kernels, typ, B, H):
+    """go2nn_rnn_cell_forward alone: h, c and the saved blocks under the fp32 rule, slots / carries / aliases bit for bit, nothing written past any output"""
+    check_cell_forward(_nn_lib(), DEV, typ, B, H)
+
+
+@pytest.mark.parametrize("typ", ["lstm", "gru"])
+@pytest.mark.parametrize("B,H", CELL_SHAPES)
+def test_cell_backward_on_gpu(kernels, typ, B, H):
+    """go2nn_rnn_cell_backward on the forward kernel's own gates against autograd through the float64 restatement: last step, no done, random done"""
+    check_cell_backward(_nn_lib(), DEV, typ, B, H)
+
+
+@pytest.mark.parametrize("specs", TWO_JOBS, ids=["small-first", "large-first"])
+def test_two_unequal_cell_jobs_in_one_launch_on_gpu(kernels, specs):
+    """the grid is sized by the larger job and the smaller one is guarded, whichever comes first: each job bit-equal to itself launched alone, every element written"""
+    check_cell_two_jobs(_nn_lib(), DEV, specs)
+
+
+@pytest.mark.parametrize("B,H", RESET_SHAPES)
+def test_reset_on_gpu(kernels, B, H):
+    """go2nn_rnn_reset over 1 .. 4 states and 1 .. 3 layers: the row of flat element k is (k / H) % B"""
+    check_reset(_nn_lib(), DEV, B, H)
+
+
+def test_refusals_on_gpu(kernels):
+    check_refusals(_nn_lib(), DEV)
+    check_shape_refusal(kernels, DEV)
+    torch.cuda.synchronize()
+
+
+def _same(a, b):
+    return len(a) == len(b) and all(torch.equal(u, v) for u, v in zip(a, b))
+
+
+@pytest.mark.parametrize("split", [True, False])
+@pytest.mark.parametrize("typ", ["lstm", "gru"])
+@pytest.mark.parametrize("H,L,N", ROLLOUT_CASES)
+def test_stacked_ragged_rollout_on_gpu(kernels, monkeypatch, typ, H, L, N, split):
+    """RolloutMemory.step / .reset with up to three layers at ragged sizes and one env (layer l fed from layer l - 1's in-place state), the critic-only step;
+    bit-reproducible from run to run"""
+    from go2_rl_gym_amd.rsl_rl.modules import fused
+    monkeypatch.setattr(fused, "_SPLIT", split)
+    a = rollout_steps(DEV, typ, H, L, N, rule=True)
+    b = rollout_steps(DEV, typ, H, L, N, rule=True)
+    torch.cuda.synchronize()
+    assert _same(a, b)
+
+
+@pytest.mark.parametrize("split", [True, False])
+@pytest.mark.parametrize("typ", ["lstm", "gru"])
+@pytest.mark.parametrize("H,L,T,B,K", UPDATE_CASES)
+def test_stacked_ragged_update_on_gpu(kernels, monkeypatch, typ, H, L, T, B, K, split):
+    """memory_sequence with up to three layers (RnnFunction.backward hands dgi W_ih down), states and dones as the strided views of recurrent_fixed_batches: the
+    output and all 4 L parameter gradients under the fp32 rule; bit-reproducible from run to run"""
+    from go2_rl_gym_amd.rsl_rl.modules import fused
+    monkeypatch.setattr(fused, "_SPLIT", split)
+    a = update_sequence(DEV, typ, H, L, T, B, K, rule=True)
+    b = update_sequence(DEV, typ, H, L, T, B, K, rule=True)
+    torch.cuda.synchronize()
+    assert _same(a, b)
