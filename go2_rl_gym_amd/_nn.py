@@ -48,6 +48,11 @@ GO2NN_MANEUVER_NUM, GO2NN_MANEUVER_ACC_FIRST, GO2NN_MANEUVER_MAX_SPECS, GO2NN_MA
 GO2NN_MANEUVER_ACC_NUM = GO2NN_MANEUVER_NUM - GO2NN_MANEUVER_ACC_FIRST
 MANEUVER_OUT = MANEUVER_ROWS[GO2NN_MANEUVER_ACC_FIRST:] + ("n",)
 MANEUVER_FIELDS = ("commands", "base_lin_vel", "base_ang_vel", "projected_gravity", "reset_buf", "time_out_buf")
+# the evaluator's sensor model: the values of Go2nnSensorIn.kind in the order of the enum GO2NN_SENSOR_* of include/go2nn.h (PASS: commands, previous actions — never delayed,
+# dropped or biased), the fields of Go2nnSensorSpec in the struct's order, and the limits of the ring, the observation width and the number of conditions
+SENSOR_KINDS = ("pass", "gyro", "gravity", "joint_pos", "joint_vel")
+SENSOR_SPEC_FIELDS = ("noise_mul", "gyro_bias", "gravity_bias", "joint_offset", "delay", "drop")
+GO2NN_SENSOR_MAX_DELAY, GO2NN_SENSOR_MAX_WIDTH, GO2NN_SENSOR_MAX_SPECS = 4, 64, 64
 _cached = None
 
 
@@ -135,6 +140,16 @@ class Go2nnManeuverIn(C.Structure):          # (within ABI 7)
     _fields_ = [(k, Go2nnEvalField) for k in MANEUVER_FIELDS] + [("num_specs", C.c_int32), ("num_commands", C.c_int32)]
 
 
+class Go2nnSensorSpec(C.Structure):          # (within ABI 7)
+    _fields_ = [("noise_mul", C.c_float), ("gyro_bias", C.c_float), ("gravity_bias", C.c_float), ("joint_offset", C.c_float), ("delay", C.c_int32), ("drop", C.c_float),
+                ("pad_", C.c_int32 * 2)]
+
+
+class Go2nnSensorIn(C.Structure):          # (within ABI 7)
+    _fields_ = [("obs", Go2nnEvalField), ("dones", C.c_void_p), ("scale", C.c_void_p), ("kind", C.c_void_p), ("D", C.c_int32), ("num_specs", C.c_int32), ("clip", C.c_float),
+                ("seed", C.c_uint32)]
+
+
 def trace_env_ids(env_ids, num_envs):
     """the tracked robots of go2nn_trace_record as the kernel needs them -> int32 numpy [K], strictly increasing, each in [0, num_envs).  The kernel cannot report a bad
     index (it would read outside the buffers), so anything else raises here."""
@@ -212,6 +227,11 @@ def bind(path):
     lib.go2nn_maneuver_apply.argtypes = [C.POINTER(Go2nnManeuverIn), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
     lib.go2nn_maneuver_accumulate.argtypes = [C.POINTER(Go2nnManeuverIn), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
     lib.go2nn_maneuver_reduce.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.go2nn_sensor_check_specs.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32]
+    lib.go2nn_sensor_state_bytes.restype = C.c_int64
+    lib.go2nn_sensor_state_bytes.argtypes = [C.c_int32, C.c_int32]
+    lib.go2nn_sensor_begin.argtypes = [C.c_void_p, C.c_void_p]
+    lib.go2nn_sensor_apply.argtypes = [C.POINTER(Go2nnSensorIn), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
     if lib.go2nn_abi_version() != GO2NN_ABI_VERSION:
         raise RuntimeError("%s: ABI version %d, expected %d" % (path, lib.go2nn_abi_version(), GO2NN_ABI_VERSION))
     return lib

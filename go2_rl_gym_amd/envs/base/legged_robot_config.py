@@ -293,6 +293,7 @@ class LeggedRobotCfgPPO(BaseConfig):
         maneuver_hold_s = 0.3   # settled = both errors stay below their thresholds for this long (the settle time includes it)
         maneuver_thr_lin = 0.3  # [m/s] ... the linear velocity error (recover_thr's convention, not a measurement)
         maneuver_thr_ang = 0.3  # [rad/s] ... and the yaw rate error
+        sensors = None          # None: the policy reads the simulator's exact, current observation.  A list of [name, {field: value}] (fields: noise [x the task's noise], gyro_bias [rad/s], gravity_bias, joint_offset [rad], delay [policy steps, <= 4], drop [probability]); --sensors: utils/evaluator.py DEFAULT_SENSORS
 
 
 class LeggedRobotCfgCTS(BaseConfig):
@@ -373,6 +374,7 @@ class LeggedRobotCfgCTS(BaseConfig):
         maneuver_hold_s = 0.3   # settled = both errors stay below their thresholds for this long (the settle time includes it)
         maneuver_thr_lin = 0.3  # [m/s] ... the linear velocity error (recover_thr's convention, not a measurement)
         maneuver_thr_ang = 0.3  # [rad/s] ... and the yaw rate error
+        sensors = None          # None: the policy reads the simulator's exact, current observation.  A list of [name, {field: value}] (fields: noise [x the task's noise], gyro_bias [rad/s], gravity_bias, joint_offset [rad], delay [policy steps, <= 4], drop [probability]); --sensors: utils/evaluator.py DEFAULT_SENSORS
 
 
 class LeggedRobotCfgMoECTS(LeggedRobotCfgCTS):

@@ -10,6 +10,9 @@ mean_level_cleared and cleared (higher is better), so --all_checkpoints --ladder
 in the run's directory.
 --maneuvers scores scripted command changes (start, brake, reverse, turn: utils/evaluator.py DEFAULT_MANEUVERS) in the scenarios' place; --metric then also takes
 switch_falls, settle_time_s, window_lin_vel_err, window_ang_vel_err (lower is better) and settled (higher is better).
+--sensors scores the default sensor conditions (noise, gyro bias, joint offset, one and two steps of latency, dropped frames: utils/evaluator.py DEFAULT_SENSORS) next to
+the scenarios; the overall figures are then means over the conditions' robots, so --all_checkpoints --sensors --metric lin_vel_err names the checkpoint that tracks best
+across all of them.
 --record N also records N robots of every (terrain x scenario) group and writes eval_results/trace_<checkpoint number>.npz into the run's directory."""
 import json
 import math
@@ -83,6 +86,8 @@ def evaluate(argv=None, log_root="default", env_kwargs=None, evaluator_kwargs=No
             rows[-1]["perturbations"] = res["perturbations"]
         if res.get("maneuvers") is not None:
             rows[-1]["maneuvers"] = res["maneuvers"]
+        if res.get("sensors") is not None:
+            rows[-1]["sensors"] = res["sensors"]
         if res.get("ladder_summary") is not None:
             rows[-1]["ladder_summary"] = res["ladder_summary"]
             import yaml

@@ -48,12 +48,22 @@ which the robot fell inside the window), `settled` (share after which both veloc
 `settle_time_s` (switch -> end of that hold, mean over the settled switches), `window_lin_vel_err` / `window_ang_vel_err` (means over the window's steps), `peak_tilt`
 (largest value inside the window, mean over switches).  With `maneuvers = None` nothing of this is allocated or launched.
 
+What the policy sees: with `evaluation.sensors` (--sensors selects DEFAULT_SENSORS; a list of [name, {field: value}]) every robot also belongs to one sensor condition
+— `noise` (multiple of the task's own observation noise), `gyro_bias` [rad/s], `gravity_bias`, `joint_offset` [rad] (a constant offset per robot and column, uniform within
++- the value), `delay` (policy steps, at most 4: the proprioceptive columns are that old) and `drop` (probability that a frame is lost and the previous one repeats) —, split
+like the perturbations: cell index = (terrain * S + scenario) * P + condition.  The observation no longer goes from the simulator straight into the policy: a step is
+    { policy(delivered), go2sim_step, write the commands, go2nn_sensor_apply(obs_buf -> delivered), go2nn_eval_accumulate }
+— two more launches (csrc/go2nn_sensor.h; the rule and the random streams are in include/go2nn.h), inside the captured chunk —, the CTS history and the recurrent state are
+fed the delivered frames too, and the metrics still read the simulator's true state.  No reduce of its own: go2nn_eval_reduce over the cells gives RESULT_KEYS per condition.
+With `sensors = None` nothing of this is allocated or launched.
+
 Isolated: nothing of the training env, the model, the optimizer or torch's generators is written; policy state the evaluation needs (the CTS observation history, the
 recurrent memory's hidden state) lives in buffers of the evaluator."""
 import copy
 import ctypes as C
 import math
 import os
+import types
 
 import numpy as np
 import torch
@@ -62,7 +72,7 @@ from .. import _abi
 from .._nn import (EVAL_FIELDS, EVAL_METRICS, GO2NN_EVAL_NUM, GO2NN_RNN_GRU, GO2NN_RNN_LSTM, GO2NN_ROBUST_ACC_NUM, GO2NN_ROBUST_MAX_SPECS, GO2NN_ROBUST_NUM, ROBUST_FIELDS, ROBUST_MASK,
                    GO2NN_LADDER_NUM, GO2NN_LADDER_OUT_NUM, LADDER_FIELDS, LADDER_OUT, GO2NN_MANEUVER_ACC_NUM, GO2NN_MANEUVER_MAX_SEGS, GO2NN_MANEUVER_MAX_SPECS, GO2NN_MANEUVER_NUM,
                    MANEUVER_FIELDS, MANEUVER_OUT, Go2nnEvalIn, Go2nnFwdJob, Go2nnLadderIn, Go2nnManeuverIn, Go2nnManeuverSpec, Go2nnMlpIO, Go2nnRnnCellJob, Go2nnRobustIn,
-                   Go2nnRobustSpec, PackedMlp)
+                   Go2nnRobustSpec, PackedMlp, GO2NN_SENSOR_MAX_DELAY, GO2NN_SENSOR_MAX_SPECS, SENSOR_KINDS, Go2nnSensorIn, Go2nnSensorSpec)
 from .helpers import class_to_dict
 
 DEFAULT_SCENARIOS = [["forward_1.0", 1.0, 0.0, 0.0], ["forward_2.0", 2.0, 0.0, 0.0], ["backward_1.0", -1.0, 0.0, 0.0], ["lateral_0.5", 0.0, 0.5, 0.0],
@@ -82,6 +92,12 @@ DEFAULT_MANEUVERS = [["start_1.0", [[0.0, 0.0, 0.0, 0.0], [5.0, 1.0, 0.0, 0.0]]]
                      ["sidestep_flip_0.5", [[0.0, 0.0, 0.5, 0.0], [5.0, 0.0, -0.5, 0.0]]], ["turn_flip_1.0", [[0.0, 0.0, 0.0, 1.0], [5.0, 0.0, 0.0, -1.0]]],
                      ["walk_into_turn_1.0", [[0.0, 1.0, 0.0, 0.0], [5.0, 1.0, 0.0, 1.0]]]]
 MANEUVER_KEYS = ("switches", "switch_falls", "settled", "settle_time_s", "window_lin_vel_err", "window_ang_vel_err", "peak_tilt")
+# name, {field: value}; fields: noise (x the task's own noise vector), gyro_bias [rad/s], gravity_bias, joint_offset [rad], delay [policy steps], drop [probability]
+DEFAULT_SENSORS = [["nominal", {}], ["noise_1.0", {"noise": 1.0}], ["noise_3.0", {"noise": 3.0}], ["gyro_bias_0.1", {"gyro_bias": 0.1}],
+                   ["joint_offset_0.05", {"joint_offset": 0.05}], ["delay_1", {"delay": 1}], ["delay_2", {"delay": 2}], ["drop_0.2", {"drop": 0.2}]]
+SENSOR_FIELDS = ("noise", "gyro_bias", "gravity_bias", "joint_offset", "delay", "drop")
+# the Go2 observation (envs/go2/go2_env.py): base angular velocity 3, projected gravity 3, commands 3, joint positions 12, joint velocities 12, previous actions 12
+GO2_OBS_KINDS = ["gyro"] * 3 + ["gravity"] * 3 + ["pass"] * 3 + ["joint_pos"] * 12 + ["joint_vel"] * 12 + ["pass"] * 12
 MAX_CHUNK = 50
 # The accumulate kernel runs AFTER the env step, when the simulator has already rolled its action history (last_actions = this step's actions): the previous step's
 # actions — the kernel's `last_actions` input — are then in the simulator's last_last_actions buffer.
@@ -291,6 +307,14 @@ class PolicyEvaluator:
         self.maneuvers = [[str(m[0]), [[float(x) for x in seg] for seg in m[1]]] for m in mans] if mans else None
         if self.maneuvers is not None and (self.ladder or self.perturbations is not None):
             raise ValueError("evaluation.maneuvers cannot be combined with evaluation.ladder or evaluation.perturbations: one evaluation splits the robots along ONE extra axis")
+        sens = _get(evaluation, "sensors")
+        self.sensors = [[str(c[0]), dict(c[1] or {})] for c in sens] if sens else None
+        if self.sensors is not None:
+            if self.maneuvers is not None or self.ladder or self.perturbations is not None:
+                raise ValueError("evaluation.sensors cannot be combined with evaluation.perturbations, evaluation.ladder or evaluation.maneuvers: one evaluation splits the "
+                                 "robots along ONE extra axis")
+            self._noise_cfg = copy.deepcopy(env_cfg.noise)          # the task's own noise scales, from the config as the task trains with it
+            self._noise_cfg.noise_level = 1.0
         if self.ladder:
             self._init_ladder()
         elif self.maneuvers is not None:          # the maneuvers take the scenarios' place: a "scenario" per maneuver, its command that of the first segment
@@ -322,6 +346,8 @@ class PolicyEvaluator:
         self.out = torch.zeros(self.num_cells, GO2NN_EVAL_NUM + 2, dtype=torch.float64, device=self.device)
         if self.perturbations is not None:
             self._build_robust()
+        if self.sensors is not None:
+            self._build_sensors()
         if self.ladder:
             self._build_ladder()
         if self.maneuvers is not None:
@@ -465,11 +491,11 @@ class PolicyEvaluator:
 
     def _build_groups(self):
         """env -> (terrain kind x scenario) group, built once on the host: the kinds are those of the columns the envs stand in (one kind, 'plane', without a terrain mesh);
-        within a kind the envs take the scenarios in turn, so the groups of a kind differ by at most one env.  With P perturbations they take the (scenario, perturbation)
+        within a kind the envs take the scenarios in turn, so the groups of a kind differ by at most one env.  With P perturbations (or P sensor conditions) they take the (scenario, perturbation)
         CELLS in turn; cell index = (terrain * S + scenario) * P + perturbation — the kernels' group —, and a group is the union of its P cells (P = 1 without).
         With the ladder's L levels they take the (level, scenario) cells in turn; cell index = (terrain * L + level) * S + scenario, a group is the union of its L cells"""
         from .terrain import KIND_NAMES
-        N, S, P = self.num_envs, len(self.scenarios), len(self.perturbations or [None])
+        N, S, P = self.num_envs, len(self.scenarios), len(self.perturbations or self.sensors or [None])
         L = len(self.levels) if self.ladder else 1
         if self.env.custom_origins:
             kind_of_env = self.env.terrain_cols2id.cpu().numpy()[self.env.terrain_types.cpu().numpy()]
@@ -535,6 +561,55 @@ class PolicyEvaluator:
             print("[go2_rl_gym_amd] evaluation: %d of %d (terrain x scenario x perturbation) cells have fewer than 4 robots (smallest: %d); raise evaluation.num_envs"
                   % (int((sizes < 4).sum()), self.num_cells, int(sizes.min())))
 
+    def _build_sensors(self):
+        """the sensor conditions as the kernel reads them: P specs (observation scales folded in), the env -> condition map, the observation's layout (kind, the task's noise
+        vector at noise_level 1), the state allocation and the delivered frame [N, D] — a fixed address, so a captured policy launch keeps reading it"""
+        conds, P, env = self.sensors, len(self.sensors), self.env
+        if P > GO2NN_SENSOR_MAX_SPECS or len({c[0] for c in conds}) != P:
+            raise ValueError("evaluation.sensors: 1 .. %d conditions with distinct names, got %r" % (GO2NN_SENSOR_MAX_SPECS, [c[0] for c in conds]))
+        D = int(env.num_obs)
+        if D != len(GO2_OBS_KINDS) or not hasattr(env, "_get_noise_scale_vec"):
+            raise ValueError("evaluation.sensors: no observation layout for %s with %d observation columns (the Go2 layout of envs/go2/go2_env.py is covered)"
+                             % (type(env).__name__, D))
+        scale = env._get_noise_scale_vec(types.SimpleNamespace(noise=self._noise_cfg)).detach().cpu().numpy().astype(np.float32)
+        kind = np.asarray([SENSOR_KINDS.index(k) for k in GO2_OBS_KINDS], np.int32)
+        o = self.cfg.normalization.obs_scales
+        specs = (Go2nnSensorSpec * P)()
+        for sp, (name, fields) in zip(specs, conds):
+            unknown = set(fields) - set(SENSOR_FIELDS)
+            if unknown:
+                raise ValueError("sensor condition %r: unknown field(s) %s (%s)" % (name, sorted(unknown), ", ".join(SENSOR_FIELDS)))
+            delay = fields.get("delay", 0)
+            if int(delay) != delay:
+                raise ValueError("sensor condition %r: delay = %r (whole policy steps, 0 .. %d)" % (name, delay, GO2NN_SENSOR_MAX_DELAY))
+            sp.noise_mul, sp.gravity_bias, sp.delay, sp.drop = float(fields.get("noise", 0.0)), float(fields.get("gravity_bias", 0.0)), int(delay), float(fields.get("drop", 0.0))
+            sp.gyro_bias, sp.joint_offset = float(fields.get("gyro_bias", 0.0)) * float(o.ang_vel), float(fields.get("joint_offset", 0.0)) * float(o.dof_pos)
+        self._check(self.nn.go2nn_sensor_check_specs(C.cast(specs, C.c_void_p), P, C.c_void_p(kind.ctypes.data), C.c_void_p(scale.ctypes.data), D), "go2nn_sensor_check_specs")
+        self.sspecs_host, self.sensor_kind_host, self.sensor_scale_host = specs, kind, scale
+        self.sspecs = torch.from_numpy(np.frombuffer(bytes(specs), np.uint8).copy()).to(self.device)
+        self.sensor_kind, self.sensor_scale = torch.from_numpy(kind).to(self.device), torch.from_numpy(scale).to(self.device)
+        self.sensor_host = self.pert_host          # the condition of every env (the cells' last axis)
+        self.sensor_of_env = torch.from_numpy(self.sensor_host).to(self.device)
+        self.sstate = torch.zeros(int(self.nn.go2nn_sensor_state_bytes(self.num_envs, D)), dtype=torch.uint8, device=self.device)
+        self.delivered = torch.zeros(self.num_envs, D, device=self.device)
+        self.sensor_clip, self.sensor_seed = float(self.cfg.normalization.clip_observations), int(_get(self.ev, "seed", 12345)) & 0xFFFFFFFF
+        sizes = np.bincount(self.cell_host, minlength=self.num_cells)
+        if sizes.min() < 4:
+            print("[go2_rl_gym_amd] evaluation: %d of %d (terrain x scenario x sensor condition) cells have fewer than 4 robots (smallest: %d); raise evaluation.num_envs"
+                  % (int((sizes < 4).sum()), self.num_cells, int(sizes.min())))
+
+    def _sensor_in(self):
+        """the sensor kernel's view of the current simulator: its observation and reset flags, and the evaluator's own layout tensors"""
+        t, a = self.env.obs_buf, Go2nnSensorIn()
+        a.obs.p, a.obs.env_stride, a.obs.comp_stride = t.data_ptr(), t.stride(0), t.stride(1)
+        a.dones, a.scale, a.kind = self.env._buf["reset_buf"].data_ptr(), self.sensor_scale.data_ptr(), self.sensor_kind.data_ptr()
+        a.D, a.num_specs, a.clip, a.seed = t.shape[1], len(self.sensors), self.sensor_clip, self.sensor_seed
+        return a
+
+    def _sensor_apply(self, sin):
+        self._check(self.nn.go2nn_sensor_apply(C.byref(sin), C.c_void_p(self.sspecs.data_ptr()), C.c_void_p(self.sensor_of_env.data_ptr()), C.c_void_p(self.sstate.data_ptr()),
+                                               C.c_void_p(self.delivered.data_ptr()), self.num_envs, self._stream()), "go2nn_sensor_apply")
+
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream) if self.on_device else None
 
@@ -588,11 +663,13 @@ class PolicyEvaluator:
         return a
 
     # ------------------------------------------------------------------ one env step of the evaluation (pure enqueue)
-    def _step(self, pol, ein, rin=None, k=None, lin=None, min_=None):
+    def _step(self, pol, ein, rin=None, k=None, lin=None, min_=None, sin=None):
         """rin: the perturbation kernels' input (None without perturbations);  k: the step's index in an eager run (None inside a capture: no callback there);
-        lin: the ladder kernel's input (None without the ladder);  min_: the maneuver kernels' input (None without maneuvers)"""
+        lin: the ladder kernel's input (None without the ladder);  min_: the maneuver kernels' input (None without maneuvers);  sin: the sensor kernel's input (None without
+        sensors: the policy then reads the simulator's observation itself)"""
         env = self.env
-        actions = pol.act(env.obs_buf)
+        obs = env.obs_buf if sin is None else self.delivered
+        actions = pol.act(obs)
         if min_ is not None:
             self._maneuver(self.nn.go2nn_maneuver_apply, "go2nn_maneuver_apply", min_)
             if k is not None and self.apply_callback is not None:
@@ -606,6 +683,8 @@ class PolicyEvaluator:
             self._maneuver(self.nn.go2nn_maneuver_accumulate, "go2nn_maneuver_accumulate", min_)
         else:
             env.commands.copy_(self.commands)          # a robot that fell was reset by the step and drew a new command: the scenario's command holds
+        if sin is not None:          # the frame the policy gets NEXT step, and what its history / memory is fed below
+            self._sensor_apply(sin)
         self._check(self.nn.go2nn_eval_accumulate(C.byref(ein), C.c_void_p(self.acc.data_ptr()), self.num_envs, self._stream()), "go2nn_eval_accumulate")
         if rin is not None:
             self._robust(self.nn.go2nn_robust_accumulate, "go2nn_robust_accumulate", rin)
@@ -613,22 +692,22 @@ class PolicyEvaluator:
             self._check(self.nn.go2nn_ladder_accumulate(C.byref(lin), C.c_void_p(self.ltable.data_ptr()), self.num_envs, self._stream()), "go2nn_ladder_accumulate")
         if self.recorder is not None:
             self.recorder.record()
-        pol.after_step(env.obs_buf, env._buf["reset_buf"])
+        pol.after_step(obs, env._buf["reset_buf"])
 
     def _clear(self):
         self._check(self.nn.go2nn_eval_clear(C.c_void_p(self.acc.data_ptr()), self.num_envs, self._stream()), "go2nn_eval_clear")
         if self.recorder is not None:
             self.recorder.clear()
 
-    def _run_eager(self, pol, ein, rin, lin=None, min_=None):
+    def _run_eager(self, pol, ein, rin, lin=None, min_=None, sin=None):
         for k in range(self.warmup_steps + self.steps):
             if k == self.warmup_steps:
                 self._clear()
-            self._step(pol, ein, rin, k, lin, min_)
+            self._step(pol, ein, rin, k, lin, min_, sin)
             if self.step_callback is not None:
                 self.step_callback(self, k, k >= self.warmup_steps)
 
-    def _run_graph(self, pol, ein, rin, lin=None, min_=None):
+    def _run_graph(self, pol, ein, rin, lin=None, min_=None, sin=None):
         """capture `chunk` steps on this evaluation's simulator, replay them for the whole horizon -> False if the capture failed (nothing has run then)"""
         from ..rsl_rl.algorithms._graph import no_gc, strict_graphs
         torch.cuda.synchronize(self.device)
@@ -636,7 +715,7 @@ class PolicyEvaluator:
         try:
             with no_gc(), torch.cuda.graph(g):
                 for _ in range(self.chunk):
-                    self._step(pol, ein, rin, lin=lin, min_=min_)
+                    self._step(pol, ein, rin, lin=lin, min_=min_, sin=sin)
         except Exception as e:      # noqa: BLE001
             if strict_graphs():
                 raise RuntimeError("HIP-graph capture of the evaluation failed (%s: %s)" % (type(e).__name__, e)) from e
@@ -659,6 +738,8 @@ class PolicyEvaluator:
         With `evaluation.maneuvers` every leaf of "groups" (a "scenario" being a maneuver) and "overall" gain MANEUVER_KEYS; also "maneuvers": {name: {RESULT_KEYS +
         MANEUVER_KEYS}} over the terrains, "maneuver_table" (go2nn_maneuver_reduce's raw output per cell) "switch_steps": {name: [counted steps]}, "maneuver_schedule": {name: [[step, vx, vy, yaw rate], ...]} and "maneuver_rule" (window and hold in steps, the thresholds).
         A trace gains "maneuvers", "maneuver_of_robot" and "switch_steps" (int32 [M, 7], padded with -1).
+        With `evaluation.sensors` also "cells": {terrain: {scenario: {condition: {RESULT_KEYS}}}}, "sensors": {condition: {RESULT_KEYS}} over the terrains and scenarios,
+        "sensor_names", "sensor_specs": {condition: {SENSOR_FIELDS}} and "cell_table" (go2nn_eval_reduce's raw output per cell).  A trace gains "sensors" and "sensor_of_robot".
         With `evaluation.record` also "trace": TrajectoryRecorder.fetch() of the counted steps plus "group_of_robot" (index into terrain_names x scenarios, terrain-major,
         per tracked robot), "terrain_names" and "scenarios".
         use_graph: None = eager, or with `evaluation.replay` eager the first time and a captured chunk afterwards (on the GPU); True / False force it."""
@@ -673,7 +754,12 @@ class PolicyEvaluator:
             zero = torch.zeros(self.num_envs, env.num_actions, device=self.device)
             _abi.check(env.lib, env.lib.go2sim_step(env.handle, C.c_void_p(zero.data_ptr()), self._stream()), "go2sim_step")          # BaseTask.reset: the first observations
             env.commands.copy_(self.commands)
-            pol.begin(env.obs_buf)
+            sin = None
+            if self.sensors is not None:          # the policy's first observation and the CTS history's first frame are sensor frames: step 0 of the sensor's own cursor
+                sin = self._sensor_in()
+                self._check(self.nn.go2nn_sensor_begin(C.c_void_p(self.sstate.data_ptr()), self._stream()), "go2nn_sensor_begin")
+                self._sensor_apply(sin)
+            pol.begin(env.obs_buf if sin is None else self.delivered)
             if self.recorder is not None:
                 self.recorder.bind(env)
             self._clear()
@@ -691,9 +777,9 @@ class PolicyEvaluator:
                 self._check(self.nn.go2nn_maneuver_begin(C.c_void_p(self.mtable.data_ptr()), self.num_envs, -self.warmup_steps, self._stream()), "go2nn_maneuver_begin")
             replay = bool(_get(self.ev, "replay", False))
             graph = (replay and self.on_device and self.evaluations > 0 and self.step_callback is None) if use_graph is None else bool(use_graph and self.on_device)
-            done = graph and self._run_graph(pol, ein, rin, lin, min_)
+            done = graph and self._run_graph(pol, ein, rin, lin, min_, sin)
             if not done:
-                self._run_eager(pol, ein, rin, lin, min_)
+                self._run_eager(pol, ein, rin, lin, min_, sin)
             self.last_mode = "graph" if done else "eager"
             self._check(self.nn.go2nn_eval_reduce(C.c_void_p(self.acc.data_ptr()), C.c_void_p(self.group.data_ptr()), self.num_envs, self.num_cells,
                                                   C.c_void_p(self.out.data_ptr()), self._stream()), "go2nn_eval_reduce")
@@ -723,6 +809,8 @@ class PolicyEvaluator:
                 trace.update(levels=list(self.levels), level_of_robot=self.level_of_env[trace["env_ids"]].copy())
             if self.perturbations is not None:          # push_steps: the counted steps (= frame indices) whose go2nn_robust_apply pushed; the frame holds the state AFTER that step
                 trace.update(perturbations=[p[0] for p in self.perturbations], pert_of_robot=self.pert_host[trace["env_ids"]].copy(), push_steps=self.push_steps.copy())
+            if self.sensors is not None:
+                trace.update(sensors=[c[0] for c in self.sensors], sensor_of_robot=self.sensor_host[trace["env_ids"]].copy())
             if self.maneuvers is not None:
                 # switch_steps [M, GO2NN_MANEUVER_MAX_SEGS - 1] int32: per maneuver the counted steps (= frame indices) at which a new segment begins — that frame carries the
                 # new command —, padded with -1 (a rectangular array: maneuvers differ in their number of switches, and the trace goes to an .npz)
@@ -791,7 +879,7 @@ class PolicyEvaluator:
         """cells: the eval reduce table per (terrain, scenario, perturbation) cell; rcells: the robust one (None without perturbations: a cell is a group then);
         lcells: the ladder's (None without the ladder), cells being per (terrain, level, scenario) then;  mcells: the maneuvers' (None without maneuvers), per
         (terrain, maneuver) cell = group"""
-        S, P = len(self.scenarios), len(self.perturbations or [None])
+        S, P = len(self.scenarios), len(self.perturbations or self.sensors or [None])
         if lcells is not None:
             table = cells.reshape(len(self.terrain_names), len(self.levels), S, -1).sum(1).reshape(len(self.groups), -1)
         else:
@@ -809,6 +897,14 @@ class PolicyEvaluator:
             res["overall"].update(self._robust_row(rcells.sum(0)))
             res.update(perturbation_names=names, cell_table=cells, robust_table=rcells, push_steps=self.push_steps.tolist(),
                        push={"first": self.push_first, "period": self.push_period, "window": self.push_window, "hold": self.push_hold, "count": self.push_count})
+        if self.sensors is not None:
+            names = [c[0] for c in self.sensors]
+            c3 = cells.reshape(len(self.groups), P, -1)
+            res["cells"] = {t: {s[0]: {n: self._row(c3[ti * S + si, pi]) for pi, n in enumerate(names)} for si, s in enumerate(self.scenarios)}
+                            for ti, t in enumerate(self.terrain_names)}
+            res["sensors"] = {n: self._row(c3[:, pi].sum(0)) for pi, n in enumerate(names)}
+            res.update(sensor_names=names, cell_table=cells,
+                       sensor_specs={n: {k: (int(f.get(k, 0)) if k == "delay" else float(f.get(k, 0.0))) for k in SENSOR_FIELDS} for n, f in self.sensors})
         if lcells is not None:
             self._ladder_results(res, cells, lcells)
         if mcells is not None:
@@ -834,7 +930,7 @@ class PolicyEvaluator:
 # ---------------------------------------------------------------------------------------------------------------------------------------------------------------
 def scalars(res):
     """[(tag, value)]: 'Eval/<metric>' for the overall figures, 'Eval/<terrain>/<scenario>/<metric>' per group, with perturbations 'Eval/robust/<name>/<metric>', with
-    maneuvers 'Eval/maneuver/<name>/<metric>' and, with the ladder, 'Eval/ladder/<terrain>/{level_cleared,mean_level_cleared}' and 'Eval/ladder/mean_level_cleared'"""
+    maneuvers 'Eval/maneuver/<name>/<metric>', with sensor conditions 'Eval/sensors/<name>/<metric>' and, with the ladder, 'Eval/ladder/<terrain>/{level_cleared,mean_level_cleared}' and 'Eval/ladder/mean_level_cleared'"""
     out = [("Eval/" + k, res["overall"][k]) for k in RESULT_KEYS]
     for t, per in res["groups"].items():
         for s, d in per.items():
@@ -843,6 +939,8 @@ def scalars(res):
         out += [("Eval/robust/%s/%s" % (n, k), d[k]) for k in RESULT_KEYS + ROBUST_KEYS]
     for n, d in (res.get("maneuvers") or {}).items():
         out += [("Eval/maneuver/%s/%s" % (n, k), d[k]) for k in RESULT_KEYS + MANEUVER_KEYS]
+    for n, d in (res.get("sensors") or {}).items():
+        out += [("Eval/sensors/%s/%s" % (n, k), d[k]) for k in RESULT_KEYS]
     if res.get("ladder_summary") is not None:
         for t, d in res["ladder_summary"].items():
             out += [("Eval/ladder/%s/%s" % (t, k), d[k]) for k in LADDER_SUMMARY_KEYS]
@@ -860,6 +958,8 @@ def results_dict(res, it=None):
         d["maneuvers"] = {n: dict(v) for n, v in res["maneuvers"].items()}
         d["maneuver_rule"] = dict(res["maneuver_rule"])
         d["maneuver_schedule"] = {n: [list(seg) for seg in segs] for n, segs in res["maneuver_schedule"].items()}
+    if res.get("sensors") is not None:          # per condition over the terrains and scenarios, next to the condition's own spec
+        d["sensors"] = {n: dict(v, spec=dict(res["sensor_specs"][n])) for n, v in res["sensors"].items()}
     if res.get("ladder") is not None:          # the full curve, and what it comes to per terrain kind
         d["ladder"] = {t: {int(lv): {s: dict(v) for s, v in per.items()} for lv, per in levels.items()} for t, levels in res["ladder"].items()}
         d["ladder_summary"] = {t: dict(v) for t, v in res["ladder_summary"].items()}
@@ -893,6 +993,11 @@ def format_table(res):
         lines += ["", "%-20s " % "maneuver" + " ".join("%18s" % c for c in cols)]
         for n, d in list(res["maneuvers"].items()) + [("all", res["overall"])]:
             lines.append("%-20s " % n + " ".join("%18d" % d[c] if c in whole else "%18.4f" % d[c] for c in cols))
+    if res.get("sensors") is not None:          # one more block: one line per sensor condition, over every terrain and scenario
+        cols = ("lin_vel_err", "ang_vel_err", "tilt", "action_rate_sq", "torque_sq", "falls", "survival", "n_envs")
+        lines += ["", "%-20s " % "sensors" + " ".join("%16s" % c for c in cols)]
+        for n, d in list(res["sensors"].items()) + [("all", res["overall"])]:
+            lines.append("%-20s " % n + " ".join("%16d" % d[c] if c == "n_envs" else "%16.4f" % d[c] for c in cols))
     return "\n".join(lines)
 
 

@@ -524,6 +524,63 @@ int go2nn_maneuver_accumulate(const Go2nnManeuverIn* in, const Go2nnManeuverSpec
  * function) of go2nn_eval_reduce: fixed order, bit-equal outputs for equal inputs, group ids outside [0, G) ignored, an empty group gives zeros.  1 <= G <= 65535. */
 int go2nn_maneuver_reduce(const float* table, const int32_t* group, int32_t N, int32_t G, double* out, void* stream);
 
+/* ---- the evaluator's sensor model: what the policy SEES — noise, bias, latency, dropped frames (go2_rl_gym_amd/utils/evaluator.py, `evaluation.sensors`).
+ * ADDED WITHIN ABI 7: four new entry points, nothing existing changes, GO2NN_ABI_VERSION stays 7.
+ * A sensor evaluation step is { policy(delivered), go2sim_step, go2nn_sensor_apply(obs_buf -> delivered), go2nn_eval_accumulate }: two more plain launches per step
+ * (capturable; one lane per observation float, no atomics), no reduce of its own.  The metrics still read the simulator's true state.  Every env e belongs to one condition
+ * sensor_of_env[e] in [0, P), P <= 64; an env with sensor_of_env[e] outside [0, P) gets its observation's bits unchanged.
+ * A condition is one Go2nnSensorSpec (an array of P of them in the buffers' memory space):
+ *   noise_mul                multiple of the task's own observation noise (1 = what the task trains with)
+ *   gyro_bias, gravity_bias, joint_offset   half-width of the constant per-(env, column) offset of the gyro / gravity / joint-position columns, in OBSERVATION units (the
+ *                            caller folds the observation scales in: rad/s x obs_scales.ang_vel, rad x obs_scales.dof_pos)
+ *   delay                    age of the proprioceptive columns in policy steps, 0 .. GO2NN_SENSOR_MAX_DELAY
+ *   drop                     probability in [0, 1) that a whole frame is lost: the proprioceptive columns then repeat what was delivered last
+ * The layout (Go2nnSensorIn): D <= GO2NN_SENSOR_MAX_WIDTH columns; scale[D], the task's noise vector at noise_level 1; kind[D], one of the enum below — PASS columns
+ * (commands, previous actions) are never delayed, dropped or biased; clip, the observation clip; seed.
+ * The state: ONE allocation of go2nn_sensor_state_bytes(N, D) bytes in the buffers' memory space: an int32 cursor (steps since go2nn_sensor_begin) in the first 256 bytes,
+ * a ring [R][N][D] of clean observations, R = GO2NN_SENSOR_MAX_DELAY + 1, and held [N][D], the frame last delivered.
+ * go2nn_sensor_apply, per (env e, column c), with s = the cursor, x = obs[e, c], fresh = (s == 0 or dones[e]):
+ *   1. ring[s % R][e][c] = x; if fresh, every slot of the ring = x (a robot that was just reset never sees its pre-fall past);
+ *   2. src = x for a PASS column, otherwise ring[(s - delay) % R][e][c];
+ *   3. the frame is DROPPED when drop > 0, not fresh, and u(seed, DROP; e, 0, s) < drop — one draw per env and step —: every column that is not PASS delivers held[e][c];
+ *   4. otherwise, with b = (2 u(seed, BIAS; e, c, 0) - 1) mag  (mag: gyro_bias / gravity_bias / joint_offset by the column's kind, 0 for the others; one draw per (e, c) for
+ *      the whole evaluation) and k = fl(scale[c] noise_mul) (one rounded fp32 product):
+ *        mag == 0 and k == 0:  out = src, the BITS (no add, no clamp: an all-zero spec is the identity, and a delay alone delivers old bits)
+ *        otherwise:            out = clamp(src + b + (2 u(seed, NOISE; e, c, s) - 1) k, -clip, clip)
+ *   5. held[e][c] = out, and out goes to the output buffer [N, D] (row-major; it must not be the input).
+ * Then the cursor is advanced by a second, one-lane launch on the same stream: the step is read from device memory, so a captured pair advances on every replay.
+ * The uniforms: u = (x >> 8) 2^-24 with x = word 0 of Philox4x32-10 under key (seed, tag) — tag 1 NOISE, 2 BIAS, 3 DROP — and counter (env, column, step, 0). */
+enum { GO2NN_SENSOR_PASS = 0, GO2NN_SENSOR_GYRO, GO2NN_SENSOR_GRAVITY, GO2NN_SENSOR_JOINT_POS, GO2NN_SENSOR_JOINT_VEL };          /* the values of kind[] */
+#define GO2NN_SENSOR_MAX_DELAY 4                                            /* policy steps: 80 ms at 50 Hz */
+#define GO2NN_SENSOR_MAX_WIDTH 64
+#define GO2NN_SENSOR_MAX_SPECS 64
+typedef struct Go2nnSensorSpec {
+  float noise_mul, gyro_bias, gravity_bias, joint_offset;
+  int32_t delay;
+  float drop;
+  int32_t pad_[2];
+} Go2nnSensorSpec;
+/* obs: the clean observation as (pointer, env stride, component stride) in ELEMENTS like Go2nnEvalIn's fields (row-major [N, D]: D and 1);  dones: uint8 [N];
+ * scale: fp32 [D], kind: int32 [D], both in the buffers' memory space;  num_specs = P. */
+typedef struct Go2nnSensorIn {
+  Go2nnEvalField obs;
+  const uint8_t* dones;
+  const float* scale;
+  const int32_t* kind;
+  int32_t D;
+  int32_t num_specs;
+  float clip;
+  uint32_t seed;
+} Go2nnSensorIn;
+/* Host-side check of P specs and the layout in HOST memory, before they are copied to the buffers' memory space: GO2NN_EINVAL with a message for a null pointer, P outside
+ * [1, 64], D outside [1, 64], kind[c] outside 0 .. 4, scale[c] negative or not finite, delay outside [0, GO2NN_SENSOR_MAX_DELAY], drop outside [0, 1) (or NaN), a
+ * magnitude (noise_mul, gyro_bias, gravity_bias, joint_offset) negative or not finite. */
+int go2nn_sensor_check_specs(const Go2nnSensorSpec* host_specs, int32_t P, const int32_t* host_kind, const float* host_scale, int32_t D);
+int64_t go2nn_sensor_state_bytes(int32_t N, int32_t D);          /* 0 for N < 1 or D outside [1, 64] */
+int go2nn_sensor_begin(void* state, void* stream);               /* cursor = 0; ring and held are left as they are (step 0 fills them) */
+/* GO2NN_EINVAL for null pointers, N < 1, D or num_specs outside [1, 64], a stride < 1, clip <= 0 (or NaN). */
+int go2nn_sensor_apply(const Go2nnSensorIn* in, const Go2nnSensorSpec* specs, const int32_t* sensor_of_env, void* state, float* out, int32_t N, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,6 +1,6 @@
 """What one policy evaluation costs (utils/evaluator.py), and what the metric kernel saves over torch expressions.
 
-    python tools/eval_bench.py [--task go2_flat] [--reps 3] [--robust] [--ladder] [--maneuvers] [--out profiles/eval_bench.json]
+    python tools/eval_bench.py [--task go2_flat] [--reps 3] [--robust] [--ladder] [--maneuvers] [--sensors] [--out profiles/eval_bench.json]
 
 Measures, on cuda:0, with the task's default `evaluation` section (1024 robots, 1 s + 10 s):
   * wall time of evaluate() run eagerly and with the captured chunk of steps replayed (simulator re-creation, capture and the final host copy included: it is what
@@ -13,6 +13,9 @@ back-to-back launches; the torch-expression comparison is left out.
 --ladder (a terrain task, e.g. --task go2): the same with evaluation.ladder on, plus go2nn_ladder_accumulate per back-to-back launch; again without the torch expressions.
 --maneuvers: the same with the default maneuvers in the scenarios' place (evaluation.maneuvers = DEFAULT_MANEUVERS), plus go2nn_maneuver_apply + go2nn_maneuver_accumulate per
 pair of back-to-back launches; again without the torch expressions.
+--sensors: a measurement of its own, ADDED to the JSON file under the key "sensors" (the file's other keys stay as they are): evaluate() run eagerly without and with the
+default sensor conditions (evaluation.sensors = DEFAULT_SENSORS), alternating, in this one session, best and median of --reps, and go2nn_sensor_apply (the frame kernel
+and its one-lane cursor launch) per back-to-back call on the evaluator's own buffers, by the method of the go2nn_eval_accumulate figure.
 Writes one JSON file and prints it."""
 import argparse
 import ctypes as C
@@ -28,7 +31,7 @@ sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 
 from go2_rl_gym_amd.envs import task_registry  # noqa: E402
-from go2_rl_gym_amd.utils.evaluator import DEFAULT_MANEUVERS, DEFAULT_PERTURBATIONS, EVAL_SOURCE, PolicyEvaluator  # noqa: E402
+from go2_rl_gym_amd.utils.evaluator import DEFAULT_MANEUVERS, DEFAULT_PERTURBATIONS, DEFAULT_SENSORS, EVAL_SOURCE, PolicyEvaluator  # noqa: E402
 from go2_rl_gym_amd.utils.helpers import class_to_dict  # noqa: E402
 
 
@@ -61,6 +64,46 @@ def timed(fn, n):
     return e0.elapsed_time(e1) * 1e3 / n, (time.perf_counter() - t0) * 1e6 / n          # device us, wall us per call
 
 
+def sensors_main(a):
+    """--sensors: the cost of the sensor model, next to the plain evaluation in the same session -> the "sensors" entry of the JSON file"""
+    env_cfg, train_cfg = task_registry.get_cfgs(a.task)
+    ev_cfg = class_to_dict(train_cfg.evaluation)
+    make = lambda sensors: PolicyEvaluator(env_cfg, dict(ev_cfg, sensors=sensors), task_class=task_registry.get_task_class(a.task), device="cuda:0")
+    evs = {"plain": make(None), "sensors": make([[n, dict(f)] for n, f in DEFAULT_SENSORS])}
+    from go2_rl_gym_amd.rsl_rl.modules import ActorCritic
+    torch.manual_seed(0)
+    ac = ActorCritic(45, 263, 12, **{k: v for k, v in class_to_dict(train_cfg.policy).items() if k in ("actor_hidden_dims", "critic_hidden_dims", "activation", "init_noise_std")}).to("cuda:0")
+    for ev in evs.values():
+        ev.evaluate(ac, use_graph=False)
+    ev = evs["sensors"]
+    sin = ev._sensor_in()
+    fn = lambda: ev._sensor_apply(sin)
+    timed(fn, 20)
+    dev_us, wall_us = timed(fn, 200)
+    entry = {"task": a.task, "device": torch.cuda.get_device_name(0), "num_envs": ev.num_envs, "steps": ev.warmup_steps + ev.steps, "conditions": [c[0] for c in ev.sensors],
+             "sensor_apply": {"device_us_per_call_back_to_back": dev_us, "host_us_per_call": wall_us, "launches_per_call": 2}}
+    if not a.kernel_only:
+        walls = {k: [] for k in evs}
+        for _ in range(a.reps):
+            for k, e in evs.items():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                e.evaluate(ac, use_graph=False)
+                walls[k].append((time.perf_counter() - t0) * 1e3)
+        entry["evaluate_wall_ms_eager"] = {k: {"best": min(w), "median": statistics.median(w)} for k, w in walls.items()}
+        out = {}
+        if os.path.exists(a.out):
+            with open(a.out) as f:
+                out = json.load(f)
+        out["sensors"] = entry
+        os.makedirs(os.path.dirname(a.out), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(out, f, indent=1)
+    print(json.dumps({"sensors": entry}))
+    for e in evs.values():
+        e.close()
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--task", default="go2_flat")
@@ -69,8 +112,11 @@ def main():
     p.add_argument("--robust", action="store_true")
     p.add_argument("--ladder", action="store_true")
     p.add_argument("--maneuvers", action="store_true")
+    p.add_argument("--sensors", action="store_true")
     p.add_argument("--out", default=os.path.join(ROOT, "profiles", "eval_bench.json"))
     a = p.parse_args()
+    if a.sensors:
+        return sensors_main(a)
     env_cfg, train_cfg = task_registry.get_cfgs(a.task)
     ev_cfg = class_to_dict(train_cfg.evaluation)
     if a.robust:
