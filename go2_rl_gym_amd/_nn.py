@@ -53,6 +53,10 @@ MANEUVER_FIELDS = ("commands", "base_lin_vel", "base_ang_vel", "projected_gravit
 SENSOR_KINDS = ("pass", "gyro", "gravity", "joint_pos", "joint_vel")
 SENSOR_SPEC_FIELDS = ("noise_mul", "gyro_bias", "gravity_bias", "joint_offset", "delay", "drop")
 GO2NN_SENSOR_MAX_DELAY, GO2NN_SENSOR_MAX_WIDTH, GO2NN_SENSOR_MAX_SPECS = 4, 64, 64
+# the Go2 tasks' 45 observation columns (envs/go2/go2_env.py): angular velocity, projected gravity, commands, joint positions, joint velocities, previous actions — what the
+# evaluator's sensor model and the training-time sensor randomisation (Go2nnSensorRand, fields in the struct's order below) both use as Go2nnSensorIn.kind
+GO2_OBS_KINDS = ["gyro"] * 3 + ["gravity"] * 3 + ["pass"] * 3 + ["joint_pos"] * 12 + ["joint_vel"] * 12 + ["pass"] * 12
+SENSOR_RAND_FIELDS = ("delay_lo", "delay_hi", "drop_lo", "drop_hi", "gyro_bias", "gravity_bias", "joint_offset", "env_offset")
 _cached = None
 
 
@@ -150,6 +154,11 @@ class Go2nnSensorIn(C.Structure):          # (within ABI 7)
                 ("seed", C.c_uint32)]
 
 
+class Go2nnSensorRand(C.Structure):          # (within ABI 7)
+    _fields_ = [("delay_lo", C.c_int32), ("delay_hi", C.c_int32), ("drop_lo", C.c_float), ("drop_hi", C.c_float), ("gyro_bias", C.c_float), ("gravity_bias", C.c_float),
+                ("joint_offset", C.c_float), ("env_offset", C.c_uint32)]
+
+
 def trace_env_ids(env_ids, num_envs):
     """the tracked robots of go2nn_trace_record as the kernel needs them -> int32 numpy [K], strictly increasing, each in [0, num_envs).  The kernel cannot report a bad
     index (it would read outside the buffers), so anything else raises here."""
@@ -232,6 +241,11 @@ def bind(path):
     lib.go2nn_sensor_state_bytes.argtypes = [C.c_int32, C.c_int32]
     lib.go2nn_sensor_begin.argtypes = [C.c_void_p, C.c_void_p]
     lib.go2nn_sensor_apply.argtypes = [C.POINTER(Go2nnSensorIn), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+    lib.go2nn_sensor_rand_check.argtypes = [C.POINTER(Go2nnSensorRand), C.c_void_p, C.c_int32]
+    lib.go2nn_sensor_rand_state_bytes.restype = C.c_int64
+    lib.go2nn_sensor_rand_state_bytes.argtypes = [C.c_int32, C.c_int32]
+    lib.go2nn_sensor_rand_begin.argtypes = [C.c_void_p, C.c_void_p]
+    lib.go2nn_sensor_rand_apply.argtypes = [C.POINTER(Go2nnSensorIn), C.POINTER(Go2nnSensorRand), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
     if lib.go2nn_abi_version() != GO2NN_ABI_VERSION:
         raise RuntimeError("%s: ABI version %d, expected %d" % (path, lib.go2nn_abi_version(), GO2NN_ABI_VERSION))
     return lib

@@ -27,7 +27,9 @@ _REWARD_KEY_ALIASES = {"feet_stumble": "stumble"}
 class LeggedRobot(BaseTask):
     _terrain_prebuilt = None      # a utils.terrain.Terrain to use instead of generating one (utils/evaluator.py recreates its simulator per evaluation and keeps the terrain on the host)
 
-    def __init__(self, cfg: LeggedRobotCfg, sim_params, physics_engine, sim_device, headless, lib=None, env_offset=0, num_envs_global=None):
+    _sensors = None               # the sensor randomisation's buffers (domain_rand.randomize_sensors; None: the policy reads the simulator's own observation)
+
+    def __init__(self, cfg: LeggedRobotCfg, sim_params, physics_engine, sim_device, headless, lib=None, env_offset=0, num_envs_global=None, nn=None):
         self.cfg = cfg
         self.sim_params = sim_params
         self.height_samples = None
@@ -38,6 +40,8 @@ class LeggedRobot(BaseTask):
         self._parse_cfg(self.cfg)
         super().__init__(self.cfg, sim_params, physics_engine, sim_device, headless, lib=lib)
         self._init_buffers()
+        if getattr(self.cfg.domain_rand, "randomize_sensors", False):
+            self._init_sensors(nn)
         self.init_done = True
         self.num_steps_per_env = 24          # hard-coded in the reference env (:58)
         self.reward_curriculum_configs = list(getattr(self.cfg.rewards, "curriculum_rewards", None) or [])
@@ -303,6 +307,71 @@ class LeggedRobot(BaseTask):
             self._level_groups = [("all", nr + 3)] + [(name, nr + 4 + KIND_NAMES.index(name)) for name in self.terrain.name2cols]
         self.add_noise = self.cfg.noise.add_noise
 
+    # ------------------------------------------------------------------ domain_rand.randomize_sensors
+    def _init_sensors(self, nn):
+        """Per-episode observation latency, dropped frames and constant gyro / gravity / encoder offsets between obs_buf and what step() returns (include/go2nn.h:
+        go2nn_sensor_rand_*; csrc/go2nn_sensor_rand.h).  nn: a go2nn library handle in the simulator's memory space (the tests hand in the host build); None loads the HIP one."""
+        from ..._nn import GO2_OBS_KINDS, SENSOR_KINDS, Go2nnSensorIn, Go2nnSensorRand, load_nn
+        d, D, N = self.cfg.domain_rand, int(self.num_obs), self.num_envs
+        if D != len(GO2_OBS_KINDS) or not hasattr(self, "_get_noise_scale_vec"):
+            raise ValueError("domain_rand.randomize_sensors: no observation layout for %s with %d observation columns (the Go2 layout of envs/go2/go2_env.py is covered)"
+                             % (type(self).__name__, D))
+        nn = load_nn() if nn is None else nn
+        if nn.go2nn_is_device_library() != self.lib.go2sim_is_device_library():
+            raise ValueError("domain_rand.randomize_sensors: the go2nn library and the simulator do not share a memory space")
+        lo, hi = d.sensor_delay_range
+        if int(lo) != lo or int(hi) != hi:
+            raise ValueError("domain_rand.sensor_delay_range = %r: whole policy steps" % (d.sensor_delay_range,))
+        r, o = Go2nnSensorRand(), self.cfg.normalization.obs_scales
+        r.delay_lo, r.delay_hi, r.drop_lo, r.drop_hi = int(lo), int(hi), float(d.sensor_drop_range[0]), float(d.sensor_drop_range[1])
+        r.gyro_bias, r.gravity_bias, r.joint_offset = float(d.sensor_gyro_bias) * float(o.ang_vel), float(d.sensor_gravity_bias), float(d.sensor_joint_offset) * float(o.dof_pos)
+        r.env_offset = self._env_offset & 0xFFFFFFFF
+        kind = np.asarray([SENSOR_KINDS.index(k) for k in GO2_OBS_KINDS], np.int32)
+        if nn.go2nn_sensor_rand_check(C.byref(r), C.c_void_p(kind.ctypes.data), D) != 0:
+            raise ValueError("domain_rand.randomize_sensors: %s" % nn.go2nn_last_error().decode())
+        dev, t = self.obs_buf.device, self.obs_buf
+        sn = self._sensors = {"nn": nn, "rand": r, "kind": torch.from_numpy(kind).to(dev), "pending": False}
+        sn["state"] = torch.zeros(int(nn.go2nn_sensor_rand_state_bytes(N, D)), dtype=torch.uint8, device=dev)
+        sn["delivered"] = torch.zeros(N, D, device=dev)
+        sn["also_fresh"] = torch.zeros(N, dtype=torch.uint8, device=dev)
+        a = sn["in"] = Go2nnSensorIn()
+        a.obs.p, a.obs.env_stride, a.obs.comp_stride = t.data_ptr(), t.stride(0), t.stride(1)
+        a.dones, a.scale, a.kind = self._buf["reset_buf"].data_ptr(), None, sn["kind"].data_ptr()
+        a.D, a.num_specs, a.clip, a.seed = D, 0, float(self.cfg.normalization.clip_observations), int(getattr(self.cfg, "seed", 1)) & 0xFFFFFFFF
+        print("[go2_rl_gym_amd] randomize_sensors: per episode, observation latency %d .. %d policy steps, dropped frames %g .. %g, offsets gyro %g rad/s, gravity %g, "
+              "joint position %g rad (the privileged observation stays exact)" % (r.delay_lo, r.delay_hi, r.drop_lo, r.drop_hi, d.sensor_gyro_bias, d.sensor_gravity_bias,
+                                                                                 d.sensor_joint_offset))
+
+    def _sensor_check(self, rc, what):
+        if rc != 0:
+            raise RuntimeError("%s failed: %s" % (what, self._sensors["nn"].go2nn_last_error().decode()))
+
+    def _sensor_apply(self, out):
+        """obs_buf -> out [N, num_obs] (a storage row or the delivered buffer) on the step's stream; envs reset from outside a step since the last call start a new episode"""
+        sn = self._sensors
+        fresh = C.c_void_p(sn["also_fresh"].data_ptr()) if sn["pending"] else None
+        self._sensor_check(sn["nn"].go2nn_sensor_rand_apply(C.byref(sn["in"]), C.byref(sn["rand"]), fresh, C.c_void_p(sn["state"].data_ptr()), C.c_void_p(out.data_ptr()),
+                                                            self.num_envs, self._stream()), "go2nn_sensor_rand_apply")
+        if sn["pending"]:
+            sn["also_fresh"].zero_()
+            sn["pending"] = False
+        return out
+
+    def get_observations(self):
+        return self.obs_buf if self._sensors is None else self._sensors["delivered"]
+
+    def reset(self):
+        """(base_task.py:82-86) with randomize_sensors the sensor state begins here: the frame of the zero-action step is its step 0"""
+        if self._sensors is None:
+            return super().reset()
+        self.reset_idx(torch.arange(self.num_envs, device=self.device))
+        sn = self._sensors
+        self._sensor_check(sn["nn"].go2nn_sensor_rand_begin(C.c_void_p(sn["state"].data_ptr()), self._stream()), "go2nn_sensor_rand_begin")
+        sn["also_fresh"].zero_()          # (step 0 refills every lane anyway)
+        sn["pending"] = False
+        obs, privileged_obs, _, _, _ = self.step(torch.zeros(self.num_envs, self.num_actions, device=self.device, requires_grad=False))
+        return obs, privileged_obs
+
     # the runner REPLACES this attribute (on_policy_runner.py:118): copy into the library's buffer instead
     @property
     def episode_length_buf(self):
@@ -352,7 +421,9 @@ class LeggedRobot(BaseTask):
         'time_outs' (ppo.py:107).  CONTRACT of the redirected form: obs_buf / privileged_obs_buf are NOT written by such a step (the
         rows handed in are), so get_observations() is stale until a plain step() or the last step of the rollout, which has no next row.
         A destination this call cannot write in place (other device, dtype or stride) makes it fall back to the plain step(); the
-        caller then sees extras without 'transition_stored' and does its own copies."""
+        caller then sees extras without 'transition_stored' and does its own copies.
+        With domain_rand.randomize_sensors the simulator writes obs_buf in either form, and what is returned — the delivered buffer, or the `obs_out` row — is written by
+        go2nn_sensor_rand_apply: the frame the robot's sensors would have delivered (_init_sensors)."""
         a = actions
         if a.dtype != torch.float32 or not a.is_contiguous() or str(a.device) != str(self.obs_buf.device):
             a = a.to(device=self.obs_buf.device, dtype=torch.float32).contiguous()
@@ -366,7 +437,8 @@ class LeggedRobot(BaseTask):
             _abi.check(self.lib, self.lib.go2sim_step(self.handle, C.c_void_p(a.data_ptr()), self._stream()), "go2sim_step")
             self._publish_extras()
             self.extras.pop("transition_stored", None)
-            return self.obs_buf, self.privileged_obs_buf, self.rew_buf, self.reset_buf, self.extras
+            obs = self.obs_buf if self._sensors is None else self._sensor_apply(self._sensors["delivered"])
+            return obs, self.privileged_obs_buf, self.rew_buf, self.reset_buf, self.extras
         o = self.abi.StepOutputs()
         fp, bp = C.POINTER(self.abi.real), C.POINTER(C.c_uint8)
         keep = []
@@ -374,6 +446,8 @@ class LeggedRobot(BaseTask):
             t = rollout.get(name)
             if name == "values" and not self.cfg.env.send_timeouts:
                 t = None                                        # no 'time_outs' in infos -> no bootstrap (ppo.py:107-108)
+            if name == "obs_out" and self._sensors is not None:
+                t = None                                        # the simulator writes obs_buf; the sensor kernel below writes the storage row in the copy's place
             if t is not None:
                 keep.append(t)
                 setattr(o, name, C.cast(C.c_void_p(t.data_ptr()), ctype))
@@ -385,6 +459,8 @@ class LeggedRobot(BaseTask):
         self._publish_extras(copied=True)
         self.extras["transition_stored"] = rollout.get("rewards_out") is not None and rollout.get("dones_out") is not None
         obs = rollout["obs_out"] if rollout.get("obs_out") is not None else self.obs_buf
+        if self._sensors is not None:
+            obs = self._sensor_apply(rollout["obs_out"] if rollout.get("obs_out") is not None else self._sensors["delivered"])
         priv = rollout["priv_out"] if rollout.get("priv_out") is not None else self.privileged_obs_buf
         return obs, priv, self.rew_buf, self.reset_buf, self.extras
 
@@ -403,6 +479,9 @@ class LeggedRobot(BaseTask):
             self._reset_ids = ids                               # keep the id tensor alive until the enqueued kernels have run
             ptr = C.c_void_p(ids.data_ptr())
             _abi.check(self.lib, self.lib.go2sim_reset_idx(self.handle, ptr, int(ids.numel()), self._stream()), "go2sim_reset_idx")
+            if self._sensors is not None:                       # a new episode for these robots at the next sensor step
+                self._sensors["also_fresh"][ids.long()] = 1
+                self._sensors["pending"] = True
         self._publish_extras()
 
     def _publish_extras(self, copied=False):

@@ -134,6 +134,12 @@ class LeggedRobotCfg(BaseConfig):
         max_push_vel_xy = 0.4
         max_push_ang_vel = 0.6
         randomize_action_delay = False
+        randomize_sensors = False        # per episode: observation latency, dropped frames, constant gyro / gravity / encoder offsets (include/go2nn.h: go2nn_sensor_rand_*); the privileged observation stays exact
+        sensor_delay_range = [0, 2]      # policy steps, inclusive, at most 4
+        sensor_drop_range = [0.0, 0.2]   # probability that a whole frame is lost: the proprioceptive columns then repeat what was delivered last
+        sensor_gyro_bias = 0.1           # [rad/s] half-width of the episode's constant offset per column; 0: none
+        sensor_gravity_bias = 0.0
+        sensor_joint_offset = 0.05       # [rad]
 
     class rewards:
         class scales:

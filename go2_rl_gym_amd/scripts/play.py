@@ -26,6 +26,7 @@ def play(args, steps=None, log_root="default", export_policy=None):
     env_cfg.terrain.curriculum = False
     env_cfg.noise.add_noise = False
     dr = env_cfg.domain_rand
+    dr.randomize_sensors = False          # (like the noise: play shows the policy on the simulator's own observation; evaluate.py --sensors scores the other case)
     dr.randomize_friction = dr.push_robots = dr.randomize_base_mass = dr.randomize_link_mass = False
     dr.randomize_base_com = dr.randomize_pd_gains = dr.randomize_motor_zero_offset = False
     env_cfg.env.test = True

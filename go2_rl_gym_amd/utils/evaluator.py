@@ -72,7 +72,7 @@ from .. import _abi
 from .._nn import (EVAL_FIELDS, EVAL_METRICS, GO2NN_EVAL_NUM, GO2NN_RNN_GRU, GO2NN_RNN_LSTM, GO2NN_ROBUST_ACC_NUM, GO2NN_ROBUST_MAX_SPECS, GO2NN_ROBUST_NUM, ROBUST_FIELDS, ROBUST_MASK,
                    GO2NN_LADDER_NUM, GO2NN_LADDER_OUT_NUM, LADDER_FIELDS, LADDER_OUT, GO2NN_MANEUVER_ACC_NUM, GO2NN_MANEUVER_MAX_SEGS, GO2NN_MANEUVER_MAX_SPECS, GO2NN_MANEUVER_NUM,
                    MANEUVER_FIELDS, MANEUVER_OUT, Go2nnEvalIn, Go2nnFwdJob, Go2nnLadderIn, Go2nnManeuverIn, Go2nnManeuverSpec, Go2nnMlpIO, Go2nnRnnCellJob, Go2nnRobustIn,
-                   Go2nnRobustSpec, PackedMlp, GO2NN_SENSOR_MAX_DELAY, GO2NN_SENSOR_MAX_SPECS, SENSOR_KINDS, Go2nnSensorIn, Go2nnSensorSpec)
+                   Go2nnRobustSpec, PackedMlp, GO2NN_SENSOR_MAX_DELAY, GO2NN_SENSOR_MAX_SPECS, GO2_OBS_KINDS, SENSOR_KINDS, Go2nnSensorIn, Go2nnSensorSpec)
 from .helpers import class_to_dict
 
 DEFAULT_SCENARIOS = [["forward_1.0", 1.0, 0.0, 0.0], ["forward_2.0", 2.0, 0.0, 0.0], ["backward_1.0", -1.0, 0.0, 0.0], ["lateral_0.5", 0.0, 0.5, 0.0],
@@ -96,8 +96,6 @@ MANEUVER_KEYS = ("switches", "switch_falls", "settled", "settle_time_s", "window
 DEFAULT_SENSORS = [["nominal", {}], ["noise_1.0", {"noise": 1.0}], ["noise_3.0", {"noise": 3.0}], ["gyro_bias_0.1", {"gyro_bias": 0.1}],
                    ["joint_offset_0.05", {"joint_offset": 0.05}], ["delay_1", {"delay": 1}], ["delay_2", {"delay": 2}], ["drop_0.2", {"drop": 0.2}]]
 SENSOR_FIELDS = ("noise", "gyro_bias", "gravity_bias", "joint_offset", "delay", "drop")
-# the Go2 observation (envs/go2/go2_env.py): base angular velocity 3, projected gravity 3, commands 3, joint positions 12, joint velocities 12, previous actions 12
-GO2_OBS_KINDS = ["gyro"] * 3 + ["gravity"] * 3 + ["pass"] * 3 + ["joint_pos"] * 12 + ["joint_vel"] * 12 + ["pass"] * 12
 MAX_CHUNK = 50
 # The accumulate kernel runs AFTER the env step, when the simulator has already rolled its action history (last_actions = this step's actions): the previous step's
 # actions — the kernel's `last_actions` input — are then in the simulator's last_last_actions buffer.

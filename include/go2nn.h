@@ -581,6 +581,47 @@ int go2nn_sensor_begin(void* state, void* stream);               /* cursor = 0; 
 /* GO2NN_EINVAL for null pointers, N < 1, D or num_specs outside [1, 64], a stride < 1, clip <= 0 (or NaN). */
 int go2nn_sensor_apply(const Go2nnSensorIn* in, const Go2nnSensorSpec* specs, const int32_t* sensor_of_env, void* state, float* out, int32_t N, void* stream);
 
+/* ---- TRAINING under randomised sensors: latency, dropped frames and constant offsets redrawn per robot and per EPISODE (domain_rand.randomize_sensors,
+ * go2_rl_gym_amd/envs/base/legged_robot.py; csrc/go2nn_sensor_rand.h).
+ * ADDED WITHIN ABI 7: four new entry points, nothing existing changes, GO2NN_ABI_VERSION stays 7.
+ * A training step is { policy(delivered), go2sim_step, go2nn_sensor_rand_apply(obs_buf -> the next storage row) }: two plain launches per step, capturable, one lane per
+ * observation float, no atomics.  The privileged observation is not touched.  No white noise is added: the simulator's own noise.add_noise does that.
+ * The layout is a Go2nnSensorIn, of which `scale` and `num_specs` are NOT read (scale may be NULL).  The ranges are one Go2nnSensorRand, passed to the kernel by value:
+ *   delay_lo, delay_hi       the episode's latency of the proprioceptive columns in policy steps, an integer of [delay_lo, delay_hi] (inclusive)
+ *   drop_lo, drop_hi         the episode's probability that a whole frame is lost, uniform in [drop_lo, drop_hi)
+ *   gyro_bias, gravity_bias, joint_offset   half-width of the episode's constant per-(env, column) offset, in OBSERVATION units (as in Go2nnSensorSpec)
+ *   env_offset               the global id of env 0 of this rank: ranks draw different conditions, and a robot's draws do not depend on how the envs are split
+ * The state: ONE allocation of go2nn_sensor_rand_state_bytes(N, D) bytes in the buffers' memory space: the int32 cursor (steps since go2nn_sensor_rand_begin) in the first
+ * 256 bytes, the ring [R][N][D] of the simulator's frames, R = GO2NN_SENSOR_MAX_DELAY + 1, held [N][D], the frame last delivered, and start [N][D] (int32), the cursor value
+ * at which the lane's episode began.  Nothing of it is read before step 0 has written it.
+ * go2nn_sensor_rand_apply, per (env e, column c), with s = the cursor, g = env_offset + e, x = obs[e, c]:
+ *   1. fresh = (s == 0 or dones[e] or (also_fresh and also_fresh[e])).  If fresh: every ring slot of the lane = x and start = s; otherwise ring[s % R] = x.  s0 = start.
+ *   2. a PASS column: out = held = x, the BITS.
+ *   3. the episode's draws, (u_d, u_p) = words (0, 1) under key (seed, 4), counter (g, 0, s0, 0):
+ *        delay = delay_lo + min((int)(u_d (delay_hi - delay_lo + 1)), delay_hi - delay_lo)     (one fp32 product, truncated)
+ *        p     = drop_lo + u_p (drop_hi - drop_lo)                                             (fp32)
+ *   4. the frame is LOST when not fresh, p > 0 and u < p with u = word 0 under key (seed, 6), counter (g, 0, s, 0): out = held, and held stays as it is.
+ *   5. src = x if fresh or delay == 0, otherwise ring[(s - delay) % R]: the refill at a reset makes this the frame of step max(s - delay, s0).
+ *   6. mag = gyro_bias / gravity_bias / joint_offset by the column's kind, 0 for joint velocities:
+ *        mag == 0:   out = held = src, the BITS (no add, no clamp)
+ *        otherwise:  out = held = clamp(src + (2 u - 1) mag, -clip, clip) with u = word 0 under key (seed, 5), counter (g, c, s0, 0)
+ * `out` [N, D] is row-major and must not be the input.  Then the cursor is advanced by a second, one-lane launch on the same stream, so a captured pair advances on every
+ * replay.  The uniforms: u = (x >> 8) 2^-24 with x a word of Philox4x32-10; tags 4 .. 6 keep these streams apart from the evaluator's 1 .. 3. */
+typedef struct Go2nnSensorRand {
+  int32_t delay_lo, delay_hi;          /* policy steps, inclusive */
+  float drop_lo, drop_hi;              /* per-episode drop probability */
+  float gyro_bias, gravity_bias, joint_offset;
+  uint32_t env_offset;                 /* global id of env 0 on this rank */
+} Go2nnSensorRand;
+/* Host-side check of the ranges and the layout in HOST memory: GO2NN_EINVAL with a message naming the field for a null pointer, D outside [1, 64], kind[c] outside 0 .. 4,
+ * anything but 0 <= delay_lo <= delay_hi <= GO2NN_SENSOR_MAX_DELAY and 0 <= drop_lo <= drop_hi < 1, a magnitude (gyro_bias, gravity_bias, joint_offset) negative or not finite. */
+int go2nn_sensor_rand_check(const Go2nnSensorRand* host_r, const int32_t* host_kind, int32_t D);
+int64_t go2nn_sensor_rand_state_bytes(int32_t N, int32_t D);          /* 0 for N < 1 or D outside [1, 64] */
+int go2nn_sensor_rand_begin(void* state, void* stream);               /* cursor = 0; ring, held and start are left as they are (step 0 fills them) */
+/* also_fresh: uint8 [N] in the buffers' memory space or NULL — envs that were reset from outside a step since the last call.  r is read on the host (a HOST pointer) and
+ * passed by value.  GO2NN_EINVAL for null pointers (also_fresh aside), N < 1, D outside [1, 64], a stride < 1, clip <= 0 (or NaN), N * D too large, ranges the check refuses. */
+int go2nn_sensor_rand_apply(const Go2nnSensorIn* in, const Go2nnSensorRand* r, const uint8_t* also_fresh, void* state, float* out, int32_t N, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
