@@ -40,6 +40,17 @@ LADDER_OUT = ("n", "cleared", "fell", "timed_out", "clear_steps", "progress")
 LADDER_STATES = ("running", "cleared", "fell", "timed_out")
 GO2NN_LADDER_NUM, GO2NN_LADDER_OUT_NUM = len(LADDER_ROWS), len(LADDER_OUT)
 LADDER_FIELDS = ("root_states", "reset_buf", "time_out_buf")
+# the evaluator's gait scores: the per-env rows of the table [GO2NN_GAIT_NUM, N], the rows of one foot (state first, then the accumulators go2nn_gait_reduce sums) and the
+# per-foot columns of the reduce's output, each in the order of its enum GO2NN_GAIT_* of include/go2nn.h; the table is the env rows, then GAIT_FOOT_ROWS per foot; the output
+# is "n", then GAIT_OUT_FOOT per foot, then support0 .. support4 and diagonal; and the buffers of Go2nnGaitIn in the struct's order
+GAIT_ENV_ROWS = ("step", "used", "support0", "support1", "support2", "support3", "support4", "diagonal")
+GAIT_FOOT_ROWS = ("prev", "phase_start", "last_td", "swing_max", "lift_z", "contact", "slip_sum", "touchdowns", "stride_steps", "strides", "stance_steps", "stances",
+                  "swing_steps", "swings", "height_sum", "clearance_sum")
+GAIT_OUT_FOOT = ("used",) + GAIT_FOOT_ROWS[GAIT_FOOT_ROWS.index("contact"):]
+GO2NN_GAIT_FOOT0, GO2NN_GAIT_NUM = len(GAIT_ENV_ROWS), len(GAIT_ENV_ROWS) + 4 * len(GAIT_FOOT_ROWS)
+GO2NN_GAIT_OUT_SUPPORT0 = 1 + 4 * len(GAIT_OUT_FOOT)
+GO2NN_GAIT_OUT_DIAGONAL, GO2NN_GAIT_OUT_NUM = GO2NN_GAIT_OUT_SUPPORT0 + 5, GO2NN_GAIT_OUT_SUPPORT0 + 6
+GAIT_FIELDS = ("rigid_body_states", "contact_forces", "reset_buf")
 # the evaluator's command maneuvers: the rows of the table [GO2NN_MANEUVER_NUM, N] in the order of the enum GO2NN_MANEUVER_* of include/go2nn.h (per-env state first, then
 # the accumulators go2nn_maneuver_reduce sums; its output columns are those plus "n"), and the buffers of Go2nnManeuverIn in the struct's order
 MANEUVER_ROWS = ("step", "open", "ok_run", "is_settled", "is_fell", "peak_tilt", "switches", "switch_falls", "settled", "settle_steps", "win_steps", "win_lin_err",
@@ -133,6 +144,21 @@ class Go2nnRobustIn(C.Structure):          # (within ABI 7)
 
 class Go2nnLadderIn(C.Structure):          # (within ABI 7)
     _fields_ = [(k, Go2nnEvalField) for k in LADDER_FIELDS] + [("dist2_thr", C.c_float), ("pad_", C.c_int32)]
+
+
+class Go2nnGaitIn(C.Structure):          # (within ABI 7)
+    _fields_ = [(k, Go2nnEvalField) for k in GAIT_FIELDS] + [("rigid_body_stride", C.c_int32), ("contact_body_stride", C.c_int32), ("foot_body", C.c_int32 * 4),
+                                                             ("contact_threshold", C.c_float), ("diagonal_mask", C.c_int32 * 2), ("pad_", C.c_int32)]
+
+
+def gait_row(foot, name):
+    """the table row of `name` (GAIT_FOOT_ROWS) of foot `foot` (in foot_body order)"""
+    return GO2NN_GAIT_FOOT0 + foot * len(GAIT_FOOT_ROWS) + GAIT_FOOT_ROWS.index(name)
+
+
+def gait_out_col(foot, name):
+    """the column of `name` (GAIT_OUT_FOOT) of foot `foot` in go2nn_gait_reduce's output"""
+    return 1 + foot * len(GAIT_OUT_FOOT) + GAIT_OUT_FOOT.index(name)
 
 
 class Go2nnManeuverSpec(C.Structure):          # (within ABI 7)
@@ -231,6 +257,9 @@ def bind(path):
     lib.go2nn_ladder_begin.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
     lib.go2nn_ladder_accumulate.argtypes = [C.POINTER(Go2nnLadderIn), C.c_void_p, C.c_int32, C.c_void_p]
     lib.go2nn_ladder_reduce.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p]
+    lib.go2nn_gait_begin.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
+    lib.go2nn_gait_accumulate.argtypes = [C.POINTER(Go2nnGaitIn), C.c_void_p, C.c_int32, C.c_void_p]
+    lib.go2nn_gait_reduce.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
     lib.go2nn_maneuver_check_specs.argtypes = [C.c_void_p, C.c_int32]
     lib.go2nn_maneuver_begin.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
     lib.go2nn_maneuver_apply.argtypes = [C.POINTER(Go2nnManeuverIn), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]

@@ -300,6 +300,8 @@ class LeggedRobotCfgPPO(BaseConfig):
         maneuver_thr_lin = 0.3  # [m/s] ... the linear velocity error (recover_thr's convention, not a measurement)
         maneuver_thr_ang = 0.3  # [rad/s] ... and the yaw rate error
         sensors = None          # None: the policy reads the simulator's exact, current observation.  A list of [name, {field: value}] (fields: noise [x the task's noise], gyro_bias [rad/s], gravity_bias, joint_offset [rad], delay [policy steps, <= 4], drop [probability]); --sensors: utils/evaluator.py DEFAULT_SENSORS
+        gait = False            # True (--gait): follow every robot's feet on the device and report duty factor, stride frequency, stance / swing time, slip, swing height and clearance, touchdown rate and the support pattern per group (utils/evaluator.py GAIT_KEYS); an add-on like `record`, it works next to every mode above
+        gait_contact_threshold = 1.0  # [N] a foot is in contact when its vertical contact force is > this (the reference's `> 1 N` rule, legged_robot.py _reward_feet_air_time; utils/recorder.py gait_summary's default)
 
 
 class LeggedRobotCfgCTS(BaseConfig):
@@ -381,6 +383,8 @@ class LeggedRobotCfgCTS(BaseConfig):
         maneuver_thr_lin = 0.3  # [m/s] ... the linear velocity error (recover_thr's convention, not a measurement)
         maneuver_thr_ang = 0.3  # [rad/s] ... and the yaw rate error
         sensors = None          # None: the policy reads the simulator's exact, current observation.  A list of [name, {field: value}] (fields: noise [x the task's noise], gyro_bias [rad/s], gravity_bias, joint_offset [rad], delay [policy steps, <= 4], drop [probability]); --sensors: utils/evaluator.py DEFAULT_SENSORS
+        gait = False            # True (--gait): follow every robot's feet on the device and report duty factor, stride frequency, stance / swing time, slip, swing height and clearance, touchdown rate and the support pattern per group (utils/evaluator.py GAIT_KEYS); an add-on like `record`, it works next to every mode above
+        gait_contact_threshold = 1.0  # [N] a foot is in contact when its vertical contact force is > this (the reference's `> 1 N` rule, legged_robot.py _reward_feet_air_time; utils/recorder.py gait_summary's default)
 
 
 class LeggedRobotCfgMoECTS(LeggedRobotCfgCTS):

@@ -13,6 +13,9 @@ switch_falls, settle_time_s, window_lin_vel_err, window_ang_vel_err (lower is be
 --sensors scores the default sensor conditions (noise, gyro bias, joint offset, one and two steps of latency, dropped frames: utils/evaluator.py DEFAULT_SENSORS) next to
 the scenarios; the overall figures are then means over the conditions' robots, so --all_checkpoints --sensors --metric lin_vel_err names the checkpoint that tracks best
 across all of them.
+--gait also scores how the robots walk (utils/evaluator.py GAIT_KEYS), next to any of the modes above; --metric then also takes the pooled gait figures: slip_speed and
+touchdowns_per_s count as lower is better, trot_share and swing_clearance as higher is better, so --all_checkpoints --gait --metric slip_speed names the checkpoint whose
+feet drag least.
 --record N also records N robots of every (terrain x scenario) group and writes eval_results/trace_<checkpoint number>.npz into the run's directory."""
 import json
 import math
@@ -26,7 +29,7 @@ from go2_rl_gym_amd.utils.evaluator import PolicyEvaluator, format_table, result
 from go2_rl_gym_amd.utils.helpers import _checkpoint_number, get_load_path
 from go2_rl_gym_amd.utils.task_registry import ROOT_DIR, task_registry
 
-HIGHER_IS_BETTER = ("survival", "speed_along_cmd", "recovered", "mean_level_cleared", "cleared", "settled")
+HIGHER_IS_BETTER = ("survival", "speed_along_cmd", "recovered", "mean_level_cleared", "cleared", "settled", "trot_share", "swing_clearance")
 
 
 def _own_flags(argv):
@@ -88,6 +91,8 @@ def evaluate(argv=None, log_root="default", env_kwargs=None, evaluator_kwargs=No
             rows[-1]["maneuvers"] = res["maneuvers"]
         if res.get("sensors") is not None:
             rows[-1]["sensors"] = res["sensors"]
+        if res.get("gait") is not None:
+            rows[-1]["gait"] = {"overall": res["gait"]["overall"], "groups": res["gait"]["groups"]}
         if res.get("ladder_summary") is not None:
             rows[-1]["ladder_summary"] = res["ladder_summary"]
             import yaml

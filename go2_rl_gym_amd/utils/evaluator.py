@@ -57,6 +57,17 @@ like the perturbations: cell index = (terrain * S + scenario) * P + condition.  
 fed the delivered frames too, and the metrics still read the simulator's true state.  No reduce of its own: go2nn_eval_reduce over the cells gives RESULT_KEYS per condition.
 With `sensors = None` nothing of this is allocated or launched.
 
+How the robot walks: with `evaluation.gait` (--gait) every robot's feet are followed too — an add-on like `record`, not an axis: it splits nothing and works in the plain
+evaluation and next to perturbations, ladder, maneuvers and sensors.  A step gains ONE launch after go2nn_eval_accumulate, inside the captured chunk,
+    { ..., go2sim_step, ..., go2nn_eval_accumulate, ..., go2nn_gait_accumulate }
+(csrc/go2nn_gait.h; the per-foot rule — utils/recorder.py gait_summary's, on the vertical contact force > `gait_contact_threshold` — is in include/go2nn.h) and the end one
+go2nn_gait_reduce over the finest cells the mode has.  The cells' rows are summed on the host in fp64 for every partition the mode reports, and the figures GAIT_KEYS are
+POOLED RATIOS over a partition's robots (sums of counts / sums of counts), not means of per-robot means, NaN where the denominator is 0: `duty_factor` (contact / used
+frames), `stride_frequency` [Hz], `stance_time`, `swing_time` [s] (complete phases only), `slip_speed` [m/s] (horizontal foot speed in contact), `swing_height` [m, world z],
+`swing_clearance` [m] (a swing's highest point above the foot's last contact frame), `touchdowns_per_s`, each per foot (`<key>/FL` ...) and over the four feet, and the
+support pattern: `trot_share` (frames on exactly one diagonal pair), `flight_share` (no foot down), `mean_feet_in_contact`.  With `gait = False` nothing of this is loaded,
+allocated or launched.
+
 Isolated: nothing of the training env, the model, the optimizer or torch's generators is written; policy state the evaluation needs (the CTS observation history, the
 recurrent memory's hidden state) lives in buffers of the evaluator."""
 import copy
@@ -72,7 +83,8 @@ from .. import _abi
 from .._nn import (EVAL_FIELDS, EVAL_METRICS, GO2NN_EVAL_NUM, GO2NN_RNN_GRU, GO2NN_RNN_LSTM, GO2NN_ROBUST_ACC_NUM, GO2NN_ROBUST_MAX_SPECS, GO2NN_ROBUST_NUM, ROBUST_FIELDS, ROBUST_MASK,
                    GO2NN_LADDER_NUM, GO2NN_LADDER_OUT_NUM, LADDER_FIELDS, LADDER_OUT, GO2NN_MANEUVER_ACC_NUM, GO2NN_MANEUVER_MAX_SEGS, GO2NN_MANEUVER_MAX_SPECS, GO2NN_MANEUVER_NUM,
                    MANEUVER_FIELDS, MANEUVER_OUT, Go2nnEvalIn, Go2nnFwdJob, Go2nnLadderIn, Go2nnManeuverIn, Go2nnManeuverSpec, Go2nnMlpIO, Go2nnRnnCellJob, Go2nnRobustIn,
-                   Go2nnRobustSpec, PackedMlp, GO2NN_SENSOR_MAX_DELAY, GO2NN_SENSOR_MAX_SPECS, GO2_OBS_KINDS, SENSOR_KINDS, Go2nnSensorIn, Go2nnSensorSpec)
+                   Go2nnRobustSpec, PackedMlp, GAIT_FIELDS, GAIT_OUT_FOOT, GO2NN_GAIT_NUM, GO2NN_GAIT_OUT_DIAGONAL, GO2NN_GAIT_OUT_NUM, GO2NN_GAIT_OUT_SUPPORT0, Go2nnGaitIn,
+                   gait_out_col, GO2NN_SENSOR_MAX_DELAY, GO2NN_SENSOR_MAX_SPECS, GO2_OBS_KINDS, SENSOR_KINDS, Go2nnSensorIn, Go2nnSensorSpec)
 from .helpers import class_to_dict
 
 DEFAULT_SCENARIOS = [["forward_1.0", 1.0, 0.0, 0.0], ["forward_2.0", 2.0, 0.0, 0.0], ["backward_1.0", -1.0, 0.0, 0.0], ["lateral_0.5", 0.0, 0.5, 0.0],
@@ -96,6 +108,11 @@ MANEUVER_KEYS = ("switches", "switch_falls", "settled", "settle_time_s", "window
 DEFAULT_SENSORS = [["nominal", {}], ["noise_1.0", {"noise": 1.0}], ["noise_3.0", {"noise": 3.0}], ["gyro_bias_0.1", {"gyro_bias": 0.1}],
                    ["joint_offset_0.05", {"joint_offset": 0.05}], ["delay_1", {"delay": 1}], ["delay_2", {"delay": 2}], ["drop_0.2", {"drop": 0.2}]]
 SENSOR_FIELDS = ("noise", "gyro_bias", "gravity_bias", "joint_offset", "delay", "drop")
+# pooled over a partition's robots: per foot ("<key>/<foot>") and over the four feet, then the support pattern
+GAIT_FOOT_KEYS = ("duty_factor", "stride_frequency", "stance_time", "swing_time", "slip_speed", "swing_height", "swing_clearance", "touchdowns_per_s")
+GAIT_PATTERN_KEYS = ("trot_share", "flight_share", "mean_feet_in_contact")
+GAIT_KEYS = GAIT_FOOT_KEYS + GAIT_PATTERN_KEYS
+DIAGONAL_PAIRS = (("FL", "RR"), ("FR", "RL"))
 MAX_CHUNK = 50
 # The accumulate kernel runs AFTER the env step, when the simulator has already rolled its action history (last_actions = this step's actions): the previous step's
 # actions — the kernel's `last_actions` input — are then in the simulator's last_last_actions buffer.
@@ -350,6 +367,9 @@ class PolicyEvaluator:
             self._build_ladder()
         if self.maneuvers is not None:
             self._build_maneuvers()
+        self.gait = bool(_get(evaluation, "gait", False))
+        if self.gait:
+            self._build_gait()
         self.dof_limits = self.env.dof_pos_limits.contiguous().clone()
         self._policy, self._policy_of = None, None
         self.recorder = None
@@ -596,6 +616,38 @@ class PolicyEvaluator:
             print("[go2_rl_gym_amd] evaluation: %d of %d (terrain x scenario x sensor condition) cells have fewer than 4 robots (smallest: %d); raise evaluation.num_envs"
                   % (int((sizes < 4).sum()), self.num_cells, int(sizes.min())))
 
+    def _build_gait(self):
+        """the gait scorer's device side: the per-env table, the reduce output per cell, the feet in foot_body order and the two diagonal pairs among them by NAME"""
+        env = self.env
+        self.gait_threshold = float(_get(self.ev, "gait_contact_threshold", 1.0))
+        if not (math.isfinite(self.gait_threshold) and self.gait_threshold >= 0.0):
+            raise ValueError("evaluation.gait_contact_threshold: a finite force >= 0 [N], got %r" % (_get(self.ev, "gait_contact_threshold"),))
+        self.gait_feet = [int(i) for i in env.feet_indices.tolist()]
+        self.foot_names = [str(env.body_names[i]).replace("_foot", "") for i in self.gait_feet]
+        masks = []
+        for pair in DIAGONAL_PAIRS:
+            at = [[f for f, n in enumerate(self.foot_names) if n.upper().startswith(leg)] for leg in pair]
+            if len(self.gait_feet) != 4 or any(len(a) != 1 for a in at):
+                raise ValueError("evaluation.gait: the feet %r do not name one FL, FR, RL and RR foot each" % (self.foot_names,))
+            masks.append((1 << at[0][0]) | (1 << at[1][0]))
+        self.gait_diagonal = masks
+        self.gtable = torch.zeros(GO2NN_GAIT_NUM, self.num_envs, device=self.device)
+        self.gout = torch.zeros(self.num_cells, GO2NN_GAIT_OUT_NUM, dtype=torch.float64, device=self.device)
+        sizes = np.bincount(self.cell_host, minlength=self.num_cells)
+        if sizes.min() < 4 and self.perturbations is None and self.sensors is None and not self.ladder and self.maneuvers is None:          # (those modes say it of the same cells themselves)
+            print("[go2_rl_gym_amd] evaluation: %d of %d (terrain x scenario) groups have fewer than 4 robots (smallest: %d) for the gait figures; raise evaluation.num_envs"
+                  % (int((sizes < 4).sum()), self.num_cells, int(sizes.min())))
+
+    def _gait_in(self):
+        """the gait kernel's view of the simulator's buffers (as TrajectoryRecorder.bind: component and body strides of the two per-body fields)"""
+        b, a = self.env._buf, Go2nnGaitIn()
+        for name in GAIT_FIELDS:
+            t, f = b[name], getattr(a, name)
+            f.p, f.env_stride, f.comp_stride = t.data_ptr(), t.stride(0), (t.stride(t.dim() - 1) if t.dim() > 1 else 0)
+        a.rigid_body_stride, a.contact_body_stride = b["rigid_body_states"].stride(1), b["contact_forces"].stride(1)
+        a.foot_body[:], a.diagonal_mask[:], a.contact_threshold = self.gait_feet, self.gait_diagonal, self.gait_threshold
+        return a
+
     def _sensor_in(self):
         """the sensor kernel's view of the current simulator: its observation and reset flags, and the evaluator's own layout tensors"""
         t, a = self.env.obs_buf, Go2nnSensorIn()
@@ -661,10 +713,10 @@ class PolicyEvaluator:
         return a
 
     # ------------------------------------------------------------------ one env step of the evaluation (pure enqueue)
-    def _step(self, pol, ein, rin=None, k=None, lin=None, min_=None, sin=None):
+    def _step(self, pol, ein, rin=None, k=None, lin=None, min_=None, sin=None, gin=None):
         """rin: the perturbation kernels' input (None without perturbations);  k: the step's index in an eager run (None inside a capture: no callback there);
         lin: the ladder kernel's input (None without the ladder);  min_: the maneuver kernels' input (None without maneuvers);  sin: the sensor kernel's input (None without
-        sensors: the policy then reads the simulator's observation itself)"""
+        sensors: the policy then reads the simulator's observation itself);  gin: the gait kernel's input (None without gait)"""
         env = self.env
         obs = env.obs_buf if sin is None else self.delivered
         actions = pol.act(obs)
@@ -688,6 +740,8 @@ class PolicyEvaluator:
             self._robust(self.nn.go2nn_robust_accumulate, "go2nn_robust_accumulate", rin)
         if lin is not None:
             self._check(self.nn.go2nn_ladder_accumulate(C.byref(lin), C.c_void_p(self.ltable.data_ptr()), self.num_envs, self._stream()), "go2nn_ladder_accumulate")
+        if gin is not None:
+            self._check(self.nn.go2nn_gait_accumulate(C.byref(gin), C.c_void_p(self.gtable.data_ptr()), self.num_envs, self._stream()), "go2nn_gait_accumulate")
         if self.recorder is not None:
             self.recorder.record()
         pol.after_step(obs, env._buf["reset_buf"])
@@ -697,15 +751,15 @@ class PolicyEvaluator:
         if self.recorder is not None:
             self.recorder.clear()
 
-    def _run_eager(self, pol, ein, rin, lin=None, min_=None, sin=None):
+    def _run_eager(self, pol, ein, rin, lin=None, min_=None, sin=None, gin=None):
         for k in range(self.warmup_steps + self.steps):
             if k == self.warmup_steps:
                 self._clear()
-            self._step(pol, ein, rin, k, lin, min_, sin)
+            self._step(pol, ein, rin, k, lin, min_, sin, gin)
             if self.step_callback is not None:
                 self.step_callback(self, k, k >= self.warmup_steps)
 
-    def _run_graph(self, pol, ein, rin, lin=None, min_=None, sin=None):
+    def _run_graph(self, pol, ein, rin, lin=None, min_=None, sin=None, gin=None):
         """capture `chunk` steps on this evaluation's simulator, replay them for the whole horizon -> False if the capture failed (nothing has run then)"""
         from ..rsl_rl.algorithms._graph import no_gc, strict_graphs
         torch.cuda.synchronize(self.device)
@@ -713,7 +767,7 @@ class PolicyEvaluator:
         try:
             with no_gc(), torch.cuda.graph(g):
                 for _ in range(self.chunk):
-                    self._step(pol, ein, rin, lin=lin, min_=min_, sin=sin)
+                    self._step(pol, ein, rin, lin=lin, min_=min_, sin=sin, gin=gin)
         except Exception as e:      # noqa: BLE001
             if strict_graphs():
                 raise RuntimeError("HIP-graph capture of the evaluation failed (%s: %s)" % (type(e).__name__, e)) from e
@@ -738,6 +792,10 @@ class PolicyEvaluator:
         A trace gains "maneuvers", "maneuver_of_robot" and "switch_steps" (int32 [M, 7], padded with -1).
         With `evaluation.sensors` also "cells": {terrain: {scenario: {condition: {RESULT_KEYS}}}}, "sensors": {condition: {RESULT_KEYS}} over the terrains and scenarios,
         "sensor_names", "sensor_specs": {condition: {SENSOR_FIELDS}} and "cell_table" (go2nn_eval_reduce's raw output per cell).  A trace gains "sensors" and "sensor_of_robot".
+        With `evaluation.gait` also "gait": {"overall": {...}, "groups": {terrain: {scenario: {...}}}} and, under the mode's own keys, "perturbations" / "sensors" /
+        "maneuvers": {name: {...}}, "cells": {terrain: {scenario: {name: {...}}}}, "ladder": {terrain: {level: {scenario: {...}}}}; every leaf has GAIT_KEYS, "<key>/<foot>"
+        for GAIT_FOOT_KEYS and "n_envs"; "gait_table" (go2nn_gait_reduce's raw output per cell), "gait_cells" (what a cell is: its axes' names), "foot_names"; "overall"
+        gains GAIT_KEYS.
         With `evaluation.record` also "trace": TrajectoryRecorder.fetch() of the counted steps plus "group_of_robot" (index into terrain_names x scenarios, terrain-major,
         per tracked robot), "terrain_names" and "scenarios".
         use_graph: None = eager, or with `evaluation.replay` eager the first time and a captured chunk afterwards (on the GPU); True / False force it."""
@@ -773,11 +831,15 @@ class PolicyEvaluator:
             if self.maneuvers is not None:          # as above; segment 0 of every maneuver also covers the warm-up, so the kernels run from the first warm-up step on
                 min_ = self._maneuver_in()
                 self._check(self.nn.go2nn_maneuver_begin(C.c_void_p(self.mtable.data_ptr()), self.num_envs, -self.warmup_steps, self._stream()), "go2nn_maneuver_begin")
+            gin = None
+            if self.gait:          # as above: the step counter starts at -warmup_steps; the first counted step opens every foot's first segment
+                gin = self._gait_in()
+                self._check(self.nn.go2nn_gait_begin(C.c_void_p(self.gtable.data_ptr()), self.num_envs, -self.warmup_steps, self._stream()), "go2nn_gait_begin")
             replay = bool(_get(self.ev, "replay", False))
             graph = (replay and self.on_device and self.evaluations > 0 and self.step_callback is None) if use_graph is None else bool(use_graph and self.on_device)
-            done = graph and self._run_graph(pol, ein, rin, lin, min_, sin)
+            done = graph and self._run_graph(pol, ein, rin, lin, min_, sin, gin)
             if not done:
-                self._run_eager(pol, ein, rin, lin, min_, sin)
+                self._run_eager(pol, ein, rin, lin, min_, sin, gin)
             self.last_mode = "graph" if done else "eager"
             self._check(self.nn.go2nn_eval_reduce(C.c_void_p(self.acc.data_ptr()), C.c_void_p(self.group.data_ptr()), self.num_envs, self.num_cells,
                                                   C.c_void_p(self.out.data_ptr()), self._stream()), "go2nn_eval_reduce")
@@ -796,11 +858,18 @@ class PolicyEvaluator:
                 self._check(self.nn.go2nn_maneuver_reduce(C.c_void_p(self.mtable.data_ptr()), C.c_void_p(self.group.data_ptr()), self.num_envs, self.num_cells,
                                                           C.c_void_p(self.mout.data_ptr()), self._stream()), "go2nn_maneuver_reduce")
                 mtable = self.mout.cpu().numpy().copy()
+            gtable = None
+            if gin is not None:
+                self._check(self.nn.go2nn_gait_reduce(C.c_void_p(self.gtable.data_ptr()), C.c_void_p(self.group.data_ptr()), self.num_envs, self.num_cells,
+                                                      C.c_void_p(self.gout.data_ptr()), self._stream()), "go2nn_gait_reduce")
+                gtable = self.gout.cpu().numpy().copy()
             table = self.out.cpu().numpy().copy()          # the device -> host copy (and synchronisation) of an evaluation
             trace = self.recorder.fetch() if self.recorder is not None else None
             self._graph = None
             self.evaluations += 1
         res = self._results(table, rtable, ltable, mtable)
+        if gtable is not None:
+            self._gait_results(res, gtable)
         if trace is not None:
             trace.update(group_of_robot=self.group_host[trace["env_ids"]].copy(), terrain_names=list(self.terrain_names), scenarios=[s[0] for s in self.scenarios])
             if self.ladder:
@@ -873,6 +942,56 @@ class PolicyEvaluator:
         res["overall"].update(cleared=self._ladder_row(whole)["cleared"], mean_level_cleared=float(np.mean([v["mean_level_cleared"] for v in summary.values()])))
         res.update(levels=list(self.levels), ladder_table=lcells, ladder_cell_table=cells, ladder_distance=self.ladder_distance, ladder_pass_share=self.ladder_pass_share)
 
+    def _gait_row(self, r):
+        """one row of go2nn_gait_reduce, or a sum of rows -> the pooled figures: GAIT_FOOT_KEYS per foot ("<key>/<foot>") and over the four feet, GAIT_PATTERN_KEYS, n_envs;
+        NaN where the denominator is 0"""
+        r = np.asarray(r, np.float64)
+        per = lambda x, n: float(x) / float(n) if n > 0 else float("nan")
+        feet = np.stack([r[gait_out_col(f, GAIT_OUT_FOOT[0]):gait_out_col(f, GAIT_OUT_FOOT[0]) + len(GAIT_OUT_FOOT)] for f in range(4)])
+        d = {}
+        for name, row in [("", feet.sum(0))] + [("/" + n, feet[f]) for f, n in enumerate(self.foot_names)]:
+            v = dict(zip(GAIT_OUT_FOOT, row))
+            d["duty_factor" + name] = per(v["contact"], v["used"])
+            d["stride_frequency" + name] = per(v["strides"], v["stride_steps"] * self.dt)
+            d["stance_time" + name] = per(v["stance_steps"] * self.dt, v["stances"])
+            d["swing_time" + name] = per(v["swing_steps"] * self.dt, v["swings"])
+            d["slip_speed" + name] = per(v["slip_sum"], v["contact"])
+            d["swing_height" + name] = per(v["height_sum"], v["swings"])
+            d["swing_clearance" + name] = per(v["clearance_sum"], v["swings"])
+            d["touchdowns_per_s" + name] = per(v["touchdowns"], v["used"] * self.dt)
+        frames, support = feet[0, 0], r[GO2NN_GAIT_OUT_SUPPORT0:GO2NN_GAIT_OUT_SUPPORT0 + 5]          # (used is the env's own count, the same under every foot)
+        d["trot_share"], d["flight_share"] = per(r[GO2NN_GAIT_OUT_DIAGONAL], frames), per(support[0], frames)
+        d["mean_feet_in_contact"] = per(float(np.dot(np.arange(5.0), support)), frames)
+        d["n_envs"] = int(r[0])
+        return d
+
+    def _gait_results(self, res, gcells):
+        """gcells: go2nn_gait_reduce's table per cell of the active mode -> res["gait"]: the cells' rows summed in fp64 for every partition the mode reports"""
+        T, S, row = len(self.terrain_names), len(self.scenarios), self._gait_row
+        P = len(self.perturbations or self.sensors or [None])
+        if self.ladder:
+            L = len(self.levels)
+            g4 = gcells.reshape(T, L, S, -1)
+            table = g4.sum(1).reshape(T * S, -1)
+        else:
+            g3 = gcells.reshape(T * S, P, -1)
+            table = g3.sum(1)
+        gait = {"overall": row(table.sum(0)), "groups": {t: {s[0]: row(table[ti * S + si]) for si, s in enumerate(self.scenarios)} for ti, t in enumerate(self.terrain_names)}}
+        axes = ["terrain", "scenario"]
+        if self.perturbations is not None or self.sensors is not None:
+            names = [p[0] for p in (self.perturbations or self.sensors)]
+            gait["cells"] = {t: {s[0]: {n: row(g3[ti * S + si, pi]) for pi, n in enumerate(names)} for si, s in enumerate(self.scenarios)} for ti, t in enumerate(self.terrain_names)}
+            gait["perturbations" if self.perturbations is not None else "sensors"] = {n: row(g3[:, pi].sum(0)) for pi, n in enumerate(names)}
+            axes.append("perturbation" if self.perturbations is not None else "sensor")
+        if self.ladder:
+            gait["ladder"] = {t: {lv: {s[0]: row(g4[ti, li, si]) for si, s in enumerate(self.scenarios)} for li, lv in enumerate(self.levels)} for ti, t in enumerate(self.terrain_names)}
+            axes = ["terrain", "level", "scenario"]
+        if self.maneuvers is not None:          # (a "scenario" is a maneuver there)
+            gait["maneuvers"] = {s[0]: row(table.reshape(T, S, -1)[:, si].sum(0)) for si, s in enumerate(self.scenarios)}
+            axes = ["terrain", "maneuver"]
+        res["overall"].update({k: gait["overall"][k] for k in GAIT_KEYS})
+        res.update(gait=gait, gait_table=gcells, gait_cells=axes, foot_names=list(self.foot_names), gait_contact_threshold=self.gait_threshold)
+
     def _results(self, cells, rcells=None, lcells=None, mcells=None):
         """cells: the eval reduce table per (terrain, scenario, perturbation) cell; rcells: the robust one (None without perturbations: a cell is a group then);
         lcells: the ladder's (None without the ladder), cells being per (terrain, level, scenario) then;  mcells: the maneuvers' (None without maneuvers), per
@@ -927,7 +1046,7 @@ class PolicyEvaluator:
 
 # ---------------------------------------------------------------------------------------------------------------------------------------------------------------
 def scalars(res):
-    """[(tag, value)]: 'Eval/<metric>' for the overall figures, 'Eval/<terrain>/<scenario>/<metric>' per group, with perturbations 'Eval/robust/<name>/<metric>', with
+    """[(tag, value)]: with gait 'Eval/gait/<key>' and 'Eval/gait/<terrain>/<scenario>/<key>'; 'Eval/<metric>' for the overall figures, 'Eval/<terrain>/<scenario>/<metric>' per group, with perturbations 'Eval/robust/<name>/<metric>', with
     maneuvers 'Eval/maneuver/<name>/<metric>', with sensor conditions 'Eval/sensors/<name>/<metric>' and, with the ladder, 'Eval/ladder/<terrain>/{level_cleared,mean_level_cleared}' and 'Eval/ladder/mean_level_cleared'"""
     out = [("Eval/" + k, res["overall"][k]) for k in RESULT_KEYS]
     for t, per in res["groups"].items():
@@ -943,6 +1062,11 @@ def scalars(res):
         for t, d in res["ladder_summary"].items():
             out += [("Eval/ladder/%s/%s" % (t, k), d[k]) for k in LADDER_SUMMARY_KEYS]
         out.append(("Eval/ladder/mean_level_cleared", res["overall"]["mean_level_cleared"]))
+    if res.get("gait") is not None:          # overall: pooled and per foot; per group: pooled
+        out += [("Eval/gait/" + k, v) for k, v in res["gait"]["overall"].items() if k != "n_envs"]
+        for t, per in res["gait"]["groups"].items():
+            for s, d in per.items():
+                out += [("Eval/gait/%s/%s/%s" % (t, s, k), d[k]) for k in GAIT_KEYS]
     return out
 
 
@@ -962,6 +1086,10 @@ def results_dict(res, it=None):
         d["ladder"] = {t: {int(lv): {s: dict(v) for s, v in per.items()} for lv, per in levels.items()} for t, levels in res["ladder"].items()}
         d["ladder_summary"] = {t: dict(v) for t, v in res["ladder_summary"].items()}
         d["ladder_levels"], d["ladder_distance"], d["ladder_pass_share"] = [int(l) for l in res["levels"]], float(res["ladder_distance"]), float(res["ladder_pass_share"])
+    if res.get("gait") is not None:          # every partition the mode reports, pooled figures per leaf; level keys as plain ints
+        plain = lambda v: {(int(k) if isinstance(k, (int, np.integer)) else k): plain(x) for k, x in v.items()} if isinstance(v, dict) else v
+        d["gait"] = plain(res["gait"])
+        d["gait_contact_threshold"], d["foot_names"] = float(res["gait_contact_threshold"]), list(res["foot_names"])
     return d
 
 
@@ -996,6 +1124,11 @@ def format_table(res):
         lines += ["", "%-20s " % "sensors" + " ".join("%16s" % c for c in cols)]
         for n, d in list(res["sensors"].items()) + [("all", res["overall"])]:
             lines.append("%-20s " % n + " ".join("%16d" % d[c] if c == "n_envs" else "%16.4f" % d[c] for c in cols))
+    if res.get("gait") is not None:          # one more block: the pooled gait figures per group
+        lines += ["", "%-16s %-14s " % ("terrain", "gait") + " ".join("%20s" % c for c in GAIT_KEYS)]
+        rows = [(t, s, d) for t, per in res["gait"]["groups"].items() for s, d in per.items()] + [("all", "all", res["gait"]["overall"])]
+        for t, s, d in rows:
+            lines.append("%-16s %-14s " % (t, s) + " ".join("%20.4f" % d[c] for c in GAIT_KEYS))
     return "\n".join(lines)
 
 

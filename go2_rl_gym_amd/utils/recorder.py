@@ -143,7 +143,8 @@ def gait_summary(trace, contact_threshold=1.0):
       stance_time       [s] mean length of the COMPLETE stance phases (touchdown and lift-off both seen in the segment);  swing_time: the same for swings
       slip_speed        [m/s] mean horizontal speed of the foot over its contact frames
       swing_height      [m] highest foot position (world z) of each complete swing, averaged
-    Host numpy on a few hundred frames."""
+    Host numpy on a few hundred frames.  The evaluator's device-side scorer (csrc/go2nn_gait.h, `evaluation.gait`) follows the same rule for every robot and is tested
+    against this function: change the two together."""
     force, pos, vel, reset, dt = trace["foot_force"], trace["foot_pos"], trace["foot_vel"], trace["reset"], float(trace["dt"])
     S, K = reset.shape
     out = {k: np.full((K, 4), np.nan) for k in GAIT_KEYS}

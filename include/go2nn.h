@@ -622,6 +622,71 @@ int go2nn_sensor_rand_begin(void* state, void* stream);               /* cursor 
  * passed by value.  GO2NN_EINVAL for null pointers (also_fresh aside), N < 1, D outside [1, 64], a stride < 1, clip <= 0 (or NaN), N * D too large, ranges the check refuses. */
 int go2nn_sensor_rand_apply(const Go2nnSensorIn* in, const Go2nnSensorRand* r, const uint8_t* also_fresh, void* state, float* out, int32_t N, void* stream);
 
+/* ---- the evaluator's gait scores: how does every evaluated robot walk (go2_rl_gym_amd/utils/evaluator.py, `evaluation.gait`; csrc/go2nn_gait.h).
+ * ADDED WITHIN ABI 7: three new entry points, nothing existing changes, GO2NN_ABI_VERSION stays 7.
+ * A gait evaluation step is { ..., go2sim_step, go2nn_eval_accumulate, go2nn_gait_accumulate }: one more plain launch per step (capturable; one lane per env, the four
+ * feet unrolled inside the lane, no atomics), and one go2nn_gait_reduce at the end.  The per-foot rule is that of utils/recorder.py gait_summary, kept in step with it.
+ * The table: fp32 [GO2NN_GAIT_NUM, N], row-major by row, column e = env e: the per-env rows of the first enum below, then GO2NN_GAIT_FOOT_ROWS rows per foot f (row
+ * GO2NN_GAIT_FOOT0 + f * GO2NN_GAIT_FOOT_ROWS + the second enum), f in foot_body order.  Counts and step sums are whole numbers held in fp32 (exact below 2^24).
+ * go2nn_gait_begin: table = 0, then STEP[e] = start for every e (the evaluator passes -warmup_steps).  An all-zero foot state is "no frame of this segment seen yet".
+ * go2nn_gait_accumulate (AFTER the step), per env, with s = STEP[e]:
+ *   s < 0:  nothing but STEP = s + 1 (contacts of the warm-up leave no trace; the first counted step opens a segment).
+ *   reset_buf set:  the frame is not used and ENDS THE SEGMENT: PREV, PHASE_START, LAST_TD = 0 for every foot.  STEP = s + 1.
+ *   otherwise the frame is used:  USED += 1;  a foot is in CONTACT when contact_forces[foot, z] > contact_threshold (strictly); z = rigid_body_states[foot, 2] (world),
+ *   speed = sqrt(vx^2 + vy^2) of rigid_body_states[foot, 7:9].  Per foot, with PREV in { 0 none, 1 swing, 2 contact }:
+ *     contact:  CONTACT += 1, SLIP_SUM += speed.
+ *     PREV == none:               the phase that opens a segment has no seen start: PHASE_START = 0;  swing: SWING_MAX = z;  contact: LIFT_Z = z.
+ *     swing -> contact (TOUCHDOWN):  TOUCHDOWNS += 1;  if LAST_TD: STRIDE_STEPS += s + 1 - LAST_TD, STRIDES += 1;  LAST_TD = s + 1;
+ *                                 if PHASE_START (the swing's lift-off was seen): SWING_STEPS += s + 1 - PHASE_START, SWINGS += 1, HEIGHT_SUM += SWING_MAX,
+ *                                 CLEARANCE_SUM += SWING_MAX - LIFT_Z;  PHASE_START = s + 1, LIFT_Z = z.
+ *     contact -> swing (LIFT-OFF):   if PHASE_START (the stance's touchdown was seen): STANCE_STEPS += s + 1 - PHASE_START, STANCES += 1;  PHASE_START = s + 1, SWING_MAX = z.
+ *     contact -> contact:  LIFT_Z = z (the foot's height on the last contact frame before a swing).     swing -> swing:  SWING_MAX = max(SWING_MAX, z).
+ *     PREV = contact ? 2 : 1.
+ *   So a contact run that opens a segment is no touchdown, a stance or a swing counts only when both of its ends were seen inside the segment, and strides are the step
+ *   differences between consecutive touchdowns of one segment.  PHASE_START and LAST_TD hold step + 1 (0 = none).  HEIGHT_SUM is in world z, which means nothing on
+ *   stairs; CLEARANCE_SUM — the rise above the lift-off point — does.
+ *   Per env, with k = the number of feet in contact: SUPPORT<k> += 1;  DIAGONAL += 1 when the feet in contact are exactly one of the two pairs diagonal_mask[0..1]
+ *   (bit f = foot f of foot_body; the host resolves FL+RR and FR+RL from the foot names — the kernel assumes no order).  STEP = s + 1.
+ * go2nn_gait_reduce: out [G, GO2NN_GAIT_OUT_NUM] (fp64), per group: its envs, then per foot the twelve columns of the third enum (USED is the env's, repeated per foot),
+ * then SUPPORT0 .. SUPPORT4 and DIAGONAL — the summation scheme (and the device function) of go2nn_eval_reduce: fixed order, bit-equal outputs for equal inputs, group ids
+ * outside [0, G) ignored, an empty group gives zeros. */
+enum { GO2NN_GAIT_STEP = 0, GO2NN_GAIT_USED, GO2NN_GAIT_SUPPORT0, GO2NN_GAIT_SUPPORT1, GO2NN_GAIT_SUPPORT2, GO2NN_GAIT_SUPPORT3, GO2NN_GAIT_SUPPORT4, GO2NN_GAIT_DIAGONAL, GO2NN_GAIT_FOOT0 };
+enum {
+  GO2NN_GAIT_F_PREV = 0, GO2NN_GAIT_F_PHASE_START, GO2NN_GAIT_F_LAST_TD, GO2NN_GAIT_F_SWING_MAX, GO2NN_GAIT_F_LIFT_Z, GO2NN_GAIT_F_CONTACT, GO2NN_GAIT_F_SLIP_SUM,
+  GO2NN_GAIT_F_TOUCHDOWNS, GO2NN_GAIT_F_STRIDE_STEPS, GO2NN_GAIT_F_STRIDES, GO2NN_GAIT_F_STANCE_STEPS, GO2NN_GAIT_F_STANCES, GO2NN_GAIT_F_SWING_STEPS, GO2NN_GAIT_F_SWINGS,
+  GO2NN_GAIT_F_HEIGHT_SUM, GO2NN_GAIT_F_CLEARANCE_SUM, GO2NN_GAIT_FOOT_ROWS
+};
+#define GO2NN_GAIT_F_ACC_FIRST GO2NN_GAIT_F_CONTACT                         /* foot rows below it are state, rows from it on are accumulators */
+#define GO2NN_GAIT_NUM (GO2NN_GAIT_FOOT0 + 4 * GO2NN_GAIT_FOOT_ROWS)
+enum {
+  GO2NN_GAIT_O_USED = 0, GO2NN_GAIT_O_CONTACT, GO2NN_GAIT_O_SLIP_SUM, GO2NN_GAIT_O_TOUCHDOWNS, GO2NN_GAIT_O_STRIDE_STEPS, GO2NN_GAIT_O_STRIDES, GO2NN_GAIT_O_STANCE_STEPS,
+  GO2NN_GAIT_O_STANCES, GO2NN_GAIT_O_SWING_STEPS, GO2NN_GAIT_O_SWINGS, GO2NN_GAIT_O_HEIGHT_SUM, GO2NN_GAIT_O_CLEARANCE_SUM, GO2NN_GAIT_OUT_FOOT_COLS
+};
+#define GO2NN_GAIT_OUT_N 0
+#define GO2NN_GAIT_OUT_FOOT0 1
+#define GO2NN_GAIT_OUT_SUPPORT0 (GO2NN_GAIT_OUT_FOOT0 + 4 * GO2NN_GAIT_OUT_FOOT_COLS)
+#define GO2NN_GAIT_OUT_DIAGONAL (GO2NN_GAIT_OUT_SUPPORT0 + 5)
+#define GO2NN_GAIT_OUT_NUM (GO2NN_GAIT_OUT_DIAGONAL + 1)
+/* The buffers as (pointer, env stride, component stride) in ELEMENTS like Go2nnTraceIn's: rigid_body_states [N, bodies, 13] and contact_forces [N, bodies, 3] with
+ * comp_stride between the components of one body and *_body_stride between bodies; foot_body names the four foot bodies; reset_buf uint8 (comp_stride unused, may be 0).
+ * contact_threshold in newtons: finite and >= 0 (the evaluator's default 1.0 is the reference's `> 1 N` rule, legged_robot.py _reward_feet_air_time).  diagonal_mask: two disjoint
+ * masks of two feet each.  Nothing but the table is written. */
+typedef struct Go2nnGaitIn {
+  Go2nnEvalField rigid_body_states, contact_forces, reset_buf;
+  int32_t rigid_body_stride;
+  int32_t contact_body_stride;
+  int32_t foot_body[4];
+  float contact_threshold;
+  int32_t diagonal_mask[2];
+  int32_t pad_;
+} Go2nnGaitIn;
+int go2nn_gait_begin(float* table, int32_t N, int32_t start, void* stream);
+/* GO2NN_EINVAL for null pointers, N < 1, an env stride < 1, a component stride (vector fields) or a body stride < 1, foot_body < 0, a contact_threshold that is negative
+ * or not finite, diagonal masks that are not two disjoint pairs of the four feet. */
+int go2nn_gait_accumulate(const Go2nnGaitIn* in, float* table, int32_t N, void* stream);
+/* GO2NN_EINVAL for null pointers, N < 1, G outside 1 .. 65535. */
+int go2nn_gait_reduce(const float* table, const int32_t* group, int32_t N, int32_t G, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
