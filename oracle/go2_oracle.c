@@ -1366,7 +1366,7 @@ int go2sim_ppo_loss(const float* mu, const float* std, const float* value, const
                     float* workspace, int32_t B, int32_t A, float clip, float vcoef, float ecoef, int32_t use_clip_v, int32_t split, void* stream) {
   (void)stream; (void)workspace;
   if (split <= 0 || split >= B) split = 0;   /* plain PPO */
-  if (!mu||!std||!value||!actions||!old_mu||!old_sigma||!old_logp||!adv||!tv||!ret||!gmu||!gstd||!gval||!stats||B<=0||A<=0||A>64) return GO2SIM_EINVAL;
+  if (!mu||!std||!value||!actions||!old_mu||!old_sigma||!old_logp||!adv||!tv||!ret||!gmu||!gstd||!gval||!stats||B<=0||A<=0||A>16) return GO2SIM_EINVAL;   /* A <= 16: the ABI's limit (include/go2sim.h) */
   double s_sur=0, s_vl=0, s_kl=0, s_ent=0; double gs[64]; for (int j=0;j<A;++j) gs[j]=0;
   const R LOG2PI = RC(1.8378770664093453);
   R ent=0; for (int j=0;j<A;++j) ent += RC(0.5) + RC(0.5)*LOG2PI + (R)log((double)std[j]);
