@@ -12,6 +12,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 NN_LIB = os.path.join(_HERE, "libgo2nn_hip.so")
 GO2NN_MAX_LAYERS, GO2NN_MAX_WIDTH, GO2NN_ABI_VERSION, GO2NN_MAX_GROUP = 6, 512, 7, 2
 GO2NN_RNN_LSTM, GO2NN_RNN_GRU, GO2NN_RNN_MAX_STATES = 0, 1, 4
+GO2NN_TM_MAX_FORWARD, GO2NN_TM_MAX_INPUT_GRAD = 3, 2
+GO2NN_WGRAD_F32_64x64, GO2NN_WGRAD_F32_64x128, GO2NN_WGRAD_SPLIT_128x128 = 1, 2, 3
 # the evaluator's accumulators, in the order of the enum GO2NN_EVAL_* of include/go2nn.h (where the formulas are)
 EVAL_METRICS = ("steps", "lin_vel_err", "ang_vel_err", "speed_along_cmd", "tilt", "power", "torque_sq", "action_rate_sq", "dof_limit_steps", "falls")
 GO2NN_EVAL_NUM = len(EVAL_METRICS)
@@ -228,6 +230,8 @@ def bind(path):
     lib.go2nn_linear_backward_input_fused_rows.argtypes = [C.c_int32]
     lib.go2nn_linear_backward_weight_group_rows.argtypes = [C.POINTER(Go2nnBwdWJob), C.c_int32]
     lib.go2nn_linear_backward_weight_group.argtypes = [C.POINTER(Go2nnBwdWJob), C.c_int32, C.c_void_p]
+    lib.go2nn_linear_group_tile_rows.argtypes = [C.c_int32] * 4          # (within ABI 7) which kernel a shape gets: 64 / 128 / 192 rows per tile; 0 on the host build
+    lib.go2nn_linear_backward_weight_group_kernel.argtypes = [C.POINTER(Go2nnBwdWJob), C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]          # -> GO2NN_WGRAD_*
     lib.go2nn_split_weights_bytes.restype = C.c_int64
     lib.go2nn_split_weights_bytes.argtypes = [C.c_int32] * 2
     lib.go2nn_split_weights.argtypes = [C.POINTER(Go2nnSplitJob), C.c_int32, C.c_void_p]

@@ -802,7 +802,7 @@ int go2nn_linear_elu_forward_group(const Go2nnFwdJob* jobs, int32_t njobs, void*
 #else
   if (jobs[0].w_split && jobs[njobs - 1].w_split && jobs[0].K >= 4 && jobs[njobs - 1].K >= 4) {          // split-operand kernel (go2nn_bx3.h)
     Bx3Args a; memset(&a, 0, sizeof(a));
-    const int tm = bx3_tm(jobs[0].M, jobs[0].N, njobs == 2 ? jobs[1].N : 0, 3);
+    const int tm = bx3_tm(jobs[0].M, jobs[0].N, njobs == 2 ? jobs[1].N : 0, GO2NN_TM_MAX_FORWARD);
     for (int j = 0; j < njobs; ++j) {
       Bx3Prob& g = a.p[j]; const Go2nnFwdJob& q = jobs[j];
       g.A = q.x; g.B = (const unsigned char*)q.w_split; g.C = q.y; g.bias = q.b; g.M = q.M; g.N = q.N; g.K = q.K; g.lda = q.K; g.ldc = q.N;
@@ -890,7 +890,7 @@ int go2nn_linear_backward_input_group(const Go2nnBwdInJob* jobs, int32_t njobs, 
 #else
   if (jobs[0].w_split && jobs[njobs - 1].w_split && jobs[0].C >= 4 && jobs[njobs - 1].C >= 4) {          // split-operand kernel: A = gz [M,C], B = the transposed image (rows k, contraction c)
     Bx3Args a; memset(&a, 0, sizeof(a));
-    const int tm = fused ? 2 : bx3_tm(jobs[0].M, jobs[0].Kin, njobs == 2 ? jobs[1].Kin : 0, 2);          // (192-row tiles measured equal for the input gradient: 100.4 against 99.5 us; not instantiated)
+    const int tm = fused ? 2 : bx3_tm(jobs[0].M, jobs[0].Kin, njobs == 2 ? jobs[1].Kin : 0, GO2NN_TM_MAX_INPUT_GRAD);          // (192-row tiles measured equal for the input gradient: 100.4 against 99.5 us; not instantiated)
     for (int j = 0; j < njobs; ++j) {
       Bx3Prob& g = a.p[j]; const Go2nnBwdInJob& q = jobs[j];
       g.Bf = q.x_in; g.ldb = q.ldx ? q.ldx : q.Kx; g.kx = q.Kx; g.wpart = q.dw_workspace;
@@ -949,6 +949,29 @@ int32_t go2nn_linear_backward_weight_group_rows(const Go2nnBwdWJob* jobs, int32_
   int ta, tn, tiles_of[GO2NN_MAX_GROUP], nsplit, rows;
   if (!wgrad3_group_shape(jobs, njobs, &ta, &tn, tiles_of, &nsplit, &rows)) FAIL(GO2NN_EINVAL, "weight-gradient group: 1..%d jobs with one M, C >= 2, Kin >= 4", GO2NN_MAX_GROUP);
   return nsplit;
+#endif
+}
+
+int32_t go2nn_linear_group_tile_rows(int32_t M, int32_t N0, int32_t N1, int32_t tm_max) {
+  if (M <= 0 || N0 <= 0 || N1 < 0 || tm_max < 1 || tm_max > GO2NN_TM_MAX_FORWARD) FAIL(GO2NN_EINVAL, "tile rows: M, N0 >= 1, N1 >= 0, tm_max 1..%d", GO2NN_TM_MAX_FORWARD);
+#ifdef GO2_EMU
+  return 0;
+#else
+  return 64 * bx3_tm(M, N0, N1, tm_max);
+#endif
+}
+
+int32_t go2nn_linear_backward_weight_group_kernel(const Go2nnBwdWJob* jobs, int32_t njobs, int32_t* nslices, int32_t* rows_per_slice) {
+  int ta, tn, tiles_of[GO2NN_MAX_GROUP], nsplit, rows;
+  if (!wgrad3_group_shape(jobs, njobs, &ta, &tn, tiles_of, &nsplit, &rows)) FAIL(GO2NN_EINVAL, "weight-gradient group: 1..%d jobs with one M, C >= 2, Kin >= 4", GO2NN_MAX_GROUP);
+#ifdef GO2_EMU
+  if (nslices) *nslices = 1;
+  if (rows_per_slice) *rows_per_slice = jobs[0].M;
+  return 0;
+#else
+  if (nslices) *nslices = nsplit;
+  if (rows_per_slice) *rows_per_slice = rows;
+  return ta == 9 ? GO2NN_WGRAD_SPLIT_128x128 : tn == 4 ? GO2NN_WGRAD_F32_64x128 : GO2NN_WGRAD_F32_64x64;
 #endif
 }
 

@@ -162,6 +162,20 @@ int go2nn_linear_backward_input_group(const Go2nnBwdInJob* jobs, int32_t njobs, 
 int32_t go2nn_linear_backward_input_fused_rows(int32_t M);          /* ABI 6: partial rows of dw_workspace */
 int32_t go2nn_linear_backward_weight_group_rows(const Go2nnBwdWJob* jobs, int32_t njobs);
 int go2nn_linear_backward_weight_group(const Go2nnBwdWJob* jobs, int32_t njobs, void* stream);
+/* Which kernel a shape gets (host-side queries, no device work; the host test build returns 0 like go2nn_mlp_arith).  ADDED WITHIN ABI 7: two new entry points, nothing
+ * existing changes, GO2NN_ABI_VERSION stays 7.  The GPU tests read them so that a case meant for one tile path cannot drift to another when a selection rule changes.
+ *   go2nn_linear_group_tile_rows            rows per workgroup tile (64, 128 or 192) of the split-operand (w_split set) forward or input-gradient group launch of M rows whose
+ *                                           jobs are N0 and N1 columns wide (N1 = 0: one job; the input gradient's columns are its Kin); tm_max = GO2NN_TM_MAX_FORWARD resp.
+ *                                           GO2NN_TM_MAX_INPUT_GRAD — the launches pass the same constants to the same selection function (the fused x_in launch is always 128)
+ *   go2nn_linear_backward_weight_group_kernel   the kernel go2nn_linear_backward_weight_group runs for `jobs` (GO2NN_WGRAD_*), with its number of row slices
+ *                                           (= go2nn_linear_backward_weight_group_rows) and the rows of one slice; negative on a group that call would refuse */
+#define GO2NN_TM_MAX_FORWARD 3
+#define GO2NN_TM_MAX_INPUT_GRAD 2
+#define GO2NN_WGRAD_F32_64x64 1        /* fp32 MFMA, 64 x 64 tiles (some Kin is not a multiple of 128) */
+#define GO2NN_WGRAD_F32_64x128 2       /* fp32 MFMA, 64 x 128 tiles */
+#define GO2NN_WGRAD_SPLIT_128x128 3    /* split-operand (Go2nnBwdWJob.split on every job, C in whole 128-row tiles, enough tiles) */
+int32_t go2nn_linear_group_tile_rows(int32_t M, int32_t N0, int32_t N1, int32_t tm_max);
+int32_t go2nn_linear_backward_weight_group_kernel(const Go2nnBwdWJob* jobs, int32_t njobs, int32_t* nslices, int32_t* rows_per_slice);
 
 /* ---- ABI 4: the same three products on the bf16 matrix pipe WITHOUT giving up fp32 operands.  Every fp32 value is split exactly into three bf16 planes
  * (8 + 8 + 8 significand bits) and a product is six bf16 MFMA terms accumulated in fp32 — the three terms left out are below 2^-23 of the product, i.e. below
