@@ -27,6 +27,10 @@ GO2NN_TRACE_WIDTH = sum(w for _, w in TRACE_BLOCKS)
 TRACE_OFFSET = {name: sum(w for _, w in TRACE_BLOCKS[:i]) for i, (name, _) in enumerate(TRACE_BLOCKS)}
 TRACE_FIELDS = ("root_states", "dof_state", "torques", "actions", "commands", "base_lin_vel", "base_ang_vel", "projected_gravity", "rigid_body_states", "contact_forces",
                 "rew_buf", "reset_buf", "time_out_buf")
+# the black box (utils/recorder.py FallRecorder): the per-robot rows of its int32 state block [GO2NN_BLACKBOX_NUM * N + 1] in the order of the enum GO2NN_BLACKBOX_* of
+# include/go2nn.h; the one step counter is the block's last int
+BLACKBOX_ROWS = ("written", "frozen", "fall_step")
+GO2NN_BLACKBOX_NUM = len(BLACKBOX_ROWS)
 # the evaluator's perturbations: the rows of the table [GO2NN_ROBUST_NUM, N] in the order of the enum GO2NN_ROBUST_* of include/go2nn.h (per-env state first, then the
 # accumulators go2nn_robust_reduce sums), the buffers of Go2nnRobustIn in the struct's order, and the mask bit of each writable dynamics row
 ROBUST_ROWS = ("step", "open", "peak_err", "peak_tilt", "ok_run", "done", "pushes", "push_falls", "recovered", "recovery_steps", "peak_err_sum", "peak_tilt_sum")
@@ -253,6 +257,8 @@ def bind(path):
     lib.go2nn_eval_reduce.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
     lib.go2nn_trace_record.argtypes = [C.POINTER(Go2nnTraceIn), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
     lib.go2nn_trace_clear.argtypes = [C.c_void_p, C.c_void_p]
+    lib.go2nn_blackbox_begin.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
+    lib.go2nn_blackbox_record.argtypes = [C.POINTER(Go2nnTraceIn), C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
     lib.go2nn_robust_check_specs.argtypes = [C.c_void_p, C.c_int32]
     lib.go2nn_robust_begin.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
     lib.go2nn_robust_apply.argtypes = [C.POINTER(Go2nnRobustIn), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]

@@ -1251,6 +1251,7 @@ int go2nn_moe_mix_forward(const float* logits, const float* outs, const float* b
 #include "go2nn_rnn.h"          // ABI 7: the recurrent memory's cell steps
 #include "go2nn_eval.h"         // (within ABI 7) the policy evaluator's metric accumulation and per-group reduction
 #include "go2nn_trace.h"        // (within ABI 7) the trajectory recorder's frame kernel
+#include "go2nn_blackbox.h"     // (within ABI 7) the evaluator's black box: a ring of frames per robot that stops at the robot's first counted fall
 #include "go2nn_gait.h"         // (within ABI 7) the evaluator's gait scores: per-foot phase bookkeeping of every robot, per-group sums
 #include "go2nn_robust.h"       // (within ABI 7) the evaluator's perturbations: scheduled pushes, perturbed dynamics rows, push-recovery scores
 #include "go2nn_ladder.h"       // (within ABI 7) the evaluator's terrain-difficulty ladder: per-robot traversal record, per-cell clearing shares

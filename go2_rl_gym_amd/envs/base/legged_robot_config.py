@@ -302,6 +302,9 @@ class LeggedRobotCfgPPO(BaseConfig):
         sensors = None          # None: the policy reads the simulator's exact, current observation.  A list of [name, {field: value}] (fields: noise [x the task's noise], gyro_bias [rad/s], gravity_bias, joint_offset [rad], delay [policy steps, <= 4], drop [probability]); --sensors: utils/evaluator.py DEFAULT_SENSORS
         gait = False            # True (--gait): follow every robot's feet on the device and report duty factor, stride frequency, stance / swing time, slip, swing height and clearance, touchdown rate and the support pattern per group (utils/evaluator.py GAIT_KEYS); an add-on like `record`, it works next to every mode above
         gait_contact_threshold = 1.0  # [N] a foot is in contact when its vertical contact force is > this (the reference's `> 1 N` rule, legged_robot.py _reward_feet_air_time; utils/recorder.py gait_summary's default)
+        blackbox = 0            # n > 0 (--blackbox [n]): keep the last `blackbox_seconds` before every robot's first counted fall on the device and fetch, per reported cell, the n fallen robots with the lowest env indices (utils/recorder.py FallRecorder -> eval_results/falls_<it>.npz); 0: nothing is allocated or launched
+        blackbox_seconds = 2.0  # [s] length of every robot's ring; memory = num_envs x steps x 448 bytes (1024 x 100: 46 MB)
+        blackbox_max_bytes = 512 * 1024 * 1024  # a black box larger than this is refused
 
 
 class LeggedRobotCfgCTS(BaseConfig):
@@ -385,6 +388,9 @@ class LeggedRobotCfgCTS(BaseConfig):
         sensors = None          # None: the policy reads the simulator's exact, current observation.  A list of [name, {field: value}] (fields: noise [x the task's noise], gyro_bias [rad/s], gravity_bias, joint_offset [rad], delay [policy steps, <= 4], drop [probability]); --sensors: utils/evaluator.py DEFAULT_SENSORS
         gait = False            # True (--gait): follow every robot's feet on the device and report duty factor, stride frequency, stance / swing time, slip, swing height and clearance, touchdown rate and the support pattern per group (utils/evaluator.py GAIT_KEYS); an add-on like `record`, it works next to every mode above
         gait_contact_threshold = 1.0  # [N] a foot is in contact when its vertical contact force is > this (the reference's `> 1 N` rule, legged_robot.py _reward_feet_air_time; utils/recorder.py gait_summary's default)
+        blackbox = 0            # n > 0 (--blackbox [n]): keep the last `blackbox_seconds` before every robot's first counted fall on the device and fetch, per reported cell, the n fallen robots with the lowest env indices (utils/recorder.py FallRecorder -> eval_results/falls_<it>.npz); 0: nothing is allocated or launched
+        blackbox_seconds = 2.0  # [s] length of every robot's ring; memory = num_envs x steps x 448 bytes (1024 x 100: 46 MB)
+        blackbox_max_bytes = 512 * 1024 * 1024  # a black box larger than this is refused
 
 
 class LeggedRobotCfgMoECTS(LeggedRobotCfgCTS):

@@ -16,7 +16,9 @@ across all of them.
 --gait also scores how the robots walk (utils/evaluator.py GAIT_KEYS), next to any of the modes above; --metric then also takes the pooled gait figures: slip_speed and
 touchdowns_per_s count as lower is better, trot_share and swing_clearance as higher is better, so --all_checkpoints --gait --metric slip_speed names the checkpoint whose
 feet drag least.
---record N also records N robots of every (terrain x scenario) group and writes eval_results/trace_<checkpoint number>.npz into the run's directory."""
+--record N also records N robots of every (terrain x scenario) group and writes eval_results/trace_<checkpoint number>.npz into the run's directory.
+--blackbox [N] also keeps the last seconds before every robot's first fall (utils/recorder.py FallRecorder), prints per cell with falls how many robots fell and when,
+and writes those of N fallen robots per cell (default 2) to eval_results/falls_<checkpoint number>.npz; read_falls and fall_summary read it back."""
 import json
 import math
 import os
@@ -104,6 +106,10 @@ def evaluate(argv=None, log_root="default", env_kwargs=None, evaluator_kwargs=No
         if res.get("trace") is not None:
             from go2_rl_gym_amd.utils.recorder import write_trace
             print("trace: %s" % write_trace(os.path.join(str(p.parent), "eval_results", "trace_%s.npz" % _checkpoint_number(p)), res["trace"]))
+        if res.get("falls") is not None:
+            from go2_rl_gym_amd.utils.recorder import write_falls
+            rows[-1]["robots_fell"] = res["falls"]["fell_total"]
+            print("falls: %s" % write_falls(os.path.join(str(p.parent), "eval_results", "falls_%s.npz" % _checkpoint_number(p)), res["falls"]))
     metric = own["metric"]
     key = lambda r: r["overall"][metric]
     best = best_checkpoint(rows, metric)

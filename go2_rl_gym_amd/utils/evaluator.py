@@ -68,6 +68,14 @@ frames), `stride_frequency` [Hz], `stance_time`, `swing_time` [s] (complete phas
 support pattern: `trot_share` (frames on exactly one diagonal pair), `flight_share` (no foot down), `mean_feet_in_contact`.  With `gait = False` nothing of this is loaded,
 allocated or launched.
 
+Why a robot fell: with `evaluation.blackbox = n > 0` (--blackbox [n]) a FallRecorder (utils/recorder.py; csrc/go2nn_blackbox.h) keeps for EVERY robot a ring of the last
+`blackbox_seconds` of frames — the trajectory recorder's 112-float frame — that stops when the robot falls on a counted step and stays stopped while the simulator resets
+the robot and carries on.  An add-on like `gait` and `record`, not an axis: one more kernel call per step (two small launches), after the recorder's slot and inside the
+captured chunk; it starts with the warm-up and is NOT cleared at the warm-up boundary, so a fall right after it still has its history.  At the end the small state block
+is read, and of every cell of the finest partition the mode reports the rings of the `n` fallen robots with the lowest env indices are gathered on the device and copied:
+res["falls"], written next to the yaml as falls_<it>.npz (utils/recorder.py read_falls, fall_summary).  Memory: num_envs x steps x 448 bytes (1024 x 100: 46 MB), refused
+above `blackbox_max_bytes`.  Only a robot's first counted fall is kept.  The scores do not depend on it; with blackbox = 0 nothing is allocated, loaded or launched.
+
 Isolated: nothing of the training env, the model, the optimizer or torch's generators is written; policy state the evaluation needs (the CTS observation history, the
 recurrent memory's hidden state) lives in buffers of the evaluator."""
 import copy
@@ -378,6 +386,11 @@ class PolicyEvaluator:
             from .recorder import TrajectoryRecorder
             ids = np.sort(np.concatenate([np.nonzero(self.cell_host == g)[0][:per_group] for g in range(self.num_cells)]))          # (a cell is a group without perturbations)
             self.recorder = TrajectoryRecorder(self.env, ids, self.steps, nn_lib=self.nn)
+        self.blackbox, self.fall_recorder = int(_get(evaluation, "blackbox", 0) or 0), None
+        if self.blackbox < 0:
+            raise ValueError("evaluation.blackbox: robots kept per cell, >= 0 (0 = off), got %r" % (_get(evaluation, "blackbox"),))
+        if self.blackbox > 0:
+            self._build_blackbox()
         self.evaluations = 0
         self.last_mode = None          # "eager" / "graph": how the latest evaluation's steps ran
 
@@ -638,6 +651,51 @@ class PolicyEvaluator:
             print("[go2_rl_gym_amd] evaluation: %d of %d (terrain x scenario) groups have fewer than 4 robots (smallest: %d) for the gait figures; raise evaluation.num_envs"
                   % (int((sizes < 4).sum()), self.num_cells, int(sizes.min())))
 
+    def _build_blackbox(self):
+        """the black box's device side: a ring of `blackbox_seconds` for every robot (utils/recorder.py FallRecorder), refused before anything is allocated when it is too
+        short to show a fall or larger than `blackbox_max_bytes`; and what a cell is called in the falls table"""
+        from .recorder import FallRecorder
+        from .._nn import GO2NN_TRACE_WIDTH
+        seconds, cap = float(_get(self.ev, "blackbox_seconds", 2.0)), int(_get(self.ev, "blackbox_max_bytes", 512 * 1024 * 1024))
+        T = int(round(seconds / self.dt))
+        if T < 2:
+            raise ValueError("evaluation.blackbox_seconds = %r is %d steps of %.4f s: the ring needs at least 2 (the fall frame and one frame before it)" % (seconds, T, self.dt))
+        need = self.num_envs * T * GO2NN_TRACE_WIDTH * 4
+        if need > cap:
+            raise ValueError("evaluation.blackbox: %d robots x %d steps x %d bytes per frame = %d bytes, more than evaluation.blackbox_max_bytes = %d; shorten "
+                             "evaluation.blackbox_seconds or lower evaluation.num_envs" % (self.num_envs, T, GO2NN_TRACE_WIDTH * 4, need, cap))
+        self.fall_recorder = FallRecorder(self.env, T, nn_lib=self.nn)
+        T_, S, P = len(self.terrain_names), len(self.scenarios), len(self.perturbations or self.sensors or [None])
+        if self.ladder:
+            names = ["%s/level_%d/%s" % (t, lv, s[0]) for t in self.terrain_names for lv in self.levels for s in self.scenarios]
+        else:
+            axis = self.perturbations or self.sensors
+            names = ["%s/%s" % (t, s[0]) + ("/" + p[0] if axis else "") for t in self.terrain_names for s in self.scenarios for p in (axis or [None])]
+        assert len(names) == self.num_cells == (T_ * S * (len(self.levels) if self.ladder else P))
+        self.cell_names = names
+
+    def _keep_fallen(self, fell):
+        """of the fallen robots, per cell of the finest partition the mode reports, the `blackbox` lowest env indices"""
+        cells = self.cell_host[fell]
+        return np.sort(np.concatenate([fell[cells == c][:self.blackbox] for c in np.unique(cells)])) if len(fell) else fell
+
+    def _label(self, d, ids):
+        """what a trace and a falls dict say about their robots `ids`: group, and with the mode's extra axis its value per robot and its schedule"""
+        d.update(group_of_robot=self.group_host[ids].copy(), terrain_names=list(self.terrain_names), scenarios=[s[0] for s in self.scenarios])
+        if self.ladder:
+            d.update(levels=list(self.levels), level_of_robot=self.level_of_env[ids].copy())
+        if self.perturbations is not None:          # push_steps: the counted steps (= frame indices) whose go2nn_robust_apply pushed; the frame holds the state AFTER that step
+            d.update(perturbations=[p[0] for p in self.perturbations], pert_of_robot=self.pert_host[ids].copy(), push_steps=self.push_steps.copy())
+        if self.sensors is not None:
+            d.update(sensors=[c[0] for c in self.sensors], sensor_of_robot=self.sensor_host[ids].copy())
+        if self.maneuvers is not None:
+            # switch_steps [M, GO2NN_MANEUVER_MAX_SEGS - 1] int32: per maneuver the counted steps (= frame indices) at which a new segment begins — that frame carries the
+            # new command —, padded with -1 (a rectangular array: maneuvers differ in their number of switches, and the trace goes to an .npz)
+            steps = np.full((len(self.maneuvers), GO2NN_MANEUVER_MAX_SEGS - 1), -1, np.int32)
+            for mi, m in enumerate(self.maneuvers):
+                steps[mi, :len(self.switch_steps[m[0]])] = self.switch_steps[m[0]]
+            d.update(maneuvers=[m[0] for m in self.maneuvers], maneuver_of_robot=self.man_host[ids].copy(), switch_steps=steps)
+
     def _gait_in(self):
         """the gait kernel's view of the simulator's buffers (as TrajectoryRecorder.bind: component and body strides of the two per-body fields)"""
         b, a = self.env._buf, Go2nnGaitIn()
@@ -744,6 +802,8 @@ class PolicyEvaluator:
             self._check(self.nn.go2nn_gait_accumulate(C.byref(gin), C.c_void_p(self.gtable.data_ptr()), self.num_envs, self._stream()), "go2nn_gait_accumulate")
         if self.recorder is not None:
             self.recorder.record()
+        if self.fall_recorder is not None:
+            self.fall_recorder.record()
         pol.after_step(obs, env._buf["reset_buf"])
 
     def _clear(self):
@@ -798,6 +858,8 @@ class PolicyEvaluator:
         gains GAIT_KEYS.
         With `evaluation.record` also "trace": TrajectoryRecorder.fetch() of the counted steps plus "group_of_robot" (index into terrain_names x scenarios, terrain-major,
         per tracked robot), "terrain_names" and "scenarios".
+        With `evaluation.blackbox` also "falls": FallRecorder.fetch() of the kept fallen robots plus the labels a trace gets, "cell_names", "cell_of_robot",
+        "fell_per_cell" (robots that fell per cell, kept or not) and "kept_per_cell".
         use_graph: None = eager, or with `evaluation.replay` eager the first time and a captured chunk afterwards (on the GPU); True / False force it."""
         with torch.inference_mode():
             if self.evaluations > 0:
@@ -835,6 +897,9 @@ class PolicyEvaluator:
             if self.gait:          # as above: the step counter starts at -warmup_steps; the first counted step opens every foot's first segment
                 gin = self._gait_in()
                 self._check(self.nn.go2nn_gait_begin(C.c_void_p(self.gtable.data_ptr()), self.num_envs, -self.warmup_steps, self._stream()), "go2nn_gait_begin")
+            if self.fall_recorder is not None:          # as above; NOT cleared at the warm-up boundary: a ring's history runs through it
+                self.fall_recorder.bind(env)
+                self.fall_recorder.begin(-self.warmup_steps)
             replay = bool(_get(self.ev, "replay", False))
             graph = (replay and self.on_device and self.evaluations > 0 and self.step_callback is None) if use_graph is None else bool(use_graph and self.on_device)
             done = graph and self._run_graph(pol, ein, rin, lin, min_, sin, gin)
@@ -865,27 +930,20 @@ class PolicyEvaluator:
                 gtable = self.gout.cpu().numpy().copy()
             table = self.out.cpu().numpy().copy()          # the device -> host copy (and synchronisation) of an evaluation
             trace = self.recorder.fetch() if self.recorder is not None else None
+            falls = self.fall_recorder.fetch(self._keep_fallen) if self.fall_recorder is not None else None
             self._graph = None
             self.evaluations += 1
         res = self._results(table, rtable, ltable, mtable)
         if gtable is not None:
             self._gait_results(res, gtable)
         if trace is not None:
-            trace.update(group_of_robot=self.group_host[trace["env_ids"]].copy(), terrain_names=list(self.terrain_names), scenarios=[s[0] for s in self.scenarios])
-            if self.ladder:
-                trace.update(levels=list(self.levels), level_of_robot=self.level_of_env[trace["env_ids"]].copy())
-            if self.perturbations is not None:          # push_steps: the counted steps (= frame indices) whose go2nn_robust_apply pushed; the frame holds the state AFTER that step
-                trace.update(perturbations=[p[0] for p in self.perturbations], pert_of_robot=self.pert_host[trace["env_ids"]].copy(), push_steps=self.push_steps.copy())
-            if self.sensors is not None:
-                trace.update(sensors=[c[0] for c in self.sensors], sensor_of_robot=self.sensor_host[trace["env_ids"]].copy())
-            if self.maneuvers is not None:
-                # switch_steps [M, GO2NN_MANEUVER_MAX_SEGS - 1] int32: per maneuver the counted steps (= frame indices) at which a new segment begins — that frame carries the
-                # new command —, padded with -1 (a rectangular array: maneuvers differ in their number of switches, and the trace goes to an .npz)
-                steps = np.full((len(self.maneuvers), GO2NN_MANEUVER_MAX_SEGS - 1), -1, np.int32)
-                for mi, m in enumerate(self.maneuvers):
-                    steps[mi, :len(self.switch_steps[m[0]])] = self.switch_steps[m[0]]
-                trace.update(maneuvers=[m[0] for m in self.maneuvers], maneuver_of_robot=self.man_host[trace["env_ids"]].copy(), switch_steps=steps)
+            self._label(trace, trace["env_ids"])
             res["trace"] = trace
+        if falls is not None:          # the kept robots' labels, and per cell how many robots fell (kept or not)
+            self._label(falls, falls["env_ids"])
+            falls.update(cell_names=list(self.cell_names), cell_of_robot=self.cell_host[falls["env_ids"]].copy(),
+                         fell_per_cell=np.bincount(self.cell_host[falls["fell_env_ids"]], minlength=self.num_cells).astype(np.int64), kept_per_cell=self.blackbox)
+            res["falls"] = falls
         return res
 
     @staticmethod
@@ -1047,7 +1105,7 @@ class PolicyEvaluator:
 # ---------------------------------------------------------------------------------------------------------------------------------------------------------------
 def scalars(res):
     """[(tag, value)]: with gait 'Eval/gait/<key>' and 'Eval/gait/<terrain>/<scenario>/<key>'; 'Eval/<metric>' for the overall figures, 'Eval/<terrain>/<scenario>/<metric>' per group, with perturbations 'Eval/robust/<name>/<metric>', with
-    maneuvers 'Eval/maneuver/<name>/<metric>', with sensor conditions 'Eval/sensors/<name>/<metric>' and, with the ladder, 'Eval/ladder/<terrain>/{level_cleared,mean_level_cleared}' and 'Eval/ladder/mean_level_cleared'"""
+    maneuvers 'Eval/maneuver/<name>/<metric>', with sensor conditions 'Eval/sensors/<name>/<metric>' and, with the ladder, 'Eval/ladder/<terrain>/{level_cleared,mean_level_cleared}' and 'Eval/ladder/mean_level_cleared'; with the black box 'Eval/falls/robots_fell'"""
     out = [("Eval/" + k, res["overall"][k]) for k in RESULT_KEYS]
     for t, per in res["groups"].items():
         for s, d in per.items():
@@ -1067,6 +1125,8 @@ def scalars(res):
         for t, per in res["gait"]["groups"].items():
             for s, d in per.items():
                 out += [("Eval/gait/%s/%s/%s" % (t, s, k), d[k]) for k in GAIT_KEYS]
+    if res.get("falls") is not None:          # with the black box: how many robots fell on a counted step
+        out.append(("Eval/falls/robots_fell", res["falls"]["fell_total"]))
     return out
 
 
@@ -1129,6 +1189,18 @@ def format_table(res):
         rows = [(t, s, d) for t, per in res["gait"]["groups"].items() for s, d in per.items()] + [("all", "all", res["gait"]["overall"])]
         for t, s, d in rows:
             lines.append("%-16s %-14s " % (t, s) + " ".join("%20.4f" % d[c] for c in GAIT_KEYS))
+    if res.get("falls") is not None:          # one more block: per cell with falls, how many robots fell and the medians over the kept ones (NaN: no frame before the fall)
+        from .recorder import fall_summary
+        falls = res["falls"]
+        sm = fall_summary(falls, contact_threshold=float(res.get("gait_contact_threshold", 1.0)))
+        cols = ("robots_fell", "kept", "time_s", "tilt_before", "feet_down_before")
+        lines += ["", "%-44s " % "falls (first counted fall per robot)" + " ".join("%17s" % c for c in cols)]
+        median = lambda v: float(np.nanmedian(v)) if np.isfinite(v).any() else float("nan")
+        for c in np.nonzero(falls["fell_per_cell"])[0]:
+            k = np.asarray(falls["cell_of_robot"]) == c
+            lines.append("%-44s " % falls["cell_names"][c] + "%17d %17d " % (falls["fell_per_cell"][c], int(k.sum()))
+                         + " ".join("%17.4f" % median(sm[key][k]) for key in ("time_s", "tilt", "feet_in_contact")))
+        lines.append("%-44s " % "all" + "%17d %17d" % (falls["fell_total"], len(falls["env_ids"])))
     return "\n".join(lines)
 
 
@@ -1142,4 +1214,7 @@ def write_results(log_dir, it, res):
     if res.get("trace") is not None:
         from .recorder import write_trace
         write_trace(os.path.join(path, "trace_%s.npz" % it), res["trace"])
+    if res.get("falls") is not None:
+        from .recorder import write_falls
+        write_falls(os.path.join(path, "falls_%s.npz" % it), res["falls"])
     return out

@@ -701,6 +701,31 @@ int go2nn_gait_accumulate(const Go2nnGaitIn* in, float* table, int32_t N, void* 
 /* GO2NN_EINVAL for null pointers, N < 1, G outside 1 .. 65535. */
 int go2nn_gait_reduce(const float* table, const int32_t* group, int32_t N, int32_t G, double* out, void* stream);
 
+/* ---- the evaluator's black box: the last T frames before every robot's FIRST COUNTED FALL (go2_rl_gym_amd/utils/recorder.py FallRecorder, `evaluation.blackbox`;
+ * csrc/go2nn_blackbox.h).
+ * ADDED WITHIN ABI 7: two new entry points, nothing existing changes, GO2NN_ABI_VERSION stays 7.
+ * A frame is the trajectory recorder's (GO2NN_TRACE_*, Go2nnTraceIn above, unchanged): the state AFTER the env step.
+ * frames: fp32 [N, T, GO2NN_TRACE_WIDTH] row-major, ROBOT-major: robot e's ring of T slots is contiguous.
+ * state:  int32 [GO2NN_BLACKBOX_NUM * N + 1]: the rows of the enum below, row-major by row (row r of robot e at r * N + e), then ONE step counter at
+ *         GO2NN_BLACKBOX_NUM * N (GO2NN_BLACKBOX_STATE_INTS(N) ints in all).
+ * go2nn_blackbox_begin: every robot WRITTEN = 0, FROZEN = 0, FALL_STEP = -1; the step counter = first_step (the evaluator passes -warmup_steps; steps < 0 are not counted).
+ * go2nn_blackbox_record (AFTER the env step), per robot, with s = the step counter before the call:
+ *   FROZEN:  the robot is skipped; nothing of its ring or of its state rows changes until the next begin.
+ *   otherwise its frame goes to slot WRITTEN % T of its ring, and then
+ *     reset_buf && !time_out_buf (a FALL, go2nn_eval_accumulate's rule) and s >= 0:  WRITTEN += 1, FROZEN = 1, FALL_STEP = s.  The ring's newest frame is the fall step's own
+ *       frame — the post-reset pose with the reset flag set, the recorder's convention —; the frames before it are the fall.
+ *     reset_buf otherwise (a time-out; a fall of the warm-up):  WRITTEN = 0: the ring starts again with the next step, nothing is followed across a reset.
+ *     no reset:  WRITTEN += 1.
+ *   The step counter becomes s + 1.
+ * So a frozen robot's ring holds its last min(WRITTEN, T) frames, the oldest in slot (WRITTEN - min(WRITTEN, T)) % T, the fall frame in slot (WRITTEN - 1) % T; only a
+ * robot's first counted fall is kept.  Two plain launches on `stream` (the frame kernel, one lane per output float, which also advances the step counter it does not read;
+ * then one lane per robot that updates the robot's state rows from the counter), no atomics, no host argument that changes per step: a captured pair replays correctly.
+ * GO2NN_EINVAL for null pointers, N < 1, T < 1, N * GO2NN_TRACE_WIDTH >= 2^31, a bad Go2nnTraceIn (as go2nn_trace_record); a refused call writes nothing. */
+enum { GO2NN_BLACKBOX_WRITTEN = 0, GO2NN_BLACKBOX_FROZEN, GO2NN_BLACKBOX_FALL_STEP, GO2NN_BLACKBOX_NUM };
+#define GO2NN_BLACKBOX_STATE_INTS(N) (GO2NN_BLACKBOX_NUM * (long long)(N) + 1)
+int go2nn_blackbox_begin(int32_t* state, int32_t N, int32_t first_step, void* stream);
+int go2nn_blackbox_record(const Go2nnTraceIn* in, int32_t N, float* frames, int32_t* state, int32_t T, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,6 +1,6 @@
 """What one policy evaluation costs (utils/evaluator.py), and what the metric kernel saves over torch expressions.
 
-    python tools/eval_bench.py [--task go2_flat] [--reps 3] [--robust] [--ladder] [--maneuvers] [--sensors] [--out profiles/eval_bench.json]
+    python tools/eval_bench.py [--task go2_flat] [--reps 3] [--robust] [--ladder] [--maneuvers] [--sensors] [--blackbox] [--out profiles/eval_bench.json]
 
 Measures, on cuda:0, with the task's default `evaluation` section (1024 robots, 1 s + 10 s):
   * wall time of evaluate() run eagerly and with the captured chunk of steps replayed (simulator re-creation, capture and the final host copy included: it is what
@@ -16,6 +16,9 @@ pair of back-to-back launches; again without the torch expressions.
 --sensors: a measurement of its own, ADDED to the JSON file under the key "sensors" (the file's other keys stay as they are): evaluate() run eagerly without and with the
 default sensor conditions (evaluation.sensors = DEFAULT_SENSORS), alternating, in this one session, best and median of --reps, and go2nn_sensor_apply (the frame kernel
 and its one-lane cursor launch) per back-to-back call on the evaluator's own buffers, by the method of the go2nn_eval_accumulate figure.
+--blackbox: a measurement of its own, written to profiles/blackbox_bench.json: evaluate() run eagerly with evaluation.blackbox off and on (2 robots kept per cell),
+alternating, at least three runs each in this one session — best, median, spread and every run —, and go2nn_blackbox_record (the frame kernel and the state kernel) per
+back-to-back call with no robot frozen, by the same method.
 Writes one JSON file and prints it."""
 import argparse
 import ctypes as C
@@ -104,6 +107,42 @@ def sensors_main(a):
         e.close()
 
 
+def blackbox_main(a):
+    """--blackbox: what the black box costs one evaluation, next to the plain evaluation of the same commit in the same session -> profiles/blackbox_bench.json"""
+    env_cfg, train_cfg = task_registry.get_cfgs(a.task)
+    ev_cfg = class_to_dict(train_cfg.evaluation)
+    make = lambda n: PolicyEvaluator(env_cfg, dict(ev_cfg, blackbox=n), task_class=task_registry.get_task_class(a.task), device="cuda:0")
+    evs = {"off": make(0), "on": make(2)}
+    from go2_rl_gym_amd.rsl_rl.modules import ActorCritic
+    torch.manual_seed(0)
+    ac = ActorCritic(45, 263, 12, **{k: v for k, v in class_to_dict(train_cfg.policy).items() if k in ("actor_hidden_dims", "critic_hidden_dims", "activation", "init_noise_std")}).to("cuda:0")
+    res = {k: ev.evaluate(ac, use_graph=False) for k, ev in evs.items()}
+    assert res["on"]["table"].tobytes() == res["off"]["table"].tobytes() and "falls" not in res["off"]
+    ev = evs["on"]
+    rec = ev.fall_recorder
+    rec.begin(0)          # nobody frozen: every back-to-back call writes every robot's frame
+    timed(rec.record, 20)
+    dev_us, wall_us = timed(rec.record, 200)
+    entry = {"task": a.task, "device": torch.cuda.get_device_name(0), "num_envs": ev.num_envs, "steps": ev.warmup_steps + ev.steps, "ring_steps": rec.T,
+             "ring_bytes": rec.frames.numel() * 4, "robots_fell": res["on"]["falls"]["fell_total"], "robots_kept": len(res["on"]["falls"]["env_ids"]),
+             "blackbox_record": {"device_us_per_call_back_to_back": dev_us, "host_us_per_call": wall_us, "launches_per_call": 2, "frame_bytes_per_call": ev.num_envs * 448}}
+    if not a.kernel_only:
+        walls = {k: [] for k in evs}
+        for _ in range(max(a.reps, 3)):          # alternating, in this one session
+            for k, e in evs.items():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                e.evaluate(ac, use_graph=False)
+                walls[k].append((time.perf_counter() - t0) * 1e3)
+        entry["evaluate_wall_ms_eager"] = {k: {"best": min(w), "median": statistics.median(w), "spread": max(w) - min(w), "all": w} for k, w in walls.items()}
+        os.makedirs(os.path.dirname(a.out), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(entry, f, indent=1)
+    print(json.dumps(entry))
+    for e in evs.values():
+        e.close()
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--task", default="go2_flat")
@@ -113,8 +152,12 @@ def main():
     p.add_argument("--ladder", action="store_true")
     p.add_argument("--maneuvers", action="store_true")
     p.add_argument("--sensors", action="store_true")
-    p.add_argument("--out", default=os.path.join(ROOT, "profiles", "eval_bench.json"))
+    p.add_argument("--blackbox", action="store_true")
+    p.add_argument("--out", default=None)
     a = p.parse_args()
+    a.out = a.out or os.path.join(ROOT, "profiles", "blackbox_bench.json" if a.blackbox else "eval_bench.json")
+    if a.blackbox:
+        return blackbox_main(a)
     if a.sensors:
         return sensors_main(a)
     env_cfg, train_cfg = task_registry.get_cfgs(a.task)
