@@ -191,6 +191,43 @@ class Go2nnSensorRand(C.Structure):          # (within ABI 7)
                 ("joint_offset", C.c_float), ("env_offset", C.c_uint32)]
 
 
+class Go2nnMirrorJob(C.Structure):          # (within ABI 7) perm and sign None: both halves of dst are copies
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("width", C.c_int32), ("perm", C.c_void_p), ("sign", C.c_void_p)]
+
+
+GO2NN_MIRROR_MAX_JOBS = 16
+
+
+def mirror_table_tensors(lib, table, device):
+    """A (perm, sign) table of utils/symmetry.py, checked on the host (go2nn_mirror_check_table: the launch cannot report a bad index) and uploaded
+    -> (int16 tensor [W], float32 tensor [W]) on `device`"""
+    import numpy as np
+    perm, sign = np.ascontiguousarray(table[0], np.int16), np.ascontiguousarray(table[1], np.float32)
+    if perm.ndim != 1 or perm.shape != sign.shape:
+        raise ValueError("a mirror table is a pair of 1-d arrays of one length, got shapes %s and %s" % (perm.shape, sign.shape))
+    if lib.go2nn_mirror_check_table(perm.ctypes.data, sign.ctypes.data, perm.shape[0]) != 0:
+        raise ValueError(lib.go2nn_last_error().decode())
+    return torch.from_numpy(perm).to(device), torch.from_numpy(sign).to(device)
+
+
+def mirror_jobs(pairs):
+    """pairs: (src [chunks * chunk_rows, ...], dst [chunks, 2 * chunk_rows, ...], (perm tensor, sign tensor) or None) -> the ctypes job array of go2nn_mirror_rows"""
+    jobs = []
+    for src, dst, tab in pairs:
+        width = int(src[0].numel()) if src.dim() > 1 else 1
+        for t in (src, dst) + (tuple(tab) if tab is not None else ()):
+            assert t.is_contiguous() and t.device == src.device, "contiguous tensors on one device"
+        assert src.dtype == dst.dtype == torch.float32 and dst.numel() == 2 * src.numel() and src.data_ptr() != dst.data_ptr()
+        assert tab is None or (tab[0].dtype == torch.int16 and tab[1].dtype == torch.float32 and tab[0].numel() == tab[1].numel() == width), "a table of the rows' width"
+        jobs.append(Go2nnMirrorJob(src.data_ptr(), dst.data_ptr(), width, tab[0].data_ptr() if tab is not None else None, tab[1].data_ptr() if tab is not None else None))
+    return (Go2nnMirrorJob * len(jobs))(*jobs)
+
+
+def mirror_rows(lib, jobs, chunks, chunk_rows, stream=None):
+    if lib.go2nn_mirror_rows(jobs, len(jobs), int(chunks), int(chunk_rows), stream) != 0:
+        raise RuntimeError("go2nn_mirror_rows failed: %s" % lib.go2nn_last_error().decode())
+
+
 def trace_env_ids(env_ids, num_envs):
     """the tracked robots of go2nn_trace_record as the kernel needs them -> int32 numpy [K], strictly increasing, each in [0, num_envs).  The kernel cannot report a bad
     index (it would read outside the buffers), so anything else raises here."""
@@ -285,6 +322,8 @@ def bind(path):
     lib.go2nn_sensor_rand_state_bytes.argtypes = [C.c_int32, C.c_int32]
     lib.go2nn_sensor_rand_begin.argtypes = [C.c_void_p, C.c_void_p]
     lib.go2nn_sensor_rand_apply.argtypes = [C.POINTER(Go2nnSensorIn), C.POINTER(Go2nnSensorRand), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+    lib.go2nn_mirror_check_table.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+    lib.go2nn_mirror_rows.argtypes = [C.POINTER(Go2nnMirrorJob), C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
     if lib.go2nn_abi_version() != GO2NN_ABI_VERSION:
         raise RuntimeError("%s: ABI version %d, expected %d" % (path, lib.go2nn_abi_version(), GO2NN_ABI_VERSION))
     return lib

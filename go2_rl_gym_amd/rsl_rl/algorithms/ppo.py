@@ -11,6 +11,9 @@ Multi-GPU (one process per GPU, torch.distributed backend 'nccl' = RCCL): each r
 replica; gradients are averaged across ranks before the clip/step and the mean KL before the learning-rate decision, so
 every rank takes the same branch; advantage statistics are all-reduced in RolloutStorage.compute_returns.
 
+Symmetry augmentation (`symmetry=`, off by default; feed-forward policies only): every mini-batch is followed by its left-right mirror image — torch indexing in
+eager mode, ONE go2nn_mirror_rows launch per update inside the captured permutation step in graph mode (the `symmetry augmentation` section below; utils/symmetry.py).
+
 The env's observation buffers are persistent device buffers that the step kernel overwrites IN PLACE (the reference
 rebinds `obs_buf` to fresh tensors every step), so `act()` copies the observations into the rollout storage immediately
 instead of keeping a reference until `process_env_step`.
@@ -28,7 +31,7 @@ from ._graph import CapturedStep, GradBucket, all_captured
 class PPO(_RolloutHeads):
     def __init__(self, actor_critic, num_learning_epochs=1, num_mini_batches=1, clip_param=0.2, gamma=0.998, lam=0.95, value_loss_coef=1.0,
                  entropy_coef=0.0, learning_rate=1e-3, max_grad_norm=1.0, use_clipped_value_loss=True, schedule="fixed", desired_kl=0.01,
-                 device="cpu", lib=None, use_graphs=None, fused_loss=None, fused_rollout=None):
+                 device="cpu", lib=None, use_graphs=None, fused_loss=None, fused_rollout=None, symmetry=False):
         self.desired_kl, self.schedule, self.learning_rate = desired_kl, schedule, learning_rate
         self.actor_critic = actor_critic
         self.actor_critic.to(device)
@@ -50,6 +53,11 @@ class PPO(_RolloutHeads):
         self._rnn, self._rm = bool(getattr(actor_critic, "is_recurrent", False)), None
         if self._rnn and _world() > 1:
             raise NotImplementedError("recurrent policies (ActorCriticRecurrent) train on one rank only: multi-rank recurrent PPO is not implemented")
+        # left-right symmetry augmentation: every mini-batch of the update is followed by its mirror image (utils/symmetry.py holds the tables and what this is not);
+        # off: nothing is loaded, allocated or launched.  The rollout, GAE, the storage and the checkpoints do not know about it; with several ranks it is rank-local.
+        self._sym, self._sym_t, self._aug = self._symmetry_tables(symmetry), None, None
+        if self._sym is not None and self._rnn:
+            raise NotImplementedError("symmetry augmentation with a recurrent policy is not implemented (the mirrored hidden state is a different piece of work)")
         self._sync_replicas(self.actor_critic)
 
     def rebind_lr(self):
@@ -64,6 +72,11 @@ class PPO(_RolloutHeads):
 
     def init_storage(self, num_envs, num_transitions_per_env, actor_obs_shape, critic_obs_shape, action_shape):
         self.storage = RolloutStorage(num_envs, num_transitions_per_env, actor_obs_shape, critic_obs_shape, action_shape, self.device, lib=self.lib)
+        if self._sym is not None:
+            st = self.storage
+            for key, t in (("obs", st.observations), ("cobs", st.privileged_observations), ("act", st.actions)):
+                if t is not None and len(self._sym_table(key)[0]) != t.shape[-1]:
+                    raise ValueError("symmetry: the rollout's %s rows have %d columns, their mirror table %d" % (key, t.shape[-1], len(self._sym_table(key)[0])))
         if self._rnn:
             ac = self.actor_critic
             ac.init_hidden_states(num_envs, self.device)
@@ -156,12 +169,66 @@ class PPO(_RolloutHeads):
         mean_value_loss, mean_surrogate_loss = 0.0, 0.0
         batches = self._rnn_batches() if self._rnn else self.storage.mini_batch_generator(self.num_mini_batches, self.num_learning_epochs)
         for batch in batches:
+            if self._sym is not None:
+                batch = self._sym_batch(batch)
             loss, value_loss, surrogate_loss, kl_mean = self._rnn_losses(batch) if self._rnn else self._losses(*batch[:9])
             self._eager_step(loss, self.optimizer, self._params, kl_mean)
             mean_value_loss += value_loss.item()
             mean_surrogate_loss += surrogate_loss.item()
         n = self.num_learning_epochs * self.num_mini_batches
         return mean_value_loss / n, mean_surrogate_loss / n
+
+    # ---- symmetry augmentation ---------------------------------------------------------------------------------
+    # A mini-batch of B rows becomes 2 B rows: the originals, then their mirror images.  Observations, actions and the old mean go through their tables; the old std is
+    # permuted (a magnitude: never negated); old values, advantages and returns are copied, and so is the old log-probability: that of a mirrored action under the mirrored
+    # old mean and the permuted std is the original's.  Everything behind the batch (losses, KL -> learning rate, clip, Adam) runs unchanged on 2 B rows; which formulation
+    # a mini-batch takes is decided by the modules as before, never by the row count: a kernel that refuses 2 B rows fails its call, and that raises.
+    def _symmetry_tables(self, symmetry):
+        """-> utils/symmetry.py:MirrorTables, or None (off)"""
+        if symmetry is None or symmetry is False:
+            return None
+        if symmetry is True or not all(hasattr(symmetry, k) for k in ("obs", "privileged_obs", "action", "action_std")):
+            raise ValueError("PPO(symmetry=...) takes the task's mirror tables, utils.symmetry.mirror_tables(env_cfg) (the runner builds them for algorithm.symmetry = True), "
+                             "got %r" % (symmetry,))
+        return symmetry
+
+    def _sym_table(self, key):
+        """the (perm, sign) numpy table of the rows of _KEYS entry `key`, None for rows that are copied"""
+        s = self._sym
+        cobs = s.privileged_obs if (self.storage is None or self.storage.privileged_observations is not None) else s.obs
+        return {"obs": s.obs, "cobs": cobs, "act": s.action, "mu": s.action, "sig": s.action_std}.get(key)
+
+    def _sym_batch(self, batch):
+        """The eager formulation (torch indexing), the numerical yardstick of the kernel path: batch of mini_batch_generator -> the same tuple at twice the rows"""
+        if self._sym_t is None:
+            dev = batch[0].device
+            self._sym_t = {k: (torch.as_tensor(self._sym_table(k)[0].astype("int64"), device=dev), torch.as_tensor(self._sym_table(k)[1], device=dev)) for k in ("obs", "cobs", "act", "mu", "sig")}
+        out = []
+        for k, x in zip(self._KEYS, batch[:9]):
+            tab = self._sym_t.get(k)
+            mirror = x if tab is None else x[:, tab[0]] if k == "sig" else x[:, tab[0]] * tab[1]
+            out.append(torch.cat([x, mirror]))
+        return tuple(out) + tuple(batch[9:])
+
+    def _nn_library(self):
+        """the policy-side library (go2nn_mirror_rows): the one the tests handed in, else the device library — missing is an error, there is no torch fallback in graph mode"""
+        if self.nn_lib is not None:
+            return self.nn_lib
+        if not str(self.device).startswith("cuda"):
+            raise RuntimeError("symmetry augmentation in graph mode runs go2nn_mirror_rows: on the CPU hand in the host build (nn_lib), or use the eager mode")
+        from ... import _nn
+        return _nn.load_nn()
+
+    def _sym_setup(self, nmb, mb):
+        """Graph mode: the augmented mini-batches self._aug[k] [nmb, 2 mb, ...] and the ONE go2nn_mirror_rows call that fills them from the permuted rollout self._perm —
+        it runs inside the captured permutation step, behind the gather.  The tables are uploaded once, here."""
+        from ... import _nn
+        lib = self._nn_library()
+        self._aug = {k: torch.empty((nmb, 2 * mb) + tuple(v.shape[1:]), device=self.device, dtype=v.dtype) for k, v in self._perm.items()}
+        tabs = {k: _nn.mirror_table_tensors(lib, self._sym_table(k), self.device) for k in ("obs", "cobs", "act", "mu", "sig")}
+        self._sym_dev = tabs          # (kept alive: the captured launch reads them)
+        self._mirror_jobs = _nn.mirror_jobs([(self._perm[k], self._aug[k], tabs.get(k)) for k in self._KEYS])
+        return lambda: _nn.mirror_rows(lib, self._mirror_jobs, nmb, mb, self._stream(self._acc))
 
     # ---- graph mode -------------------------------------------------------------------------------------------
     _KEYS = ("obs", "cobs", "act", "val", "adv", "ret", "logp", "mu", "sig")
@@ -173,6 +240,8 @@ class PPO(_RolloutHeads):
         if self._rnn:
             batch = self._rnn_fixed[i]
             return list(self._rnn_heads_inputs(batch)) + [t.reshape(-1, t.shape[-1]) for t in batch[2:9]]
+        if self._aug is not None:          # symmetry: chunk i of the permuted rollout followed by its mirror image (go2nn_mirror_rows, once per update)
+            return [self._aug[k][i] for k in self._KEYS]
         mb = self._mb
         return [self._perm[k][i * mb:(i + 1) * mb] for k in self._KEYS]
 
@@ -243,6 +312,7 @@ class PPO(_RolloutHeads):
             self._perm = {k: torch.empty((nmb * mb,) + tuple(v.shape[1:]), device=self.device, dtype=v.dtype) for k, v in self._flat.items()}
             self._acc = torch.zeros(2, device=self.device)
             self._bucket = None
+            mirror = self._sym_setup(nmb, mb) if self._sym is not None else None
             if _collectives_on():
                 self._graph = self._reduced_steps(self._graph_front, self._graph_back, (lambda: self._bucket), "PPO mini-batch")
             else:
@@ -260,7 +330,7 @@ class PPO(_RolloutHeads):
                 self._make_shuffle_key()
             rows = nmb * mb
 
-            def permute():
+            def gather():
                 if not use_lib:
                     self._acc.zero_()
                     indices = torch.randperm(rows, requires_grad=False, device=self.device)
@@ -272,6 +342,11 @@ class PPO(_RolloutHeads):
                     idx = torch.randperm(rows, requires_grad=False, device=self.device).to(torch.int64).contiguous()
                 p = self._ptr
                 self._call("go2sim_shuffle_gather", self._gather_jobs, len(keys), rows, p(idx), p(self._shuffle_key), p(self._acc), int(self._acc.numel()), self._stream(self._acc))
+
+            def permute():
+                gather()
+                if mirror is not None:          # symmetry: the one go2nn_mirror_rows launch, in the same captured step
+                    mirror()
             self._permute = CapturedStep(permute, enabled=self._capture, warmup=2, name="PPO rollout permutation", optional=True)
         self._permute()
         for _ in range(self._graph_reps):

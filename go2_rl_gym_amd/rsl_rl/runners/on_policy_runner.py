@@ -155,7 +155,11 @@ class OnPolicyRunner:
     def _build_algorithm(self, train_cfg, use_graphs):
         num_critic_obs = self.env.num_privileged_obs if self.env.num_privileged_obs is not None else self.env.num_obs
         actor_critic = _POLICIES[self.cfg["policy_class_name"]](self.env.num_obs, num_critic_obs, self.env.num_actions, **self.policy_cfg).to(self.device)
-        self.alg = _ALGS[self.cfg["algorithm_class_name"]](actor_critic, device=self.device, lib=self.lib, use_graphs=use_graphs, **self.alg_cfg)
+        alg_cfg = dict(self.alg_cfg)
+        if alg_cfg.get("symmetry"):          # algorithm.symmetry = True: the task's mirror tables, from the env's own config (any layout but the Go2 tasks' raises)
+            from ...utils.symmetry import mirror_tables
+            alg_cfg["symmetry"] = mirror_tables(self.env.cfg)
+        self.alg = _ALGS[self.cfg["algorithm_class_name"]](actor_critic, device=self.device, lib=self.lib, use_graphs=use_graphs, **alg_cfg)
 
     def _begin_learn(self):
         pass

@@ -726,6 +726,30 @@ enum { GO2NN_BLACKBOX_WRITTEN = 0, GO2NN_BLACKBOX_FROZEN, GO2NN_BLACKBOX_FALL_ST
 int go2nn_blackbox_begin(int32_t* state, int32_t N, int32_t first_step, void* stream);
 int go2nn_blackbox_record(const Go2nnTraceIn* in, int32_t N, float* frames, int32_t* state, int32_t T, void* stream);
 
+/* ---- the PPO update's left-right symmetry augmentation: every mini-batch followed by its mirror image (go2_rl_gym_amd/rsl_rl/algorithms/ppo.py, `algorithm.symmetry`;
+ * the tables: go2_rl_gym_amd/utils/symmetry.py; csrc/go2nn_mirror.h).
+ * ADDED WITHIN ABI 7: two new entry points, nothing existing changes, GO2NN_ABI_VERSION stays 7.
+ * One plain launch per update (capturable), after the rollout's permutation, for up to GO2NN_MIRROR_MAX_JOBS tensors: the job index sits in the grid, one lane per source
+ * element, no LDS, no atomics.  Per job: src fp32 [chunks * chunk_rows, width] row-major; dst fp32 [chunks, 2, chunk_rows, width] row-major, not overlapping src:
+ *   dst[c, 0, r, :] = src[c * chunk_rows + r, :]                                  (the BITS)
+ *   dst[c, 1, r, j] = sign[j] * src[c * chunk_rows + r, perm[j]]                  (one fp32 product by +-1.0f: exact, -0.0 and denormals included)
+ * so chunk c of dst is one contiguous mini-batch of 2 * chunk_rows rows: the originals, then their mirror images.  perm == sign == NULL: both halves are copies.
+ * perm (int16 [width]) and sign (fp32 [width]) live in the buffers' memory space and are uploaded once; the launch cannot read them back, so go2nn_mirror_check_table checks
+ * them in HOST memory before the upload: GO2NN_EINVAL for a null pointer, width outside [1, 32767], perm[j] outside [0, width), a sign that is neither +1 nor -1.
+ * go2nn_mirror_rows: GO2NN_EINVAL, with nothing written, for a null pointer (jobs, src, dst; perm without sign or sign without perm), n_jobs outside
+ * [1, GO2NN_MIRROR_MAX_JOBS], chunks or chunk_rows < 1, width outside [1, 32767], a dst of 2^31 elements or more, 2^24 blocks or more (a block covers up to 4096
+ * source floats of ONE chunk of one job); the host build also for perm[j] outside [0, width). */
+#define GO2NN_MIRROR_MAX_JOBS 16
+typedef struct Go2nnMirrorJob {
+  const float* src;
+  float* dst;
+  int32_t width;
+  const int16_t* perm;
+  const float* sign;
+} Go2nnMirrorJob;
+int go2nn_mirror_check_table(const int16_t* host_perm, const float* host_sign, int32_t width);
+int go2nn_mirror_rows(const Go2nnMirrorJob* jobs, int32_t n_jobs, int32_t chunks, int32_t chunk_rows, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
