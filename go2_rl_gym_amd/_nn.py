@@ -57,6 +57,16 @@ GO2NN_GAIT_FOOT0, GO2NN_GAIT_NUM = len(GAIT_ENV_ROWS), len(GAIT_ENV_ROWS) + 4 * 
 GO2NN_GAIT_OUT_SUPPORT0 = 1 + 4 * len(GAIT_OUT_FOOT)
 GO2NN_GAIT_OUT_DIAGONAL, GO2NN_GAIT_OUT_NUM = GO2NN_GAIT_OUT_SUPPORT0 + 5, GO2NN_GAIT_OUT_SUPPORT0 + 6
 GAIT_FIELDS = ("rigid_body_states", "contact_forces", "reset_buf")
+# the evaluator's asymmetry scores: the rows of the table [GO2NN_ASYM_NUM, N] in the order of the enum GO2NN_ASYM_* of include/go2nn.h (the last eight are the four
+# (left, right) pairs ASYM_PAIRS); go2nn_asym_reduce's output is "n", every row but "step" (eq_max as the group's max), then per pair its imbalance sum and env count; and
+# the buffers of Go2nnAsymIn in the struct's order
+ASYM_ROWS = ("step", "eq_steps", "eq_sq", "eq_sq_hip", "eq_sq_thigh", "eq_sq_calf", "act_sq", "eq_max", "sym_steps", "act_sq_l", "act_sq_r", "torque_sq_l", "torque_sq_r",
+             "power_l", "power_r", "contact_l", "contact_r")
+ASYM_PAIRS = ("act_sq", "torque_sq", "power", "contact")
+GO2NN_ASYM_NUM, GO2NN_ASYM_PAIR0 = len(ASYM_ROWS), ASYM_ROWS.index("act_sq_l")
+ASYM_OUT = ("n",) + ASYM_ROWS[1:] + tuple("%s_%s" % (p, k) for p in ASYM_PAIRS for k in ("imb", "imb_n"))
+GO2NN_ASYM_OUT_IMB0, GO2NN_ASYM_OUT_NUM = GO2NN_ASYM_NUM, len(ASYM_OUT)
+ASYM_FIELDS = ("commands", "dof_state", "torques", "contact_forces", "reset_buf")
 # the evaluator's command maneuvers: the rows of the table [GO2NN_MANEUVER_NUM, N] in the order of the enum GO2NN_MANEUVER_* of include/go2nn.h (per-env state first, then
 # the accumulators go2nn_maneuver_reduce sums; its output columns are those plus "n"), and the buffers of Go2nnManeuverIn in the struct's order
 MANEUVER_ROWS = ("step", "open", "ok_run", "is_settled", "is_fell", "peak_tilt", "switches", "switch_falls", "settled", "settle_steps", "win_steps", "win_lin_err",
@@ -155,6 +165,13 @@ class Go2nnLadderIn(C.Structure):          # (within ABI 7)
 class Go2nnGaitIn(C.Structure):          # (within ABI 7)
     _fields_ = [(k, Go2nnEvalField) for k in GAIT_FIELDS] + [("rigid_body_stride", C.c_int32), ("contact_body_stride", C.c_int32), ("foot_body", C.c_int32 * 4),
                                                              ("contact_threshold", C.c_float), ("diagonal_mask", C.c_int32 * 2), ("pad_", C.c_int32)]
+
+
+class Go2nnAsymIn(C.Structure):          # (within ABI 7)
+    _fields_ = [(k, Go2nnEvalField) for k in ASYM_FIELDS] + [("dof_vel_offset", C.c_int32), ("contact_body_stride", C.c_int32), ("foot_body", C.c_int32 * 4),
+                                                             ("foot_side", C.c_int32 * 4), ("joint_side", C.c_int32 * 12), ("joint_kind", C.c_int32 * 12),
+                                                             ("action_perm", C.c_int16 * 12), ("action_sign", C.c_float * 12), ("contact_threshold", C.c_float),
+                                                             ("pad_", C.c_int32)]
 
 
 def gait_row(foot, name):
@@ -307,6 +324,9 @@ def bind(path):
     lib.go2nn_gait_begin.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
     lib.go2nn_gait_accumulate.argtypes = [C.POINTER(Go2nnGaitIn), C.c_void_p, C.c_int32, C.c_void_p]
     lib.go2nn_gait_reduce.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.go2nn_asym_begin.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
+    lib.go2nn_asym_accumulate.argtypes = [C.POINTER(Go2nnAsymIn), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+    lib.go2nn_asym_reduce.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
     lib.go2nn_maneuver_check_specs.argtypes = [C.c_void_p, C.c_int32]
     lib.go2nn_maneuver_begin.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
     lib.go2nn_maneuver_apply.argtypes = [C.POINTER(Go2nnManeuverIn), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]

@@ -306,6 +306,7 @@ class LeggedRobotCfgPPO(BaseConfig):
         blackbox = 0            # n > 0 (--blackbox [n]): keep the last `blackbox_seconds` before every robot's first counted fall on the device and fetch, per reported cell, the n fallen robots with the lowest env indices (utils/recorder.py FallRecorder -> eval_results/falls_<it>.npz); 0: nothing is allocated or launched
         blackbox_seconds = 2.0  # [s] length of every robot's ring; memory = num_envs x steps x 448 bytes (1024 x 100: 46 MB)
         blackbox_max_bytes = 512 * 1024 * 1024  # a black box larger than this is refused
+        asymmetry = False       # True (--asymmetry): also run the policy on the mirror image of every observation and report how far it is from equivariant (equivariance_rmse, per joint kind, relative, max) and, on steps whose command has vy = yaw = 0, how unequally the robot loads its left and right legs (action, torque, power, contact: left share and per-robot imbalance; utils/evaluator.py ASYM_KEYS); an add-on like `gait`, it works next to every mode above; feed-forward and CTS policies
 
 
 class LeggedRobotCfgCTS(BaseConfig):
@@ -392,6 +393,7 @@ class LeggedRobotCfgCTS(BaseConfig):
         blackbox = 0            # n > 0 (--blackbox [n]): keep the last `blackbox_seconds` before every robot's first counted fall on the device and fetch, per reported cell, the n fallen robots with the lowest env indices (utils/recorder.py FallRecorder -> eval_results/falls_<it>.npz); 0: nothing is allocated or launched
         blackbox_seconds = 2.0  # [s] length of every robot's ring; memory = num_envs x steps x 448 bytes (1024 x 100: 46 MB)
         blackbox_max_bytes = 512 * 1024 * 1024  # a black box larger than this is refused
+        asymmetry = False       # True (--asymmetry): also run the policy on the mirror image of every observation and report how far it is from equivariant (equivariance_rmse, per joint kind, relative, max) and, on steps whose command has vy = yaw = 0, how unequally the robot loads its left and right legs (action, torque, power, contact: left share and per-robot imbalance; utils/evaluator.py ASYM_KEYS); an add-on like `gait`, it works next to every mode above; feed-forward and CTS policies
 
 
 class LeggedRobotCfgMoECTS(LeggedRobotCfgCTS):

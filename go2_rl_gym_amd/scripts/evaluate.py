@@ -16,6 +16,9 @@ across all of them.
 --gait also scores how the robots walk (utils/evaluator.py GAIT_KEYS), next to any of the modes above; --metric then also takes the pooled gait figures: slip_speed and
 touchdowns_per_s count as lower is better, trot_share and swing_clearance as higher is better, so --all_checkpoints --gait --metric slip_speed names the checkpoint whose
 feet drag least.
+--asymmetry also scores left-right asymmetry (utils/evaluator.py ASYM_KEYS), next to any of the modes above; --metric then also takes equivariance_rmse (and /hip, /thigh,
+/calf), equivariance_rel, equivariance_max and imbalance/action, /torque, /power, /contact — all lower is better —, so --all_checkpoints --asymmetry --metric
+equivariance_rmse compares a --symmetry run with a plain one.  left_share/* says WHICH side carries more and has no better direction: it is refused as a metric.
 --record N also records N robots of every (terrain x scenario) group and writes eval_results/trace_<checkpoint number>.npz into the run's directory.
 --blackbox [N] also keeps the last seconds before every robot's first fall (utils/recorder.py FallRecorder), prints per cell with falls how many robots fell and when,
 and writes those of N fallen robots per cell (default 2) to eval_results/falls_<checkpoint number>.npz; read_falls and fall_summary read it back."""
@@ -51,12 +54,26 @@ def _own_flags(argv):
     return own, rest
 
 
+def check_metric(metric):
+    if metric.startswith("left_share/"):
+        raise ValueError("--metric %s: a left share says which side carries more (0.5 is balanced) and has no better direction; rank by imbalance/%s instead"
+                         % (metric, metric.split("/", 1)[1]))
+
+
+def metric_value(row, metric):
+    """a checkpoint row's overall `metric`: the scores' own, or with --asymmetry one of the asymmetry figures (kept in their own section: they leave `overall` alone)"""
+    if metric in row["overall"]:
+        return row["overall"][metric]
+    return row["asymmetry"]["overall"][metric] if "asymmetry" in row else row["overall"][metric]
+
+
 def best_checkpoint(rows, metric):
     """the row with the best overall `metric`.  A figure that does not exist (NaN: settle_time_s without a settled switch, recovery_time_s without a recovered push) ranks
     last, whatever the order of the rows"""
+    check_metric(metric)
     higher = metric in HIGHER_IS_BETTER
     worst = float("-inf") if higher else float("inf")
-    value = lambda r: r["overall"][metric]
+    value = lambda r: metric_value(r, metric)
     rank = lambda r: worst if isinstance(value(r), float) and math.isnan(value(r)) else value(r)
     return (max if higher else min)(rows, key=rank)
 
@@ -64,6 +81,7 @@ def best_checkpoint(rows, metric):
 def evaluate(argv=None, log_root="default", env_kwargs=None, evaluator_kwargs=None):
     """env_kwargs / evaluator_kwargs: extra arguments of the env / of PolicyEvaluator (tests hand in host libraries, as through runner.evaluator_kwargs)"""
     own, rest = _own_flags(list(sys.argv[1:] if argv is None else argv))
+    check_metric(own["metric"])
     args = get_args(rest)
     env_cfg, train_cfg = task_registry.get_cfgs(name=args.task)
     env_cfg.env.num_envs = min(env_cfg.env.num_envs, 64)          # the runner's own env only carries the model's shapes here; the evaluator brings its own simulator
@@ -95,6 +113,8 @@ def evaluate(argv=None, log_root="default", env_kwargs=None, evaluator_kwargs=No
             rows[-1]["sensors"] = res["sensors"]
         if res.get("gait") is not None:
             rows[-1]["gait"] = {"overall": res["gait"]["overall"], "groups": res["gait"]["groups"]}
+        if res.get("asymmetry") is not None:
+            rows[-1]["asymmetry"] = {"overall": res["asymmetry"]["overall"], "groups": res["asymmetry"]["groups"]}
         if res.get("ladder_summary") is not None:
             rows[-1]["ladder_summary"] = res["ladder_summary"]
             import yaml
@@ -111,7 +131,7 @@ def evaluate(argv=None, log_root="default", env_kwargs=None, evaluator_kwargs=No
             rows[-1]["robots_fell"] = res["falls"]["fell_total"]
             print("falls: %s" % write_falls(os.path.join(str(p.parent), "eval_results", "falls_%s.npz" % _checkpoint_number(p)), res["falls"]))
     metric = own["metric"]
-    key = lambda r: r["overall"][metric]
+    key = lambda r: metric_value(r, metric)
     best = best_checkpoint(rows, metric)
     out = {"task": args.task, "metric": metric, "best": best["checkpoint"], "best_value": key(best), "checkpoints": rows}
     print(json.dumps(out))

@@ -76,6 +76,17 @@ is read, and of every cell of the finest partition the mode reports the rings of
 res["falls"], written next to the yaml as falls_<it>.npz (utils/recorder.py read_falls, fall_summary).  Memory: num_envs x steps x 448 bytes (1024 x 100: 46 MB), refused
 above `blackbox_max_bytes`.  Only a robot's first counted fall is kept.  The scores do not depend on it; with blackbox = 0 nothing is allocated, loaded or launched.
 
+How even the policy and the robot are, left against right: with `evaluation.asymmetry` (--asymmetry) every step also runs the policy on the mirror image of the observation
+it has just read, and one more launch after the simulator's step scores both — an add-on like `gait`: it splits nothing and works next to every mode,
+    { a = policy(o), go2nn_mirror_rows(o [, the CTS history ring]), a_m = policy(M_o o), ..., go2sim_step(a), ..., go2nn_asym_accumulate(a, a_m) }
+(csrc/go2nn_asym.h; the rule is in include/go2nn.h; the tables are utils/symmetry.py's), all inside the captured chunk, and at the end one go2nn_asym_reduce over the
+finest cells the mode has.  With e = a - M_a a_m, on every counted step: `equivariance_rmse` (over the 12 joints; `/hip`, `/thigh`, `/calf` over the 4 of a kind),
+`equivariance_rel` (|e| / |a|), `equivariance_max`.  On the counted steps without a reset whose command has vy == 0 and yaw == 0 exactly (`sym_steps_share` of all): for x in
+action (a^2), torque (tau^2), power (|tau qd|), contact (feet with force z > `gait_contact_threshold`) `left_share/<x>` = L / (L + R) and `imbalance/<x>` = the mean over
+the robots of each robot's own |L - R| / (L + R).  ASYM_KEYS are pooled ratios of the cells' sums (the max of their maxima), NaN where nothing was counted; they live in
+res["asymmetry"] only — res["overall"] and every other result are those of the flag-off run.  The mirrored forward shares the weights and nothing else with act(); a
+recurrent policy is refused (its mirrored stream needs a twin hidden state).  With `asymmetry = False` nothing of this is loaded, allocated or launched.
+
 Isolated: nothing of the training env, the model, the optimizer or torch's generators is written; policy state the evaluation needs (the CTS observation history, the
 recurrent memory's hidden state) lives in buffers of the evaluator."""
 import copy
@@ -92,7 +103,8 @@ from .._nn import (EVAL_FIELDS, EVAL_METRICS, GO2NN_EVAL_NUM, GO2NN_RNN_GRU, GO2
                    GO2NN_LADDER_NUM, GO2NN_LADDER_OUT_NUM, LADDER_FIELDS, LADDER_OUT, GO2NN_MANEUVER_ACC_NUM, GO2NN_MANEUVER_MAX_SEGS, GO2NN_MANEUVER_MAX_SPECS, GO2NN_MANEUVER_NUM,
                    MANEUVER_FIELDS, MANEUVER_OUT, Go2nnEvalIn, Go2nnFwdJob, Go2nnLadderIn, Go2nnManeuverIn, Go2nnManeuverSpec, Go2nnMlpIO, Go2nnRnnCellJob, Go2nnRobustIn,
                    Go2nnRobustSpec, PackedMlp, GAIT_FIELDS, GAIT_OUT_FOOT, GO2NN_GAIT_NUM, GO2NN_GAIT_OUT_DIAGONAL, GO2NN_GAIT_OUT_NUM, GO2NN_GAIT_OUT_SUPPORT0, Go2nnGaitIn,
-                   gait_out_col, GO2NN_SENSOR_MAX_DELAY, GO2NN_SENSOR_MAX_SPECS, GO2_OBS_KINDS, SENSOR_KINDS, Go2nnSensorIn, Go2nnSensorSpec)
+                   gait_out_col, ASYM_FIELDS, ASYM_OUT, ASYM_PAIRS, GO2NN_ASYM_NUM, GO2NN_ASYM_OUT_NUM, Go2nnAsymIn, GO2NN_SENSOR_MAX_DELAY, GO2NN_SENSOR_MAX_SPECS, GO2_OBS_KINDS, SENSOR_KINDS, Go2nnSensorIn, Go2nnSensorSpec)
+from .._nn import mirror_rows
 from .helpers import class_to_dict
 
 DEFAULT_SCENARIOS = [["forward_1.0", 1.0, 0.0, 0.0], ["forward_2.0", 2.0, 0.0, 0.0], ["backward_1.0", -1.0, 0.0, 0.0], ["lateral_0.5", 0.0, 0.5, 0.0],
@@ -121,6 +133,10 @@ GAIT_FOOT_KEYS = ("duty_factor", "stride_frequency", "stance_time", "swing_time"
 GAIT_PATTERN_KEYS = ("trot_share", "flight_share", "mean_feet_in_contact")
 GAIT_KEYS = GAIT_FOOT_KEYS + GAIT_PATTERN_KEYS
 DIAGONAL_PAIRS = (("FL", "RR"), ("FR", "RL"))
+# pooled over a partition's robots: the equivariance error of the policy on the visited states, then per load x its left share and the per-robot mean imbalance
+ASYM_LOADS = ("action", "torque", "power", "contact")          # in the order of ASYM_PAIRS (act_sq, torque_sq, power, contact)
+ASYM_EQ_KEYS = ("equivariance_rmse", "equivariance_rmse/hip", "equivariance_rmse/thigh", "equivariance_rmse/calf", "equivariance_rel", "equivariance_max")
+ASYM_KEYS = ASYM_EQ_KEYS + ("sym_steps_share",) + tuple("left_share/" + x for x in ASYM_LOADS) + tuple("imbalance/" + x for x in ASYM_LOADS)
 MAX_CHUNK = 50
 # The accumulate kernel runs AFTER the env step, when the simulator has already rolled its action history (last_actions = this step's actions): the previous step's
 # actions — the kernel's `last_actions` input — are then in the simulator's last_last_actions buffer.
@@ -179,6 +195,10 @@ class _Policy:
     def act(self, obs):
         raise NotImplementedError
 
+    def act_mirrored(self, obs_m, hist_m=None):
+        """the action mean of the MIRRORED observation (`evaluation.asymmetry`): the same weights and kernels as act(), on buffers of its own; no state of act() moves"""
+        raise NotImplementedError
+
     def after_step(self, obs, dones_u8):
         pass
 
@@ -195,6 +215,9 @@ class _MlpPolicy(_Policy):
 
     def act(self, obs):
         return self.actor.forward(obs)
+
+    def act_mirrored(self, obs_m, hist_m=None):
+        return self.actor.forward(obs_m)
 
 
 class _CtsPolicy(_Policy):
@@ -217,6 +240,7 @@ class _CtsPolicy(_Policy):
             self.enc, self.actor = PackedMlp(ev.nn, None, linears=enc), PackedMlp(ev.nn, None, linears=act)
             self.L = enc[-1].out_features
             self.latent = torch.zeros(N, self.L, device=dev)
+            self.latent_m = torch.zeros(N, self.L, device=dev) if ev.asymmetry else None
 
     def _push(self, obs, dones_u8):
         lib = self.ev.env.lib
@@ -245,6 +269,17 @@ class _CtsPolicy(_Policy):
         actions = torch.empty(N, A, device=obs.device)
         self._rows(self.enc, Go2nnMlpIO(hist.data_ptr(), None, None, self.latent.data_ptr(), self.H * self.D, 0, self.H * self.D, N, self.L, 1))
         self._rows(self.actor, Go2nnMlpIO(self.latent.data_ptr(), obs.data_ptr(), None, actions.data_ptr(), self.L, obs.shape[1], self.L, N, A, 0))
+        return actions
+
+    def act_mirrored(self, obs_m, hist_m=None):
+        """hist_m [N, H * D]: the mirror image of the history ring act() has just read (the evaluator's mirror launch makes it next to obs_m)"""
+        N = self.ev.num_envs
+        if not self.kernels:
+            return self.model.policy_mean(self.model.student_latent(hist_m)[0], obs_m).contiguous()
+        A = self.actor.out_dim
+        actions = torch.empty(N, A, device=obs_m.device)
+        self._rows(self.enc, Go2nnMlpIO(hist_m.data_ptr(), None, None, self.latent_m.data_ptr(), self.H * self.D, 0, self.H * self.D, N, self.L, 1))
+        self._rows(self.actor, Go2nnMlpIO(self.latent_m.data_ptr(), obs_m.data_ptr(), None, actions.data_ptr(), self.L, obs_m.shape[1], self.L, N, A, 0))
         return actions
 
     def after_step(self, obs, dones_u8):
@@ -288,6 +323,10 @@ class _RecurrentPolicy(_Policy):
             self._check(nn_.go2nn_rnn_cell_forward((Go2nnRnnCellJob * 1)(job), 1, self._stream()), "go2nn_rnn_cell_forward")
             x = h
         return self.actor.forward(x)
+
+    def act_mirrored(self, obs_m, hist_m=None):
+        raise NotImplementedError("evaluation.asymmetry with a recurrent policy: the mirrored observation stream needs a twin hidden state of its own (zeroed on the same "
+                                  "dones as act()'s), which the evaluator does not keep yet")
 
     def after_step(self, obs, dones_u8):
         sts = [self.h] + ([self.c] if self.lstm else [])
@@ -378,6 +417,9 @@ class PolicyEvaluator:
         self.gait = bool(_get(evaluation, "gait", False))
         if self.gait:
             self._build_gait()
+        self.asymmetry = bool(_get(evaluation, "asymmetry", False))
+        if self.asymmetry:
+            self._build_asymmetry()
         self.dof_limits = self.env.dof_pos_limits.contiguous().clone()
         self._policy, self._policy_of = None, None
         self.recorder = None
@@ -651,6 +693,60 @@ class PolicyEvaluator:
             print("[go2_rl_gym_amd] evaluation: %d of %d (terrain x scenario) groups have fewer than 4 robots (smallest: %d) for the gait figures; raise evaluation.num_envs"
                   % (int((sizes < 4).sum()), self.num_cells, int(sizes.min())))
 
+    def _build_asymmetry(self):
+        """the asymmetry scorer's device side: the mirror tables of the task's layout (any other layout raises mirror_tables' ValueError), the sides of the feet by NAME,
+        the per-env table, the reduce output per cell and the buffer the mirror launch writes the observation and its mirror image to"""
+        from .symmetry import joint_kinds, joint_sides, leg_side, mirror_tables
+        from .._nn import mirror_table_tensors
+        env, N = self.env, self.num_envs
+        self.asym_tables = mirror_tables(self.cfg)
+        perm, sign = self.asym_tables.action
+        if len(perm) != 12:
+            raise ValueError("evaluation.asymmetry: the kernel scores 12 joints, the action table has %d" % len(perm))
+        self.asym_feet = [int(i) for i in env.feet_indices.tolist()]
+        names = [str(env.body_names[i]) for i in self.asym_feet]
+        if len(names) != 4:
+            raise ValueError("evaluation.asymmetry: four feet are needed, got %r" % (names,))
+        self.asym_foot_side = [leg_side(n) for n in names]
+        if sum(self.asym_foot_side) != 0:
+            raise ValueError("evaluation.asymmetry: the feet %r are not two left and two right ones" % (names,))
+        self.asym_joint_side, self.asym_joint_kind = joint_sides().tolist(), joint_kinds().tolist()
+        self.asym_threshold = float(_get(self.ev, "gait_contact_threshold", 1.0))
+        if not (math.isfinite(self.asym_threshold) and self.asym_threshold >= 0.0):
+            raise ValueError("evaluation.gait_contact_threshold: a finite force >= 0 [N], got %r" % (_get(self.ev, "gait_contact_threshold"),))
+        self.asym_obs_table = mirror_table_tensors(self.nn, self.asym_tables.obs, self.device)
+        self.atable = torch.zeros(GO2NN_ASYM_NUM, N, device=self.device)
+        self.aout = torch.zeros(self.num_cells, GO2NN_ASYM_OUT_NUM, dtype=torch.float64, device=self.device)
+        self.asym_obs = torch.zeros(2, N, len(self.asym_tables.obs[0]), device=self.device)          # [0]: the copy half of go2nn_mirror_rows, [1]: the mirror image
+        self.asym_hist = self.asym_hist_table = self.asym_last = None
+
+    def _asym_in(self):
+        """the asymmetry kernel's view of the simulator's buffers (as _gait_in) and its small tables, by value"""
+        b, a = self.env._buf, Go2nnAsymIn()
+        for name in ASYM_FIELDS:
+            t, f = b[name], getattr(a, name)
+            f.p, f.env_stride, f.comp_stride = t.data_ptr(), t.stride(0), (t.stride(t.dim() - 1) if t.dim() > 1 else 0)
+        d = b["dof_state"]
+        a.dof_state.comp_stride, a.dof_vel_offset, a.contact_body_stride = d.stride(1), d.stride(2), b["contact_forces"].stride(1)
+        a.foot_body[:], a.foot_side[:], a.joint_side[:], a.joint_kind[:] = self.asym_feet, self.asym_foot_side, self.asym_joint_side, self.asym_joint_kind
+        a.action_perm[:], a.action_sign[:] = [int(p) for p in self.asym_tables.action[0]], [float(s) for s in self.asym_tables.action[1]]
+        a.contact_threshold = self.asym_threshold
+        return a
+
+    def _asym_jobs(self, pol, obs):
+        """the one mirror launch of a step: the observation the policy reads and, for a policy with a history ring (CTS), the ring -> the go2nn_mirror_rows job array"""
+        from .symmetry import history_table
+        from .._nn import mirror_jobs, mirror_table_tensors
+        pairs = [(obs, self.asym_obs, self.asym_obs_table)]
+        hist = getattr(pol, "history", None)
+        if hist is not None:
+            N, H, D = hist.shape
+            if self.asym_hist is None or tuple(self.asym_hist.shape) != (2, N, H * D):
+                self.asym_hist = torch.zeros(2, N, H * D, device=self.device)
+                self.asym_hist_table = mirror_table_tensors(self.nn, history_table(self.asym_tables.obs, H), self.device)
+            pairs.append((hist.view(N, H * D), self.asym_hist, self.asym_hist_table))
+        return mirror_jobs(pairs), (self.asym_hist[1] if hist is not None else None)
+
     def _build_blackbox(self):
         """the black box's device side: a ring of `blackbox_seconds` for every robot (utils/recorder.py FallRecorder), refused before anything is allocated when it is too
         short to show a fall or larger than `blackbox_max_bytes`; and what a cell is called in the falls table"""
@@ -771,13 +867,17 @@ class PolicyEvaluator:
         return a
 
     # ------------------------------------------------------------------ one env step of the evaluation (pure enqueue)
-    def _step(self, pol, ein, rin=None, k=None, lin=None, min_=None, sin=None, gin=None):
+    def _step(self, pol, ein, rin=None, k=None, lin=None, min_=None, sin=None, gin=None, ain=None):
         """rin: the perturbation kernels' input (None without perturbations);  k: the step's index in an eager run (None inside a capture: no callback there);
         lin: the ladder kernel's input (None without the ladder);  min_: the maneuver kernels' input (None without maneuvers);  sin: the sensor kernel's input (None without
-        sensors: the policy then reads the simulator's observation itself);  gin: the gait kernel's input (None without gait)"""
+        sensors: the policy then reads the simulator's observation itself);  gin: the gait kernel's input (None without gait);  ain: (the asymmetry kernel's input, the
+        mirror launch's jobs, the mirrored history or None) (None without asymmetry)"""
         env = self.env
         obs = env.obs_buf if sin is None else self.delivered
         actions = pol.act(obs)
+        if ain is not None:          # the mirror image of what act() has just read, and the same weights on it; nothing act() owns moves
+            mirror_rows(self.nn, ain[1], 1, self.num_envs, self._stream())
+            mirrored = pol.act_mirrored(self.asym_obs[1], ain[2])
         if min_ is not None:
             self._maneuver(self.nn.go2nn_maneuver_apply, "go2nn_maneuver_apply", min_)
             if k is not None and self.apply_callback is not None:
@@ -800,6 +900,10 @@ class PolicyEvaluator:
             self._check(self.nn.go2nn_ladder_accumulate(C.byref(lin), C.c_void_p(self.ltable.data_ptr()), self.num_envs, self._stream()), "go2nn_ladder_accumulate")
         if gin is not None:
             self._check(self.nn.go2nn_gait_accumulate(C.byref(gin), C.c_void_p(self.gtable.data_ptr()), self.num_envs, self._stream()), "go2nn_gait_accumulate")
+        if ain is not None:
+            self._check(self.nn.go2nn_asym_accumulate(C.byref(ain[0]), C.c_void_p(actions.data_ptr()), C.c_void_p(mirrored.data_ptr()), C.c_void_p(self.atable.data_ptr()),
+                                                      self.num_envs, self._stream()), "go2nn_asym_accumulate")
+            self.asym_last = (actions, mirrored)          # (what a step_callback of a test reads next to asym_obs)
         if self.recorder is not None:
             self.recorder.record()
         if self.fall_recorder is not None:
@@ -811,15 +915,15 @@ class PolicyEvaluator:
         if self.recorder is not None:
             self.recorder.clear()
 
-    def _run_eager(self, pol, ein, rin, lin=None, min_=None, sin=None, gin=None):
+    def _run_eager(self, pol, ein, rin, lin=None, min_=None, sin=None, gin=None, ain=None):
         for k in range(self.warmup_steps + self.steps):
             if k == self.warmup_steps:
                 self._clear()
-            self._step(pol, ein, rin, k, lin, min_, sin, gin)
+            self._step(pol, ein, rin, k, lin, min_, sin, gin, ain)
             if self.step_callback is not None:
                 self.step_callback(self, k, k >= self.warmup_steps)
 
-    def _run_graph(self, pol, ein, rin, lin=None, min_=None, sin=None, gin=None):
+    def _run_graph(self, pol, ein, rin, lin=None, min_=None, sin=None, gin=None, ain=None):
         """capture `chunk` steps on this evaluation's simulator, replay them for the whole horizon -> False if the capture failed (nothing has run then)"""
         from ..rsl_rl.algorithms._graph import no_gc, strict_graphs
         torch.cuda.synchronize(self.device)
@@ -827,7 +931,7 @@ class PolicyEvaluator:
         try:
             with no_gc(), torch.cuda.graph(g):
                 for _ in range(self.chunk):
-                    self._step(pol, ein, rin, lin=lin, min_=min_, sin=sin, gin=gin)
+                    self._step(pol, ein, rin, lin=lin, min_=min_, sin=sin, gin=gin, ain=ain)
         except Exception as e:      # noqa: BLE001
             if strict_graphs():
                 raise RuntimeError("HIP-graph capture of the evaluation failed (%s: %s)" % (type(e).__name__, e)) from e
@@ -856,6 +960,8 @@ class PolicyEvaluator:
         "maneuvers": {name: {...}}, "cells": {terrain: {scenario: {name: {...}}}}, "ladder": {terrain: {level: {scenario: {...}}}}; every leaf has GAIT_KEYS, "<key>/<foot>"
         for GAIT_FOOT_KEYS and "n_envs"; "gait_table" (go2nn_gait_reduce's raw output per cell), "gait_cells" (what a cell is: its axes' names), "foot_names"; "overall"
         gains GAIT_KEYS.
+        With `evaluation.asymmetry` also "asymmetry": the same tree as "gait" ("overall", "groups" and the mode's own keys), every leaf with ASYM_KEYS and "n_envs";
+        "asymmetry_table" (go2nn_asym_reduce's raw output per cell), "asymmetry_cells" and "asymmetry_contact_threshold".  "overall" gains nothing.
         With `evaluation.record` also "trace": TrajectoryRecorder.fetch() of the counted steps plus "group_of_robot" (index into terrain_names x scenarios, terrain-major,
         per tracked robot), "terrain_names" and "scenarios".
         With `evaluation.blackbox` also "falls": FallRecorder.fetch() of the kept fallen robots plus the labels a trace gets, "cell_names", "cell_of_robot",
@@ -867,6 +973,8 @@ class PolicyEvaluator:
             if self._policy_of is not actor_critic:
                 self._policy, self._policy_of = _make_policy(self, actor_critic), actor_critic
             pol, env = self._policy, self.env
+            if self.asymmetry and isinstance(pol, _RecurrentPolicy):          # refused before anything runs
+                pol.act_mirrored(None)
             _abi.check(env.lib, env.lib.go2sim_reset_all(env.handle, self._stream()), "go2sim_reset_all")
             env.commands.copy_(self.commands)
             zero = torch.zeros(self.num_envs, env.num_actions, device=self.device)
@@ -897,14 +1005,19 @@ class PolicyEvaluator:
             if self.gait:          # as above: the step counter starts at -warmup_steps; the first counted step opens every foot's first segment
                 gin = self._gait_in()
                 self._check(self.nn.go2nn_gait_begin(C.c_void_p(self.gtable.data_ptr()), self.num_envs, -self.warmup_steps, self._stream()), "go2nn_gait_begin")
+            ain = None
+            if self.asymmetry:          # as above: the step counter starts at -warmup_steps and the kernel advances it
+                jobs, hist_m = self._asym_jobs(pol, env.obs_buf if sin is None else self.delivered)
+                ain = (self._asym_in(), jobs, hist_m)
+                self._check(self.nn.go2nn_asym_begin(C.c_void_p(self.atable.data_ptr()), self.num_envs, -self.warmup_steps, self._stream()), "go2nn_asym_begin")
             if self.fall_recorder is not None:          # as above; NOT cleared at the warm-up boundary: a ring's history runs through it
                 self.fall_recorder.bind(env)
                 self.fall_recorder.begin(-self.warmup_steps)
             replay = bool(_get(self.ev, "replay", False))
             graph = (replay and self.on_device and self.evaluations > 0 and self.step_callback is None) if use_graph is None else bool(use_graph and self.on_device)
-            done = graph and self._run_graph(pol, ein, rin, lin, min_, sin, gin)
+            done = graph and self._run_graph(pol, ein, rin, lin, min_, sin, gin, ain)
             if not done:
-                self._run_eager(pol, ein, rin, lin, min_, sin, gin)
+                self._run_eager(pol, ein, rin, lin, min_, sin, gin, ain)
             self.last_mode = "graph" if done else "eager"
             self._check(self.nn.go2nn_eval_reduce(C.c_void_p(self.acc.data_ptr()), C.c_void_p(self.group.data_ptr()), self.num_envs, self.num_cells,
                                                   C.c_void_p(self.out.data_ptr()), self._stream()), "go2nn_eval_reduce")
@@ -928,6 +1041,12 @@ class PolicyEvaluator:
                 self._check(self.nn.go2nn_gait_reduce(C.c_void_p(self.gtable.data_ptr()), C.c_void_p(self.group.data_ptr()), self.num_envs, self.num_cells,
                                                       C.c_void_p(self.gout.data_ptr()), self._stream()), "go2nn_gait_reduce")
                 gtable = self.gout.cpu().numpy().copy()
+            atable = None
+            if ain is not None:
+                self._check(self.nn.go2nn_asym_reduce(C.c_void_p(self.atable.data_ptr()), C.c_void_p(self.group.data_ptr()), self.num_envs, self.num_cells,
+                                                      C.c_void_p(self.aout.data_ptr()), self._stream()), "go2nn_asym_reduce")
+                atable = self.aout.cpu().numpy().copy()
+                self.asym_last = None
             table = self.out.cpu().numpy().copy()          # the device -> host copy (and synchronisation) of an evaluation
             trace = self.recorder.fetch() if self.recorder is not None else None
             falls = self.fall_recorder.fetch(self._keep_fallen) if self.fall_recorder is not None else None
@@ -936,6 +1055,8 @@ class PolicyEvaluator:
         res = self._results(table, rtable, ltable, mtable)
         if gtable is not None:
             self._gait_results(res, gtable)
+        if atable is not None:
+            self._asym_results(res, atable)
         if trace is not None:
             self._label(trace, trace["env_ids"])
             res["trace"] = trace
@@ -1023,32 +1144,72 @@ class PolicyEvaluator:
         d["n_envs"] = int(r[0])
         return d
 
-    def _gait_results(self, res, gcells):
-        """gcells: go2nn_gait_reduce's table per cell of the active mode -> res["gait"]: the cells' rows summed in fp64 for every partition the mode reports"""
-        T, S, row = len(self.terrain_names), len(self.scenarios), self._gait_row
+    def _addon_tree(self, cells, row, pool=np.sum):
+        """cells: an add-on's reduce table per cell of the active mode;  pool(a, axis): stacked rows -> the row of their union (a sum in fp64);  row: such a row -> its figures.
+        -> ({"overall", "groups" and the mode's own keys: `row` of every partition the mode reports}, what a cell is: its axes' names)"""
+        T, S = len(self.terrain_names), len(self.scenarios)
         P = len(self.perturbations or self.sensors or [None])
         if self.ladder:
             L = len(self.levels)
-            g4 = gcells.reshape(T, L, S, -1)
-            table = g4.sum(1).reshape(T * S, -1)
+            g4 = cells.reshape(T, L, S, -1)
+            table = pool(g4, 1).reshape(T * S, -1)
         else:
-            g3 = gcells.reshape(T * S, P, -1)
-            table = g3.sum(1)
-        gait = {"overall": row(table.sum(0)), "groups": {t: {s[0]: row(table[ti * S + si]) for si, s in enumerate(self.scenarios)} for ti, t in enumerate(self.terrain_names)}}
+            g3 = cells.reshape(T * S, P, -1)
+            table = pool(g3, 1)
+        tree = {"overall": row(pool(table, 0)), "groups": {t: {s[0]: row(table[ti * S + si]) for si, s in enumerate(self.scenarios)} for ti, t in enumerate(self.terrain_names)}}
         axes = ["terrain", "scenario"]
         if self.perturbations is not None or self.sensors is not None:
             names = [p[0] for p in (self.perturbations or self.sensors)]
-            gait["cells"] = {t: {s[0]: {n: row(g3[ti * S + si, pi]) for pi, n in enumerate(names)} for si, s in enumerate(self.scenarios)} for ti, t in enumerate(self.terrain_names)}
-            gait["perturbations" if self.perturbations is not None else "sensors"] = {n: row(g3[:, pi].sum(0)) for pi, n in enumerate(names)}
+            tree["cells"] = {t: {s[0]: {n: row(g3[ti * S + si, pi]) for pi, n in enumerate(names)} for si, s in enumerate(self.scenarios)} for ti, t in enumerate(self.terrain_names)}
+            tree["perturbations" if self.perturbations is not None else "sensors"] = {n: row(pool(g3[:, pi], 0)) for pi, n in enumerate(names)}
             axes.append("perturbation" if self.perturbations is not None else "sensor")
         if self.ladder:
-            gait["ladder"] = {t: {lv: {s[0]: row(g4[ti, li, si]) for si, s in enumerate(self.scenarios)} for li, lv in enumerate(self.levels)} for ti, t in enumerate(self.terrain_names)}
+            tree["ladder"] = {t: {lv: {s[0]: row(g4[ti, li, si]) for si, s in enumerate(self.scenarios)} for li, lv in enumerate(self.levels)} for ti, t in enumerate(self.terrain_names)}
             axes = ["terrain", "level", "scenario"]
         if self.maneuvers is not None:          # (a "scenario" is a maneuver there)
-            gait["maneuvers"] = {s[0]: row(table.reshape(T, S, -1)[:, si].sum(0)) for si, s in enumerate(self.scenarios)}
+            tree["maneuvers"] = {s[0]: row(pool(table.reshape(T, S, -1)[:, si], 0)) for si, s in enumerate(self.scenarios)}
             axes = ["terrain", "maneuver"]
+        return tree, axes
+
+    def _gait_results(self, res, gcells):
+        """gcells: go2nn_gait_reduce's table per cell of the active mode -> res["gait"]: the cells' rows summed in fp64 for every partition the mode reports"""
+        gait, axes = self._addon_tree(gcells, self._gait_row)
         res["overall"].update({k: gait["overall"][k] for k in GAIT_KEYS})
         res.update(gait=gait, gait_table=gcells, gait_cells=axes, foot_names=list(self.foot_names), gait_contact_threshold=self.gait_threshold)
+
+    @staticmethod
+    def _asym_pool(rows, axis=0):
+        """stacked rows of go2nn_asym_reduce -> the row of their union along `axis` (not the last): every column a sum, eq_max the max"""
+        rows = np.asarray(rows, np.float64)
+        out, c = rows.sum(axis), ASYM_OUT.index("eq_max")
+        out[..., c] = rows[..., c].max(axis)
+        return out
+
+    @staticmethod
+    def _asym_row(r):
+        """one row of go2nn_asym_reduce, or a pooled one (_asym_pool) -> ASYM_KEYS and n_envs: pooled ratios of the sums, NaN where nothing was counted"""
+        v = dict(zip(ASYM_OUT, (float(x) for x in r)))
+        per = lambda x, n: x / n if n > 0 else float("nan")
+        root = lambda x: math.sqrt(x) if x == x else x
+        steps = v["eq_steps"]
+        d = {"equivariance_rmse": root(per(v["eq_sq"], 12.0 * steps))}
+        for kind in ("hip", "thigh", "calf"):
+            d["equivariance_rmse/" + kind] = root(per(v["eq_sq_" + kind], 4.0 * steps))
+        d["equivariance_rel"] = root(per(v["eq_sq"], v["act_sq"]))
+        d["equivariance_max"] = v["eq_max"] if steps > 0 else float("nan")
+        d["sym_steps_share"] = per(v["sym_steps"], steps)
+        for x, p in zip(ASYM_LOADS, ASYM_PAIRS):
+            d["left_share/" + x] = per(v[p + "_l"], v[p + "_l"] + v[p + "_r"])
+        for x, p in zip(ASYM_LOADS, ASYM_PAIRS):
+            d["imbalance/" + x] = per(v[p + "_imb"], v[p + "_imb_n"])
+        d["n_envs"] = int(v["n"])
+        return d
+
+    def _asym_results(self, res, acells):
+        """acells: go2nn_asym_reduce's table per cell of the active mode -> res["asymmetry"]: the cells' rows pooled for every partition the mode reports.
+        res["overall"] is left as it is: with the flag on every other result is that of the flag-off run"""
+        asym, axes = self._addon_tree(acells, self._asym_row, self._asym_pool)
+        res.update(asymmetry=asym, asymmetry_table=acells, asymmetry_cells=axes, asymmetry_contact_threshold=self.asym_threshold)
 
     def _results(self, cells, rcells=None, lcells=None, mcells=None):
         """cells: the eval reduce table per (terrain, scenario, perturbation) cell; rcells: the robust one (None without perturbations: a cell is a group then);
@@ -1104,7 +1265,7 @@ class PolicyEvaluator:
 
 # ---------------------------------------------------------------------------------------------------------------------------------------------------------------
 def scalars(res):
-    """[(tag, value)]: with gait 'Eval/gait/<key>' and 'Eval/gait/<terrain>/<scenario>/<key>'; 'Eval/<metric>' for the overall figures, 'Eval/<terrain>/<scenario>/<metric>' per group, with perturbations 'Eval/robust/<name>/<metric>', with
+    """[(tag, value)]: with gait 'Eval/gait/<key>' and 'Eval/gait/<terrain>/<scenario>/<key>'; with asymmetry 'Eval/asymmetry/<key>' and 'Eval/asymmetry/<terrain>/<scenario>/<key>'; 'Eval/<metric>' for the overall figures, 'Eval/<terrain>/<scenario>/<metric>' per group, with perturbations 'Eval/robust/<name>/<metric>', with
     maneuvers 'Eval/maneuver/<name>/<metric>', with sensor conditions 'Eval/sensors/<name>/<metric>' and, with the ladder, 'Eval/ladder/<terrain>/{level_cleared,mean_level_cleared}' and 'Eval/ladder/mean_level_cleared'; with the black box 'Eval/falls/robots_fell'"""
     out = [("Eval/" + k, res["overall"][k]) for k in RESULT_KEYS]
     for t, per in res["groups"].items():
@@ -1125,6 +1286,11 @@ def scalars(res):
         for t, per in res["gait"]["groups"].items():
             for s, d in per.items():
                 out += [("Eval/gait/%s/%s/%s" % (t, s, k), d[k]) for k in GAIT_KEYS]
+    if res.get("asymmetry") is not None:          # 'Eval/asymmetry/<key>' overall and 'Eval/asymmetry/<terrain>/<scenario>/<key>' per group
+        out += [("Eval/asymmetry/" + k, res["asymmetry"]["overall"][k]) for k in ASYM_KEYS]
+        for t, per in res["asymmetry"]["groups"].items():
+            for s, d in per.items():
+                out += [("Eval/asymmetry/%s/%s/%s" % (t, s, k), d[k]) for k in ASYM_KEYS]
     if res.get("falls") is not None:          # with the black box: how many robots fell on a counted step
         out.append(("Eval/falls/robots_fell", res["falls"]["fell_total"]))
     return out
@@ -1146,10 +1312,13 @@ def results_dict(res, it=None):
         d["ladder"] = {t: {int(lv): {s: dict(v) for s, v in per.items()} for lv, per in levels.items()} for t, levels in res["ladder"].items()}
         d["ladder_summary"] = {t: dict(v) for t, v in res["ladder_summary"].items()}
         d["ladder_levels"], d["ladder_distance"], d["ladder_pass_share"] = [int(l) for l in res["levels"]], float(res["ladder_distance"]), float(res["ladder_pass_share"])
+    plain = lambda v: {(int(k) if isinstance(k, (int, np.integer)) else k): plain(x) for k, x in v.items()} if isinstance(v, dict) else v
     if res.get("gait") is not None:          # every partition the mode reports, pooled figures per leaf; level keys as plain ints
-        plain = lambda v: {(int(k) if isinstance(k, (int, np.integer)) else k): plain(x) for k, x in v.items()} if isinstance(v, dict) else v
         d["gait"] = plain(res["gait"])
         d["gait_contact_threshold"], d["foot_names"] = float(res["gait_contact_threshold"]), list(res["foot_names"])
+    if res.get("asymmetry") is not None:          # as the gait section: every partition the mode reports
+        d["asymmetry"] = plain(res["asymmetry"])
+        d["asymmetry_contact_threshold"] = float(res["asymmetry_contact_threshold"])
     return d
 
 
@@ -1189,6 +1358,12 @@ def format_table(res):
         rows = [(t, s, d) for t, per in res["gait"]["groups"].items() for s, d in per.items()] + [("all", "all", res["gait"]["overall"])]
         for t, s, d in rows:
             lines.append("%-16s %-14s " % (t, s) + " ".join("%20.4f" % d[c] for c in GAIT_KEYS))
+    if res.get("asymmetry") is not None:          # one more block: the policy's equivariance error and the left / right load per group
+        cols = ("equivariance_rmse", "equivariance_rel", "equivariance_max", "sym_steps_share") + tuple("left_share/" + x for x in ASYM_LOADS) + tuple("imbalance/" + x for x in ASYM_LOADS)
+        lines += ["", "%-16s %-14s " % ("terrain", "asymmetry") + " ".join("%18s" % c for c in cols)]
+        rows = [(t, s, d) for t, per in res["asymmetry"]["groups"].items() for s, d in per.items()] + [("all", "all", res["asymmetry"]["overall"])]
+        for t, s, d in rows:
+            lines.append("%-16s %-14s " % (t, s) + " ".join("%18.3e" % d[c] if c.startswith("equivariance") else "%18.4f" % d[c] for c in cols))
     if res.get("falls") is not None:          # one more block: per cell with falls, how many robots fell and the medians over the kept ones (NaN: no frame before the fall)
         from .recorder import fall_summary
         falls = res["falls"]

@@ -96,6 +96,33 @@ def mirror_tables(env_cfg):
     return MirrorTables(obs, priv, act, layout_table(ACTION_BLOCKS, signed=False))
 
 
+def history_table(obs_table, H):
+    """The table of a row of H observation frames side by side [H * W] (the CTS student's history): the actor table tiled H times, frame h's columns staying in frame h."""
+    perm, sign = np.asarray(obs_table[0], np.int64), np.asarray(obs_table[1], np.float32)
+    W, H = len(perm), int(H)
+    if H < 1 or H * W > 32767:
+        raise ValueError("history_table: %r frames of %d columns (1 <= H, H * W <= 32767)" % (H, W))
+    return (np.concatenate([perm + h * W for h in range(H)]).astype(np.int16), np.tile(sign, H))
+
+
+def joint_sides():
+    """-> int32 [12]: +1 for a joint of a left leg, -1 of a right leg, in the joint block's order (LEGS x JOINTS)"""
+    return np.asarray([leg_side(leg) for leg in LEGS for _ in JOINTS], np.int32)
+
+
+def joint_kinds():
+    """-> int32 [12]: the joint's index in JOINTS (0 hip, 1 thigh, 2 calf), in the joint block's order"""
+    return np.asarray([k for _ in LEGS for k in range(len(JOINTS))], np.int32)
+
+
+def leg_side(name):
+    """+1 / -1 for a name that starts with a left / right leg of LEGS ("FL", "RL_foot", ...): the side is the leg name's second letter, as LEG_MIRROR swaps it"""
+    leg = str(name).upper()[:2]
+    if leg not in LEGS or leg[1] not in "LR" or LEG_MIRROR[leg][1] == leg[1]:
+        raise ValueError("%r does not start with one of the legs %s" % (name, ", ".join(LEGS)))
+    return 1 if leg[1] == "L" else -1
+
+
 def mirror_rows(x, table):
     """numpy: the mirror image of the rows of x [..., W]"""
     perm, sign = table

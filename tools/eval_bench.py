@@ -1,6 +1,6 @@
 """What one policy evaluation costs (utils/evaluator.py), and what the metric kernel saves over torch expressions.
 
-    python tools/eval_bench.py [--task go2_flat] [--reps 3] [--robust] [--ladder] [--maneuvers] [--sensors] [--blackbox] [--out profiles/eval_bench.json]
+    python tools/eval_bench.py [--task go2_flat] [--reps 3] [--robust] [--ladder] [--maneuvers] [--sensors] [--blackbox] [--asymmetry] [--out profiles/eval_bench.json]
 
 Measures, on cuda:0, with the task's default `evaluation` section (1024 robots, 1 s + 10 s):
   * wall time of evaluate() run eagerly and with the captured chunk of steps replayed (simulator re-creation, capture and the final host copy included: it is what
@@ -19,6 +19,9 @@ and its one-lane cursor launch) per back-to-back call on the evaluator's own buf
 --blackbox: a measurement of its own, written to profiles/blackbox_bench.json: evaluate() run eagerly with evaluation.blackbox off and on (2 robots kept per cell),
 alternating, at least three runs each in this one session — best, median, spread and every run —, and go2nn_blackbox_record (the frame kernel and the state kernel) per
 back-to-back call with no robot frozen, by the same method.
+--asymmetry: a measurement of its own, ADDED to profiles/asymmetry_bench.json under the task's name: evaluate() run eagerly with evaluation.asymmetry off and on,
+alternating, --reps runs each (at least five) in this one session — best, median, spread and every run —, and per back-to-back call on the evaluator's own buffers the
+three extra pieces of a step: the mirror launch, the policy's second forward and go2nn_asym_accumulate.
 Writes one JSON file and prints it."""
 import argparse
 import ctypes as C
@@ -143,6 +146,60 @@ def blackbox_main(a):
         e.close()
 
 
+def asymmetry_main(a):
+    """--asymmetry: what the asymmetry scores cost one evaluation, next to the plain evaluation of the same commit in the same session -> profiles/asymmetry_bench.json"""
+    env_cfg, train_cfg = task_registry.get_cfgs(a.task)
+    ev_cfg = class_to_dict(train_cfg.evaluation)
+    make = lambda on: PolicyEvaluator(env_cfg, dict(ev_cfg, asymmetry=on), task_class=task_registry.get_task_class(a.task), device="cuda:0")
+    evs = {"off": make(False), "on": make(True)}
+    torch.manual_seed(0)
+    pol = class_to_dict(train_cfg.policy)
+    if "history_length" in class_to_dict(train_cfg):          # the CTS family
+        from go2_rl_gym_amd.rsl_rl.modules.actor_critic_cts import ActorCriticCTS
+        ac = ActorCriticCTS(45, 263, 12, evs["on"].num_envs, int(train_cfg.history_length), **pol).to("cuda:0")
+    else:
+        from go2_rl_gym_amd.rsl_rl.modules import ActorCritic
+        ac = ActorCritic(45, 263, 12, **{k: v for k, v in pol.items() if k in ("actor_hidden_dims", "critic_hidden_dims", "activation", "init_noise_std")}).to("cuda:0")
+    res = {k: ev.evaluate(ac, use_graph=False) for k, ev in evs.items()}
+    assert res["on"]["table"].tobytes() == res["off"]["table"].tobytes() and "asymmetry" not in res["off"]
+    ev = evs["on"]
+    pol_, st, N = ev._policy, ev._stream(), ev.num_envs
+    from go2_rl_gym_amd._nn import mirror_rows
+    with torch.inference_mode():
+        jobs, hist_m = ev._asym_jobs(pol_, ev.env.obs_buf)
+        ain = ev._asym_in()
+        act = pol_.act(ev.env.obs_buf)
+        pieces = {"mirror_rows": lambda: mirror_rows(ev.nn, jobs, 1, N, st), "act_mirrored": lambda: pol_.act_mirrored(ev.asym_obs[1], hist_m),
+                  "asym_accumulate": lambda: ev.nn.go2nn_asym_accumulate(C.byref(ain), C.c_void_p(act.data_ptr()), C.c_void_p(act.data_ptr()), C.c_void_p(ev.atable.data_ptr()), N, st)}
+        cost = {}
+        for name, fn in pieces.items():
+            timed(fn, 20)
+            dev_us, wall_us = timed(fn, 200)
+            cost[name] = {"device_us_per_call_back_to_back": dev_us, "host_us_per_call": wall_us}
+    entry = {"task": a.task, "device": torch.cuda.get_device_name(0), "num_envs": N, "steps": ev.warmup_steps + ev.steps, "policy": type(ac).__name__,
+             "overall": {k: v for k, v in res["on"]["asymmetry"]["overall"].items()}, "per_step": cost}
+    if not a.kernel_only:
+        walls = {k: [] for k in evs}
+        for _ in range(max(a.reps, 5)):          # alternating, in this one session
+            for k, e in evs.items():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                e.evaluate(ac, use_graph=False)
+                walls[k].append((time.perf_counter() - t0) * 1e3)
+        entry["evaluate_wall_ms_eager"] = {k: {"best": min(w), "median": statistics.median(w), "spread": max(w) - min(w), "all": w} for k, w in walls.items()}
+        out = {}
+        if os.path.exists(a.out):
+            with open(a.out) as f:
+                out = json.load(f)
+        out[a.task] = entry
+        os.makedirs(os.path.dirname(a.out), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(out, f, indent=1)
+    print(json.dumps({a.task: entry}))
+    for e in evs.values():
+        e.close()
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--task", default="go2_flat")
@@ -153,9 +210,12 @@ def main():
     p.add_argument("--maneuvers", action="store_true")
     p.add_argument("--sensors", action="store_true")
     p.add_argument("--blackbox", action="store_true")
+    p.add_argument("--asymmetry", action="store_true")
     p.add_argument("--out", default=None)
     a = p.parse_args()
-    a.out = a.out or os.path.join(ROOT, "profiles", "blackbox_bench.json" if a.blackbox else "eval_bench.json")
+    a.out = a.out or os.path.join(ROOT, "profiles", "asymmetry_bench.json" if a.asymmetry else "blackbox_bench.json" if a.blackbox else "eval_bench.json")
+    if a.asymmetry:
+        return asymmetry_main(a)
     if a.blackbox:
         return blackbox_main(a)
     if a.sensors:
