@@ -1,7 +1,8 @@
 // go2nn_asym.h — the evaluator's left-right asymmetry scores (include/go2nn.h: go2nn_asym_*, added within ABI 7; go2_rl_gym_amd/utils/evaluator.py, `evaluation.asymmetry`).
-// Included at the end of go2nn_impl.cpp after go2nn_gait.h (FAIL, HIPCHK are the former's helpers; EVAL_FN, eval_b, eval_group_sum go2nn_eval.h's).
+// Included at the end of go2nn_impl.cpp after go2nn_gait.h (FAIL is the former's helper; EVAL_FN, EVAL_MEMBER, eval_f, eval_b, eval_field_fault and the launch scaffold —
+// eval_table_begin, eval_per_env, eval_reduce over eval_group_sum and, for the EQ_MAX column, eval_group_max — go2nn_eval.h's).
 //
-// One launch per env step, one lane per env, the twelve joints and the four feet unrolled inside the lane; no LDS, no atomics, no cross-lane traffic.  go2nn_asym_accumulate
+// One launch per env step (eval_per_env_kernel<AsymAccumulate>), one lane per env, the twelve joints and the four feet unrolled inside the lane; no LDS, no atomics, no cross-lane traffic.  go2nn_asym_accumulate
 // (after the step) reads per env the action and the action of the mirrored observation (2 x 12 floats, row-major: a lane's 48 bytes are three 16-byte pieces of lines its
 // neighbours share), three command components, twelve torques and joint velocities, four vertical contact forces and one flag, and read-modify-writes the env's column of
 // the table [GO2NN_ASYM_NUM, N]: with the HIP simulator's field-major buffers (env stride 1) consecutive lanes touch consecutive addresses of every component and of every
@@ -91,55 +92,19 @@ struct AsymTerm {
 static_assert(GO2NN_ASYM_STEP == 0 && GO2NN_ASYM_NUM == GO2NN_ASYM_PAIR0 + 8, "STEP is the first row; the four (L, R) pairs are the last eight");
 #define ASYM_OUT_EQ_MAX (GO2NN_ASYM_OUT_ROW0 + GO2NN_ASYM_EQ_MAX - 1)
 
-// The largest term(e) over the envs e of group g (0 for an empty group: the terms are >= 0), eval_group_sum's scheme with max in place of +: any order gives the same bits.
-#ifdef GO2_EMU
-template <class Term> static inline double asym_group_max(const int32_t* group, int N, int g, Term term) {
-  double m = 0.0;
-  for (int e = 0; e < N; ++e)
-    if (group[e] == g) m = fmax(m, term(e));
-  return m;
-}
-#else
-template <class Term> __device__ __forceinline__ double asym_group_max(const int32_t* group, int N, int g, Term term) {
-  __shared__ double part[EVAL_THREADS];
-  const int t = threadIdx.x;
-  double m = 0.0;
-  for (int e = t; e < N; e += EVAL_THREADS)
-    if (group[e] == g) m = fmax(m, term(e));
-  part[t] = m;
-  __syncthreads();
-  for (int w = EVAL_THREADS / 2; w > 0; w >>= 1) {
-    if (t < w) part[t] = fmax(part[t], part[t + w]);
-    __syncthreads();
-  }
-  return part[0];
-}
-
-__global__ void __launch_bounds__(EVAL_THREADS) go2nn_asym_begin_kernel(float* table, int N, float start) {
-  const long long k = (long long)blockIdx.x * EVAL_THREADS + threadIdx.x;
-  if (k < (long long)GO2NN_ASYM_NUM * N) table[k] = k < N ? start : 0.f;          // (STEP is the table's first N floats)
-}
-__global__ void __launch_bounds__(EVAL_THREADS) go2nn_asym_accumulate_kernel(const Go2nnAsymIn in, const float* actions, const float* mirrored, float* table, int N) {
-  const int e = blockIdx.x * EVAL_THREADS + threadIdx.x;
-  if (e < N) asym_accumulate_env(in, actions, mirrored, table, N, e);
-}
-// grid = (G, GO2NN_ASYM_OUT_NUM); the branch is uniform over the workgroup
-__global__ void __launch_bounds__(EVAL_THREADS) go2nn_asym_reduce_kernel(const float* table, const int32_t* group, int N, double* out) {
-  const int g = blockIdx.x, c = blockIdx.y;
-  const AsymTerm term{table, N, c};
-  const double s = c == ASYM_OUT_EQ_MAX ? asym_group_max(group, N, g, term) : eval_group_sum(group, N, g, term);
-  if (threadIdx.x == 0) out[(long long)g * GO2NN_ASYM_OUT_NUM + c] = s;
-}
-#endif
+struct AsymAccumulate {
+  Go2nnAsymIn in; const float *actions, *mirrored; float* table; int N;
+  EVAL_MEMBER void operator()(int e) const { asym_accumulate_env(in, actions, mirrored, table, N, e); }
+};
 
 static const char* asym_in_bad(const Go2nnAsymIn* in) {
-  const Go2nnEvalField* f[] = {&in->commands, &in->dof_state, &in->torques, &in->contact_forces, &in->reset_buf};
-  for (const Go2nnEvalField* x : f) {
-    if (!x->p) return "a null buffer pointer";
-    if (x->env_stride < 1) return "a field with an env stride < 1";
-    if (x != &in->reset_buf && x->comp_stride < 1) return "a vector field with a component stride < 1";
-  }
-  if (in->reset_buf.comp_stride < 0) return "a vector field with a component stride < 1";
+  const Go2nnEvalField* f[] = {&in->commands, &in->dof_state, &in->torques, &in->contact_forces, &in->reset_buf};          // (reset_buf, the per-env field, comes last)
+  for (const Go2nnEvalField* x : f)
+    switch (eval_field_fault(*x, x == &in->reset_buf ? 0 : 1)) {
+      case EVAL_FIELD_NULL: return "a null buffer pointer";
+      case EVAL_FIELD_ENV_STRIDE: return "a field with an env stride < 1";
+      case EVAL_FIELD_COMP_STRIDE: return "a vector field with a component stride < 1";
+    }
   if (in->dof_vel_offset < 1) return "dof_vel_offset < 1";
   if (in->contact_body_stride < 1) return "a body stride < 1";
   for (int k = 0; k < 4; ++k) {
@@ -160,48 +125,22 @@ extern "C" {
 
 int go2nn_asym_begin(float* table, int32_t N, int32_t start, void* stream) {
   if (!table || N < 1) FAIL(GO2NN_EINVAL, "asym begin: bad argument (a table and N >= 1)");
-  const long long n = (long long)GO2NN_ASYM_NUM * N;
-#ifdef GO2_EMU
-  (void)stream;
-  for (long long k = 0; k < n; ++k) table[k] = 0.f;
-  for (int e = 0; e < N; ++e) table[(long long)GO2NN_ASYM_STEP * N + e] = (float)start;
-#else
-  hipLaunchKernelGGL(go2nn_asym_begin_kernel, dim3((unsigned)((n + EVAL_THREADS - 1) / EVAL_THREADS)), dim3(EVAL_THREADS), 0, (hipStream_t)stream, table, N, (float)start);
-  HIPCHK(hipGetLastError());
-#endif
-  return 0;
+  return eval_table_begin(table, GO2NN_ASYM_NUM, N, (float)start, stream);          // (STEP is the table's first row: the static_assert above)
 }
 
 int go2nn_asym_accumulate(const Go2nnAsymIn* in, const float* actions, const float* mirrored_actions, float* table, int32_t N, void* stream) {
   if (!in || !actions || !mirrored_actions || !table || N < 1) FAIL(GO2NN_EINVAL, "asym accumulate: null argument or N < 1");
   if (const char* bad = asym_in_bad(in)) FAIL(GO2NN_EINVAL, "asym accumulate: %s", bad);
-#ifdef GO2_EMU
-  (void)stream;
-  for (int e = 0; e < N; ++e) asym_accumulate_env(*in, actions, mirrored_actions, table, N, e);
-#else
-  hipLaunchKernelGGL(go2nn_asym_accumulate_kernel, dim3((unsigned)((N + EVAL_THREADS - 1) / EVAL_THREADS)), dim3(EVAL_THREADS), 0, (hipStream_t)stream, *in, actions,
-                     mirrored_actions, table, N);
-  HIPCHK(hipGetLastError());
-#endif
-  return 0;
+  return eval_per_env(AsymAccumulate{*in, actions, mirrored_actions, table, N}, N, stream);
 }
 
 int go2nn_asym_reduce(const float* table, const int32_t* group, int32_t N, int32_t G, double* out, void* stream) {
   if (!table || !group || !out || N < 1 || G < 1 || G > 65535) FAIL(GO2NN_EINVAL, "asym reduce: bad argument (1 <= G <= 65535)");
 #ifdef GO2_EMU
-  (void)stream;
   for (int e = 0; e < N; ++e)          // the host build can read the ids (the device build ignores those outside [0, G))
     if (group[e] < 0 || group[e] >= G) FAIL(GO2NN_EINVAL, "asym reduce: group[%d] = %d outside [0, %d)", e, group[e], G);
-  for (int g = 0; g < G; ++g)
-    for (int c = 0; c < GO2NN_ASYM_OUT_NUM; ++c) {
-      const AsymTerm term{table, N, c};
-      out[(long long)g * GO2NN_ASYM_OUT_NUM + c] = c == ASYM_OUT_EQ_MAX ? asym_group_max(group, N, g, term) : eval_group_sum(group, N, g, term);
-    }
-#else
-  hipLaunchKernelGGL(go2nn_asym_reduce_kernel, dim3((unsigned)G, GO2NN_ASYM_OUT_NUM), dim3(EVAL_THREADS), 0, (hipStream_t)stream, table, group, N, out);
-  HIPCHK(hipGetLastError());
 #endif
-  return 0;
+  return eval_reduce<ASYM_OUT_EQ_MAX>(AsymTerm{table, N, 0}, group, N, G, GO2NN_ASYM_OUT_NUM, out, stream);          // EQ_MAX: the group's max (eval_group_max), every other column its sum
 }
 
 }  // extern "C"

@@ -1,11 +1,17 @@
-// go2nn_eval.h — the policy evaluator's metric kernels (include/go2nn.h: go2nn_eval_*, added within ABI 7; go2_rl_gym_amd/utils/evaluator.py).
-// Included at the end of go2nn_impl.cpp (FAIL, HIPCHK are its helpers).
+// go2nn_eval.h — the policy evaluator's metric kernels (include/go2nn.h: go2nn_eval_*, added within ABI 7; go2_rl_gym_amd/utils/evaluator.py) and the launch scaffold that
+// every scoring family shares (go2nn_robust.h, go2nn_ladder.h, go2nn_maneuver.h, go2nn_gait.h, go2nn_asym.h).  Included at the end of go2nn_impl.cpp (FAIL, HIPCHK are its helpers).
 //
 // go2nn_eval_accumulate: one launch per env step, one lane per env.  A lane reads its env's ~75 input values through (env stride, component stride) pairs — with the
 // HIP simulator's field-major buffers consecutive lanes read consecutive addresses of every component, i.e. each load instruction of a wave is one dense 256-byte line —
 // and read-modify-writes its column of the metric-major accumulator [GO2NN_EVAL_NUM, N] (dense again).  No LDS, no atomics, no cross-lane traffic: a streaming kernel of
 // ~0.4 KB per env.  go2nn_eval_reduce: one workgroup per (group, output column): lane t adds the envs t, t + 256, ... of the group in fp64, then a fixed LDS tree over the
 // 256 partials — the order is a function of (N, G) only.  The host build runs the same element function and the same summation order in plain loops.
+//
+// THE SCAFFOLD.  A family writes one element function per env and one Term functor per reduce; the three launch shapes around them live here, once, with their host loops:
+//   eval_per_env(f, N)                       grid = ceil(N / 256), lane e calls f(e): eval_per_env_kernel<EvalAccumulate>, <LadderAccumulate>, ... in a kernel trace
+//   eval_table_begin(table, rows, N, start)  grid = ceil(rows N / 256), one float per lane: row 0 (a family's STEP row) = start, every other row = 0
+//   eval_reduce(term, group, N, G, cols)     grid = (G, cols), workgroup (g, c) writes out[g cols + c] = eval_group_sum of the Term at column c (eval_group_max for MAX_COL)
+// eval_field_fault is the one statement of what a Go2nnEvalField must satisfy; each family words its own messages around it.
 #ifndef GO2NN_EVAL_H
 #define GO2NN_EVAL_H
 
@@ -55,6 +61,11 @@ EVAL_FN void eval_accumulate_env(const Go2nnEvalIn& in, float* acc, int N, int e
   for (int m = 0; m < GO2NN_EVAL_NUM; ++m) acc[(long long)m * N + e] += t[m];
 }
 
+struct EvalAccumulate {
+  Go2nnEvalIn in; float* acc; int N;
+  EVAL_MEMBER void operator()(int e) const { eval_accumulate_env(in, acc, N, e); }
+};
+
 // what env e contributes to output column c of its group: the ten accumulators, 1 (the group's size), 1 if the env never fell
 EVAL_FN double eval_reduce_term(const float* acc, int N, int e, int c) {
   if (c < GO2NN_EVAL_NUM) return (double)acc[(long long)c * N + e];
@@ -67,8 +78,53 @@ struct EvalTerm {
   EVAL_MEMBER double operator()(int e) const { return eval_reduce_term(acc, N, e, c); }
 };
 
+// What is wrong with a field, in the order it is looked at: no pointer, an env stride < 1, a component stride < min_comp (1 for a vector field; 0 for a per-env field, which
+// has no second component to step to).
+enum { EVAL_FIELD_OK = 0, EVAL_FIELD_NULL, EVAL_FIELD_ENV_STRIDE, EVAL_FIELD_COMP_STRIDE };
+static int eval_field_fault(const Go2nnEvalField& f, int min_comp) {
+  return !f.p ? EVAL_FIELD_NULL : f.env_stride < 1 ? EVAL_FIELD_ENV_STRIDE : f.comp_stride < min_comp ? EVAL_FIELD_COMP_STRIDE : EVAL_FIELD_OK;
+}
+
+// f(e) for every env e < N, one lane per env (host: in env order).  F holds by value what the lane needs — the family's In struct, its pointers, N — and is a named type at
+// namespace scope, so that the instantiation has a readable name.
+#ifndef GO2_EMU
+template <class F> __global__ void __launch_bounds__(EVAL_THREADS) eval_per_env_kernel(const F f, int N) {
+  const int e = blockIdx.x * EVAL_THREADS + threadIdx.x;
+  if (e < N) f(e);
+}
+#endif
+template <class F> static int eval_per_env(const F& f, int N, void* stream) {
+#ifdef GO2_EMU
+  (void)stream;
+  for (int e = 0; e < N; ++e) f(e);
+#else
+  hipLaunchKernelGGL(eval_per_env_kernel<F>, dim3((unsigned)((N + EVAL_THREADS - 1) / EVAL_THREADS)), dim3(EVAL_THREADS), 0, (hipStream_t)stream, f, N);
+  HIPCHK(hipGetLastError());
+#endif
+  return 0;
+}
+
+// table [rows, N]: row 0 = start, every other row = 0
+#ifndef GO2_EMU
+__global__ void __launch_bounds__(EVAL_THREADS) eval_table_begin_kernel(float* table, long long n, int N, float start) {
+  const long long k = (long long)blockIdx.x * EVAL_THREADS + threadIdx.x;
+  if (k < n) table[k] = k < N ? start : 0.f;
+}
+#endif
+static int eval_table_begin(float* table, int rows, int N, float start, void* stream) {
+  const long long n = (long long)rows * N;
+#ifdef GO2_EMU
+  (void)stream;
+  for (long long k = 0; k < n; ++k) table[k] = k < N ? start : 0.f;
+#else
+  hipLaunchKernelGGL(eval_table_begin_kernel, dim3((unsigned)((n + EVAL_THREADS - 1) / EVAL_THREADS)), dim3(EVAL_THREADS), 0, (hipStream_t)stream, table, n, N, start);
+  HIPCHK(hipGetLastError());
+#endif
+  return 0;
+}
+
 // The sum of term(e) over the envs e of group g, in an order that depends on N only: partial t adds the envs t, t + 256, ... in fp64, then a fixed tree over the 256
-// partials.  Device: called by every thread of a 256-thread workgroup, the sum is valid in thread 0.  Shared by go2nn_eval_reduce and go2nn_robust_reduce (go2nn_robust.h).
+// partials.  Device: called by every thread of a 256-thread workgroup, the sum is valid in thread 0.  Every family's reduce goes through it (eval_reduce below).
 #ifdef GO2_EMU
 template <class Term> static inline double eval_group_sum(const int32_t* group, int N, int g, Term term) {
   double part[EVAL_THREADS];
@@ -99,28 +155,63 @@ template <class Term> __device__ __forceinline__ double eval_group_sum(const int
 }
 #endif
 
-#ifndef GO2_EMU
-__global__ void __launch_bounds__(EVAL_THREADS) go2nn_eval_accumulate_kernel(const Go2nnEvalIn in, float* acc, int N) {
-  const int e = blockIdx.x * EVAL_THREADS + threadIdx.x;
-  if (e < N) eval_accumulate_env(in, acc, N, e);
+// The largest term(e) over the envs e of group g (0 for an empty group: the terms are >= 0), eval_group_sum's scheme with max in place of +: any order gives the same bits.
+#ifdef GO2_EMU
+template <class Term> static inline double eval_group_max(const int32_t* group, int N, int g, Term term) {
+  double m = 0.0;
+  for (int e = 0; e < N; ++e)
+    if (group[e] == g) m = fmax(m, term(e));
+  return m;
 }
-__global__ void __launch_bounds__(EVAL_THREADS) go2nn_eval_clear_kernel(float* acc, long long n) {
-  const long long k = (long long)blockIdx.x * EVAL_THREADS + threadIdx.x;
-  if (k < n) acc[k] = 0.f;
-}
-// grid = (G, GO2NN_EVAL_NUM + 2)
-__global__ void __launch_bounds__(EVAL_THREADS) go2nn_eval_reduce_kernel(const float* acc, const int32_t* group, int N, double* out) {
-  const int g = blockIdx.x, c = blockIdx.y;
-  const double s = eval_group_sum(group, N, g, EvalTerm{acc, N, c});
-  if (threadIdx.x == 0) out[(long long)g * (GO2NN_EVAL_NUM + 2) + c] = s;
+#else
+template <class Term> __device__ __forceinline__ double eval_group_max(const int32_t* group, int N, int g, Term term) {
+  __shared__ double part[EVAL_THREADS];
+  const int t = threadIdx.x;
+  double m = 0.0;
+  for (int e = t; e < N; e += EVAL_THREADS)
+    if (group[e] == g) m = fmax(m, term(e));
+  part[t] = m;
+  __syncthreads();
+  for (int w = EVAL_THREADS / 2; w > 0; w >>= 1) {
+    if (t < w) part[t] = fmax(part[t], part[t + w]);
+    __syncthreads();
+  }
+  return part[0];
 }
 #endif
+
+// out[g * cols + c] for every group g < G and column c < cols: the group's sum of the Term at column c (a Term has a member `c`, set here), or its max where c == MAX_COL.
+// MAX_COL = -1 (no such column) instantiates no max tree, so no second LDS array; with one, the branch is uniform over the workgroup.
+template <int MAX_COL, class Term> EVAL_FN double eval_group_value(const int32_t* group, int N, int g, const Term& term) {
+  if constexpr (MAX_COL >= 0)
+    if (term.c == MAX_COL) return eval_group_max(group, N, g, term);
+  return eval_group_sum(group, N, g, term);
+}
+#ifndef GO2_EMU
+template <int MAX_COL, class Term> __global__ void __launch_bounds__(EVAL_THREADS) eval_reduce_kernel(Term term, const int32_t* group, int N, int cols, double* out) {
+  const int g = blockIdx.x;
+  term.c = blockIdx.y;
+  const double s = eval_group_value<MAX_COL>(group, N, g, term);
+  if (threadIdx.x == 0) out[(long long)g * cols + term.c] = s;
+}
+#endif
+template <int MAX_COL = -1, class Term> static int eval_reduce(Term term, const int32_t* group, int N, int G, int cols, double* out, void* stream) {
+#ifdef GO2_EMU
+  (void)stream;
+  for (int g = 0; g < G; ++g)
+    for (term.c = 0; term.c < cols; ++term.c) out[(long long)g * cols + term.c] = eval_group_value<MAX_COL>(group, N, g, term);
+#else
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(eval_reduce_kernel<MAX_COL, Term>), dim3((unsigned)G, (unsigned)cols), dim3(EVAL_THREADS), 0, (hipStream_t)stream, term, group, N, cols, out);
+  HIPCHK(hipGetLastError());
+#endif
+  return 0;
+}
 
 static int eval_in_ok(const Go2nnEvalIn* in) {
   const Go2nnEvalField* f[] = {&in->commands, &in->base_lin_vel, &in->base_ang_vel, &in->projected_gravity, &in->dof_state, &in->torques, &in->actions, &in->last_actions,
                                &in->reset_buf, &in->time_out_buf};
   for (const Go2nnEvalField* x : f)
-    if (!x->p || x->env_stride < 1 || x->comp_stride < 0) return 0;
+    if (eval_field_fault(*x, 0)) return 0;
   return in->dof_limits != nullptr && in->dof_vel_offset >= 1;
 }
 
@@ -128,40 +219,17 @@ extern "C" {
 
 int go2nn_eval_clear(float* acc, int32_t N, void* stream) {
   if (!acc || N < 1) FAIL(GO2NN_EINVAL, "eval clear: bad argument");
-  const long long n = (long long)GO2NN_EVAL_NUM * N;
-#ifdef GO2_EMU
-  (void)stream;
-  for (long long k = 0; k < n; ++k) acc[k] = 0.f;
-#else
-  hipLaunchKernelGGL(go2nn_eval_clear_kernel, dim3((unsigned)((n + EVAL_THREADS - 1) / EVAL_THREADS)), dim3(EVAL_THREADS), 0, (hipStream_t)stream, acc, n);
-  HIPCHK(hipGetLastError());
-#endif
-  return 0;
+  return eval_table_begin(acc, GO2NN_EVAL_NUM, N, 0.f, stream);
 }
 
 int go2nn_eval_accumulate(const Go2nnEvalIn* in, float* acc, int32_t N, void* stream) {
   if (!in || !acc || N < 1 || !eval_in_ok(in)) FAIL(GO2NN_EINVAL, "eval accumulate: bad argument (every field needs a pointer, an env stride >= 1 and a component stride >= 0)");
-#ifdef GO2_EMU
-  (void)stream;
-  for (int e = 0; e < N; ++e) eval_accumulate_env(*in, acc, N, e);
-#else
-  hipLaunchKernelGGL(go2nn_eval_accumulate_kernel, dim3((unsigned)((N + EVAL_THREADS - 1) / EVAL_THREADS)), dim3(EVAL_THREADS), 0, (hipStream_t)stream, *in, acc, N);
-  HIPCHK(hipGetLastError());
-#endif
-  return 0;
+  return eval_per_env(EvalAccumulate{*in, acc, N}, N, stream);
 }
 
 int go2nn_eval_reduce(const float* acc, const int32_t* group, int32_t N, int32_t G, double* out, void* stream) {
   if (!acc || !group || !out || N < 1 || G < 1 || G > 65535) FAIL(GO2NN_EINVAL, "eval reduce: bad argument (1 <= G <= 65535)");
-#ifdef GO2_EMU
-  (void)stream;
-  for (int g = 0; g < G; ++g)
-    for (int c = 0; c < GO2NN_EVAL_NUM + 2; ++c) out[(long long)g * (GO2NN_EVAL_NUM + 2) + c] = eval_group_sum(group, N, g, EvalTerm{acc, N, c});
-#else
-  hipLaunchKernelGGL(go2nn_eval_reduce_kernel, dim3((unsigned)G, GO2NN_EVAL_NUM + 2), dim3(EVAL_THREADS), 0, (hipStream_t)stream, acc, group, N, out);
-  HIPCHK(hipGetLastError());
-#endif
-  return 0;
+  return eval_reduce(EvalTerm{acc, N, 0}, group, N, G, GO2NN_EVAL_NUM + 2, out, stream);
 }
 
 }  // extern "C"

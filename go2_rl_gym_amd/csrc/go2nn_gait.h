@@ -1,7 +1,8 @@
 // go2nn_gait.h — the evaluator's gait scores (include/go2nn.h: go2nn_gait_*, added within ABI 7; go2_rl_gym_amd/utils/evaluator.py, `evaluation.gait`).
-// Included at the end of go2nn_impl.cpp after go2nn_trace.h (FAIL, HIPCHK are the former's helpers; EVAL_FN, eval_b, eval_group_sum go2nn_eval.h's).
+// Included at the end of go2nn_impl.cpp after go2nn_trace.h (FAIL is the former's helper; EVAL_FN, EVAL_MEMBER, eval_b, eval_field_fault and the launch scaffold —
+// eval_table_begin, eval_per_env, eval_reduce over eval_group_sum — go2nn_eval.h's).
 //
-// One launch per env step, one lane per env, the four feet unrolled inside the lane; no LDS, no atomics, no cross-lane traffic.  go2nn_gait_accumulate (after the step) reads
+// One launch per env step (eval_per_env_kernel<GaitAccumulate>), one lane per env, the four feet unrolled inside the lane; no LDS, no atomics, no cross-lane traffic.  go2nn_gait_accumulate (after the step) reads
 // per foot four floats (force z; world z, vx, vy of the foot body) and one flag, and read-modify-writes the env's column of the table [GO2NN_GAIT_NUM, N]: with the HIP
 // simulator's field-major buffers (env stride 1) consecutive lanes touch consecutive addresses of every component and of every table row, i.e. each load / store instruction
 // of a wave is one dense 256-byte line, like ladder_accumulate_env.  Most rows move only on a touchdown or a lift-off; a plain frame touches the foot's PREV and one of
@@ -114,28 +115,16 @@ struct GaitTerm {
 static_assert(GO2NN_GAIT_DIAGONAL == GO2NN_GAIT_SUPPORT0 + 5 && GO2NN_GAIT_OUT_DIAGONAL == GO2NN_GAIT_OUT_SUPPORT0 + 5, "DIAGONAL follows SUPPORT4 in the table and in the output");
 static_assert(GO2NN_GAIT_FOOT_ROWS - GO2NN_GAIT_F_ACC_FIRST == GO2NN_GAIT_OUT_FOOT_COLS - 1, "the foot's accumulator rows are the output's foot columns after USED, in order");
 
-#ifndef GO2_EMU
-__global__ void __launch_bounds__(EVAL_THREADS) go2nn_gait_begin_kernel(float* table, int N, float start) {
-  const long long k = (long long)blockIdx.x * EVAL_THREADS + threadIdx.x;
-  static_assert(GO2NN_GAIT_STEP == 0, "the STEP row is the table's first N floats");
-  if (k < (long long)GO2NN_GAIT_NUM * N) table[k] = k < N ? start : 0.f;
-}
-__global__ void __launch_bounds__(EVAL_THREADS) go2nn_gait_accumulate_kernel(const Go2nnGaitIn in, float* table, int N) {
-  const int e = blockIdx.x * EVAL_THREADS + threadIdx.x;
-  if (e < N) gait_accumulate_env(in, table, N, e);
-}
-// grid = (G, GO2NN_GAIT_OUT_NUM)
-__global__ void __launch_bounds__(EVAL_THREADS) go2nn_gait_reduce_kernel(const float* table, const int32_t* group, int N, double* out) {
-  const int g = blockIdx.x, c = blockIdx.y;
-  const double s = eval_group_sum(group, N, g, GaitTerm{table, N, c});
-  if (threadIdx.x == 0) out[(long long)g * GO2NN_GAIT_OUT_NUM + c] = s;
-}
-#endif
+struct GaitAccumulate {
+  Go2nnGaitIn in; float* table; int N;
+  EVAL_MEMBER void operator()(int e) const { gait_accumulate_env(in, table, N, e); }
+};
 
 static const char* gait_in_bad(const Go2nnGaitIn* in) {
-  if (!in->rigid_body_states.p || !in->contact_forces.p || !in->reset_buf.p) return "a null buffer pointer";
-  if (in->rigid_body_states.env_stride < 1 || in->contact_forces.env_stride < 1 || in->reset_buf.env_stride < 1) return "a field with an env stride < 1";
-  if (in->rigid_body_states.comp_stride < 1 || in->contact_forces.comp_stride < 1 || in->reset_buf.comp_stride < 0) return "a vector field with a component stride < 1";
+  const int rb = eval_field_fault(in->rigid_body_states, 1), cf = eval_field_fault(in->contact_forces, 1), reset = eval_field_fault(in->reset_buf, 0);
+  if (rb == EVAL_FIELD_NULL || cf == EVAL_FIELD_NULL || reset == EVAL_FIELD_NULL) return "a null buffer pointer";
+  if (rb == EVAL_FIELD_ENV_STRIDE || cf == EVAL_FIELD_ENV_STRIDE || reset == EVAL_FIELD_ENV_STRIDE) return "a field with an env stride < 1";
+  if (rb || cf || reset) return "a vector field with a component stride < 1";
   if (in->rigid_body_stride < 1 || in->contact_body_stride < 1) return "a body stride < 1";
   for (int f = 0; f < 4; ++f)
     if (in->foot_body[f] < 0) return "foot_body < 0";
@@ -149,42 +138,19 @@ extern "C" {
 
 int go2nn_gait_begin(float* table, int32_t N, int32_t start, void* stream) {
   if (!table || N < 1) FAIL(GO2NN_EINVAL, "gait begin: bad argument (a table and N >= 1)");
-  const long long n = (long long)GO2NN_GAIT_NUM * N;
-#ifdef GO2_EMU
-  (void)stream;
-  for (long long k = 0; k < n; ++k) table[k] = 0.f;
-  for (int e = 0; e < N; ++e) table[(long long)GO2NN_GAIT_STEP * N + e] = (float)start;
-#else
-  hipLaunchKernelGGL(go2nn_gait_begin_kernel, dim3((unsigned)((n + EVAL_THREADS - 1) / EVAL_THREADS)), dim3(EVAL_THREADS), 0, (hipStream_t)stream, table, N, (float)start);
-  HIPCHK(hipGetLastError());
-#endif
-  return 0;
+  static_assert(GO2NN_GAIT_STEP == 0, "the STEP row is the table's first N floats");
+  return eval_table_begin(table, GO2NN_GAIT_NUM, N, (float)start, stream);
 }
 
 int go2nn_gait_accumulate(const Go2nnGaitIn* in, float* table, int32_t N, void* stream) {
   if (!in || !table || N < 1) FAIL(GO2NN_EINVAL, "gait accumulate: null argument or N < 1");
   if (const char* bad = gait_in_bad(in)) FAIL(GO2NN_EINVAL, "gait accumulate: %s", bad);
-#ifdef GO2_EMU
-  (void)stream;
-  for (int e = 0; e < N; ++e) gait_accumulate_env(*in, table, N, e);
-#else
-  hipLaunchKernelGGL(go2nn_gait_accumulate_kernel, dim3((unsigned)((N + EVAL_THREADS - 1) / EVAL_THREADS)), dim3(EVAL_THREADS), 0, (hipStream_t)stream, *in, table, N);
-  HIPCHK(hipGetLastError());
-#endif
-  return 0;
+  return eval_per_env(GaitAccumulate{*in, table, N}, N, stream);
 }
 
 int go2nn_gait_reduce(const float* table, const int32_t* group, int32_t N, int32_t G, double* out, void* stream) {
   if (!table || !group || !out || N < 1 || G < 1 || G > 65535) FAIL(GO2NN_EINVAL, "gait reduce: bad argument (1 <= G <= 65535)");
-#ifdef GO2_EMU
-  (void)stream;
-  for (int g = 0; g < G; ++g)
-    for (int c = 0; c < GO2NN_GAIT_OUT_NUM; ++c) out[(long long)g * GO2NN_GAIT_OUT_NUM + c] = eval_group_sum(group, N, g, GaitTerm{table, N, c});
-#else
-  hipLaunchKernelGGL(go2nn_gait_reduce_kernel, dim3((unsigned)G, GO2NN_GAIT_OUT_NUM), dim3(EVAL_THREADS), 0, (hipStream_t)stream, table, group, N, out);
-  HIPCHK(hipGetLastError());
-#endif
-  return 0;
+  return eval_reduce(GaitTerm{table, N, 0}, group, N, G, GO2NN_GAIT_OUT_NUM, out, stream);
 }
 
 }  // extern "C"

@@ -1,7 +1,8 @@
 // go2nn_ladder.h — the evaluator's terrain-difficulty ladder (include/go2nn.h: go2nn_ladder_*, added within ABI 7; go2_rl_gym_amd/utils/evaluator.py).
-// Included at the end of go2nn_impl.cpp after go2nn_robust.h (FAIL, HIPCHK are the former's helpers; EVAL_FN, eval_f, eval_b, eval_group_sum go2nn_eval.h's).
+// Included at the end of go2nn_impl.cpp after go2nn_robust.h (FAIL is the former's helper; EVAL_FN, EVAL_MEMBER, eval_f, eval_b, eval_field_fault and the launch scaffold —
+// eval_table_begin, eval_per_env, eval_reduce over eval_group_sum — go2nn_eval.h's).
 //
-// One launch per env step, one lane per env, no LDS, no atomics, no cross-lane traffic.  go2nn_ladder_accumulate (after the step) reads two root-state floats and two flags
+// One launch per env step (eval_per_env_kernel<LadderAccumulate>), one lane per env, no LDS, no atomics, no cross-lane traffic.  go2nn_ladder_accumulate (after the step) reads two root-state floats and two flags
 // and read-modify-writes the env's column of the table [GO2NN_LADDER_NUM, N]: with the HIP simulator's field-major buffers (env stride 1) consecutive lanes touch consecutive
 // addresses of every component and of every table row, i.e. each load / store instruction of a wave is one dense 256-byte line.  8 B + 2 B read and 24 B read-modify-written
 // per env: launch-bound at evaluation sizes (1024 lanes = 16 waves).  Distances are compared squared: there is no sqrt in the per-step kernel (the reduce takes one per env,
@@ -55,28 +56,16 @@ struct LadderTerm {
   }
 };
 
-#ifndef GO2_EMU
-__global__ void __launch_bounds__(EVAL_THREADS) go2nn_ladder_begin_kernel(float* table, int N, float start) {
-  const long long k = (long long)blockIdx.x * EVAL_THREADS + threadIdx.x;
-  static_assert(GO2NN_LADDER_STEP == 0, "the STEP row is the table's first N floats");
-  if (k < (long long)GO2NN_LADDER_NUM * N) table[k] = k < N ? start : 0.f;
-}
-__global__ void __launch_bounds__(EVAL_THREADS) go2nn_ladder_accumulate_kernel(const Go2nnLadderIn in, float* table, int N) {
-  const int e = blockIdx.x * EVAL_THREADS + threadIdx.x;
-  if (e < N) ladder_accumulate_env(in, table, N, e);
-}
-// grid = (G, GO2NN_LADDER_OUT_NUM)
-__global__ void __launch_bounds__(EVAL_THREADS) go2nn_ladder_reduce_kernel(const float* table, const int32_t* group, int N, double dist2_thr, double* out) {
-  const int g = blockIdx.x, c = blockIdx.y;
-  const double s = eval_group_sum(group, N, g, LadderTerm{table, N, c, dist2_thr});
-  if (threadIdx.x == 0) out[(long long)g * GO2NN_LADDER_OUT_NUM + c] = s;
-}
-#endif
+struct LadderAccumulate {
+  Go2nnLadderIn in; float* table; int N;
+  EVAL_MEMBER void operator()(int e) const { ladder_accumulate_env(in, table, N, e); }
+};
 
 static const char* ladder_in_bad(const Go2nnLadderIn* in) {
-  if (!in->root_states.p || !in->reset_buf.p || !in->time_out_buf.p) return "a null buffer pointer";
-  if (in->root_states.env_stride < 1 || in->root_states.comp_stride < 1) return "root_states with an env stride or a component stride < 1";
-  if (in->reset_buf.env_stride < 1 || in->time_out_buf.env_stride < 1 || in->reset_buf.comp_stride < 0 || in->time_out_buf.comp_stride < 0) return "a flag field with an env stride < 1";
+  const int root = eval_field_fault(in->root_states, 1), reset = eval_field_fault(in->reset_buf, 0), tout = eval_field_fault(in->time_out_buf, 0);
+  if (root == EVAL_FIELD_NULL || reset == EVAL_FIELD_NULL || tout == EVAL_FIELD_NULL) return "a null buffer pointer";
+  if (root) return "root_states with an env stride or a component stride < 1";
+  if (reset || tout) return "a flag field with an env stride < 1";
   if (!(in->dist2_thr > 0.f)) return "dist2_thr <= 0";
   return nullptr;
 }
@@ -85,43 +74,20 @@ extern "C" {
 
 int go2nn_ladder_begin(float* table, int32_t N, int32_t start, void* stream) {
   if (!table || N < 1) FAIL(GO2NN_EINVAL, "ladder begin: bad argument (a table and N >= 1)");
-  const long long n = (long long)GO2NN_LADDER_NUM * N;
-#ifdef GO2_EMU
-  (void)stream;
-  for (long long k = 0; k < n; ++k) table[k] = 0.f;
-  for (int e = 0; e < N; ++e) table[(long long)GO2NN_LADDER_STEP * N + e] = (float)start;
-#else
-  hipLaunchKernelGGL(go2nn_ladder_begin_kernel, dim3((unsigned)((n + EVAL_THREADS - 1) / EVAL_THREADS)), dim3(EVAL_THREADS), 0, (hipStream_t)stream, table, N, (float)start);
-  HIPCHK(hipGetLastError());
-#endif
-  return 0;
+  static_assert(GO2NN_LADDER_STEP == 0, "the STEP row is the table's first N floats");
+  return eval_table_begin(table, GO2NN_LADDER_NUM, N, (float)start, stream);
 }
 
 int go2nn_ladder_accumulate(const Go2nnLadderIn* in, float* table, int32_t N, void* stream) {
   if (!in || !table || N < 1) FAIL(GO2NN_EINVAL, "ladder accumulate: null argument or N < 1");
   if (const char* bad = ladder_in_bad(in)) FAIL(GO2NN_EINVAL, "ladder accumulate: %s", bad);
-#ifdef GO2_EMU
-  (void)stream;
-  for (int e = 0; e < N; ++e) ladder_accumulate_env(*in, table, N, e);
-#else
-  hipLaunchKernelGGL(go2nn_ladder_accumulate_kernel, dim3((unsigned)((N + EVAL_THREADS - 1) / EVAL_THREADS)), dim3(EVAL_THREADS), 0, (hipStream_t)stream, *in, table, N);
-  HIPCHK(hipGetLastError());
-#endif
-  return 0;
+  return eval_per_env(LadderAccumulate{*in, table, N}, N, stream);
 }
 
 int go2nn_ladder_reduce(const float* table, const int32_t* group, int32_t N, int32_t G, float dist2_thr, double* out, void* stream) {
   if (!table || !group || !out || N < 1 || G < 1 || G > 65535) FAIL(GO2NN_EINVAL, "ladder reduce: bad argument (1 <= G <= 65535)");
   if (!(dist2_thr > 0.f)) FAIL(GO2NN_EINVAL, "ladder reduce: dist2_thr <= 0");
-#ifdef GO2_EMU
-  (void)stream;
-  for (int g = 0; g < G; ++g)
-    for (int c = 0; c < GO2NN_LADDER_OUT_NUM; ++c) out[(long long)g * GO2NN_LADDER_OUT_NUM + c] = eval_group_sum(group, N, g, LadderTerm{table, N, c, (double)dist2_thr});
-#else
-  hipLaunchKernelGGL(go2nn_ladder_reduce_kernel, dim3((unsigned)G, GO2NN_LADDER_OUT_NUM), dim3(EVAL_THREADS), 0, (hipStream_t)stream, table, group, N, (double)dist2_thr, out);
-  HIPCHK(hipGetLastError());
-#endif
-  return 0;
+  return eval_reduce(LadderTerm{table, N, 0, (double)dist2_thr}, group, N, G, GO2NN_LADDER_OUT_NUM, out, stream);
 }
 
 }  // extern "C"

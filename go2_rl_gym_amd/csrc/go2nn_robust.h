@@ -1,7 +1,8 @@
 // go2nn_robust.h — the evaluator's perturbation kernels (include/go2nn.h: go2nn_robust_*, added within ABI 7; go2_rl_gym_amd/utils/evaluator.py).
-// Included at the end of go2nn_impl.cpp after go2nn_trace.h (FAIL, HIPCHK are the former's helpers; EVAL_FN, eval_f, eval_b, eval_group_sum go2nn_eval.h's).
+// Included at the end of go2nn_impl.cpp after go2nn_trace.h (FAIL is the former's helper; EVAL_FN, EVAL_MEMBER, eval_f, eval_b, eval_field_fault and the launch scaffold —
+// eval_table_begin, eval_per_env, eval_reduce over eval_group_sum — go2nn_eval.h's).
 //
-// Two launches per env step, one lane per env, no LDS, no atomics, no cross-lane traffic.  go2nn_robust_apply (before the step) writes the env's masked dynamics rows —
+// Two launches per env step (eval_per_env_kernel<RobustApply>, <RobustAccumulate>), one lane per env, no LDS, no atomics, no cross-lane traffic.  go2nn_robust_apply (before the step) writes the env's masked dynamics rows —
 // up to 38 floats — and, on a scheduled step, adds the rotated impulse to three root-state floats; go2nn_robust_accumulate (after it) reads 7 floats and two flags and
 // read-modify-writes the env's column of the table [GO2NN_ROBUST_NUM, N].  With the HIP simulator's field-major buffers (env stride 1) consecutive lanes touch consecutive
 // addresses of every component and of every table row: each load / store instruction of a wave is one dense 256-byte line.  The spec is read through pert_of_env — at most 64
@@ -96,41 +97,23 @@ struct RobustTerm {
   EVAL_MEMBER double operator()(int e) const { return c < GO2NN_ROBUST_ACC_NUM ? (double)table[(long long)(GO2NN_ROBUST_ACC_FIRST + c) * N + e] : 1.0; }
 };
 
-#ifndef GO2_EMU
-__global__ void __launch_bounds__(EVAL_THREADS) go2nn_robust_begin_kernel(float* table, int N, float start) {
-  const long long k = (long long)blockIdx.x * EVAL_THREADS + threadIdx.x;
-  static_assert(GO2NN_ROBUST_STEP == 0, "the STEP row is the table's first N floats");
-  if (k < (long long)GO2NN_ROBUST_NUM * N) table[k] = k < N ? start : 0.f;
-}
-__global__ void __launch_bounds__(EVAL_THREADS) go2nn_robust_apply_kernel(const Go2nnRobustIn in, const Go2nnRobustSpec* specs, const int32_t* pert_of_env, float* table, int N) {
-  const int e = blockIdx.x * EVAL_THREADS + threadIdx.x;
-  if (e < N) robust_apply_env(in, specs, pert_of_env, table, N, e);
-}
-__global__ void __launch_bounds__(EVAL_THREADS) go2nn_robust_accumulate_kernel(const Go2nnRobustIn in, const Go2nnRobustSpec* specs, const int32_t* pert_of_env, float* table,
-                                                                                int N) {
-  const int e = blockIdx.x * EVAL_THREADS + threadIdx.x;
-  if (e < N) robust_accumulate_env(in, specs, pert_of_env, table, N, e);
-}
-// grid = (G, GO2NN_ROBUST_ACC_NUM + 1)
-__global__ void __launch_bounds__(EVAL_THREADS) go2nn_robust_reduce_kernel(const float* table, const int32_t* group, int N, double* out) {
-  const int g = blockIdx.x, c = blockIdx.y;
-  const double s = eval_group_sum(group, N, g, RobustTerm{table, N, c});
-  if (threadIdx.x == 0) out[(long long)g * (GO2NN_ROBUST_ACC_NUM + 1) + c] = s;
-}
-#endif
+struct RobustApply {
+  Go2nnRobustIn in; const Go2nnRobustSpec* specs; const int32_t* pert_of_env; float* table; int N;
+  EVAL_MEMBER void operator()(int e) const { robust_apply_env(in, specs, pert_of_env, table, N, e); }
+};
+struct RobustAccumulate {
+  Go2nnRobustIn in; const Go2nnRobustSpec* specs; const int32_t* pert_of_env; float* table; int N;
+  EVAL_MEMBER void operator()(int e) const { robust_accumulate_env(in, specs, pert_of_env, table, N, e); }
+};
 
 static const char* robust_in_bad(const Go2nnRobustIn* in) {
   const Go2nnEvalField* vec[] = {&in->root_states, &in->commands, &in->base_lin_vel, &in->projected_gravity, &in->motor_strengths, &in->p_gains_multiplier,
                                  &in->d_gains_multiplier};
   const Go2nnEvalField* scalar[] = {&in->reset_buf, &in->time_out_buf, &in->added_base_mass, &in->friction_coeffs};
-  for (const Go2nnEvalField* x : vec) {
-    if (!x->p) return "a null buffer pointer";
-    if (x->env_stride < 1 || x->comp_stride < 1) return "a vector field with an env stride or a component stride < 1";
-  }
-  for (const Go2nnEvalField* x : scalar) {
-    if (!x->p) return "a null buffer pointer";
-    if (x->env_stride < 1 || x->comp_stride < 0) return "a per-env field with an env stride < 1";
-  }
+  for (const Go2nnEvalField* x : vec)
+    if (const int bad = eval_field_fault(*x, 1)) return bad == EVAL_FIELD_NULL ? "a null buffer pointer" : "a vector field with an env stride or a component stride < 1";
+  for (const Go2nnEvalField* x : scalar)
+    if (const int bad = eval_field_fault(*x, 0)) return bad == EVAL_FIELD_NULL ? "a null buffer pointer" : "a per-env field with an env stride < 1";
   if (in->num_specs < 1 || in->num_specs > GO2NN_ROBUST_MAX_SPECS) return "num_specs outside [1, 64]";
   return nullptr;
 }
@@ -153,57 +136,25 @@ int go2nn_robust_check_specs(const Go2nnRobustSpec* specs, int32_t P) {
 
 int go2nn_robust_begin(float* table, int32_t N, int32_t start, void* stream) {
   if (!table || N < 1) FAIL(GO2NN_EINVAL, "robust begin: bad argument (a table and N >= 1)");
-  const long long n = (long long)GO2NN_ROBUST_NUM * N;
-#ifdef GO2_EMU
-  (void)stream;
-  for (long long k = 0; k < n; ++k) table[k] = 0.f;
-  for (int e = 0; e < N; ++e) table[(long long)GO2NN_ROBUST_STEP * N + e] = (float)start;
-#else
-  hipLaunchKernelGGL(go2nn_robust_begin_kernel, dim3((unsigned)((n + EVAL_THREADS - 1) / EVAL_THREADS)), dim3(EVAL_THREADS), 0, (hipStream_t)stream, table, N, (float)start);
-  HIPCHK(hipGetLastError());
-#endif
-  return 0;
+  static_assert(GO2NN_ROBUST_STEP == 0, "the STEP row is the table's first N floats");
+  return eval_table_begin(table, GO2NN_ROBUST_NUM, N, (float)start, stream);
 }
 
 int go2nn_robust_apply(const Go2nnRobustIn* in, const Go2nnRobustSpec* specs, const int32_t* pert_of_env, float* table, int32_t N, void* stream) {
   if (!in || !specs || !pert_of_env || !table || N < 1) FAIL(GO2NN_EINVAL, "robust apply: null argument or N < 1");
   if (const char* bad = robust_in_bad(in)) FAIL(GO2NN_EINVAL, "robust apply: %s", bad);
-#ifdef GO2_EMU
-  (void)stream;
-  for (int e = 0; e < N; ++e) robust_apply_env(*in, specs, pert_of_env, table, N, e);
-#else
-  hipLaunchKernelGGL(go2nn_robust_apply_kernel, dim3((unsigned)((N + EVAL_THREADS - 1) / EVAL_THREADS)), dim3(EVAL_THREADS), 0, (hipStream_t)stream, *in, specs, pert_of_env,
-                     table, N);
-  HIPCHK(hipGetLastError());
-#endif
-  return 0;
+  return eval_per_env(RobustApply{*in, specs, pert_of_env, table, N}, N, stream);
 }
 
 int go2nn_robust_accumulate(const Go2nnRobustIn* in, const Go2nnRobustSpec* specs, const int32_t* pert_of_env, float* table, int32_t N, void* stream) {
   if (!in || !specs || !pert_of_env || !table || N < 1) FAIL(GO2NN_EINVAL, "robust accumulate: null argument or N < 1");
   if (const char* bad = robust_in_bad(in)) FAIL(GO2NN_EINVAL, "robust accumulate: %s", bad);
-#ifdef GO2_EMU
-  (void)stream;
-  for (int e = 0; e < N; ++e) robust_accumulate_env(*in, specs, pert_of_env, table, N, e);
-#else
-  hipLaunchKernelGGL(go2nn_robust_accumulate_kernel, dim3((unsigned)((N + EVAL_THREADS - 1) / EVAL_THREADS)), dim3(EVAL_THREADS), 0, (hipStream_t)stream, *in, specs,
-                     pert_of_env, table, N);
-  HIPCHK(hipGetLastError());
-#endif
-  return 0;
+  return eval_per_env(RobustAccumulate{*in, specs, pert_of_env, table, N}, N, stream);
 }
 
 int go2nn_robust_reduce(const float* table, const int32_t* group, int32_t N, int32_t G, double* out, void* stream) {
   if (!table || !group || !out || N < 1 || G < 1 || G > 65535) FAIL(GO2NN_EINVAL, "robust reduce: bad argument (1 <= G <= 65535)");
-#ifdef GO2_EMU
-  (void)stream;
-  for (int g = 0; g < G; ++g)
-    for (int c = 0; c < GO2NN_ROBUST_ACC_NUM + 1; ++c) out[(long long)g * (GO2NN_ROBUST_ACC_NUM + 1) + c] = eval_group_sum(group, N, g, RobustTerm{table, N, c});
-#else
-  hipLaunchKernelGGL(go2nn_robust_reduce_kernel, dim3((unsigned)G, GO2NN_ROBUST_ACC_NUM + 1), dim3(EVAL_THREADS), 0, (hipStream_t)stream, table, group, N, out);
-  HIPCHK(hipGetLastError());
-#endif
-  return 0;
+  return eval_reduce(RobustTerm{table, N, 0}, group, N, G, GO2NN_ROBUST_ACC_NUM + 1, out, stream);
 }
 
 }  // extern "C"

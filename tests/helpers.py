@@ -498,3 +498,28 @@ def load_nn_emu():
     lib = _nn.bind(out)
     assert lib.go2nn_is_device_library() == 0
     return lib
+
+
+# ---- the evaluator's per-group reduces (go2nn_*_reduce): what the reduce_case and test_reduce_* of the six host test modules share ----------------------------------
+def lognormal_table(rng, rows, N):
+    """[rows, N] fp32 of both signs, magnitudes over many decades: sums that show a changed order or an fp32 partial"""
+    return (rng.normal(0, 1, (rows, N)) * np.exp(rng.normal(0, 3, (rows, N)))).astype(np.float32)
+
+
+def reduce_groups(rng, N, G, outside=2):
+    """[N] int32 group ids in [-outside, G + outside): ids outside [0, G) are ignored, the groups are of unequal size, and group 1 stays empty"""
+    group = rng.integers(-outside, G + outside, N).astype(np.int32)
+    group[group == 1] = 0
+    return group
+
+
+def reduce_twice(reduce, table, group, G, cols):
+    """reduce(table, group, N, G, out) -> status is a host library's go2nn_*_reduce over pointers: two runs into -1-filled [G, cols] outputs give the same bytes,
+    and G = 0 is refused -> the output"""
+    p = lambda a: C.c_void_p(a.ctypes.data)
+    outs = [np.full((G, cols), -1.0) for _ in range(2)]
+    for out in outs:
+        assert reduce(p(table), p(group), table.shape[1], G, p(out)) == 0
+    assert outs[0].tobytes() == outs[1].tobytes()
+    assert reduce(p(table), p(group), table.shape[1], 0, p(outs[1])) != 0
+    return outs[0]

@@ -10,7 +10,7 @@ import pytest
 import torch
 import yaml
 
-from helpers import ROOT, load_nn_emu, load_oracle
+from helpers import ROOT, load_nn_emu, load_oracle, lognormal_table, reduce_groups, reduce_twice
 from go2_rl_gym_amd import _nn
 from go2_rl_gym_amd._nn import EVAL_FIELDS, EVAL_METRICS, GO2NN_EVAL_NUM, Go2nnEvalIn
 from go2_rl_gym_amd.envs import task_registry
@@ -143,11 +143,9 @@ def reduce_reference(acc, group, G):
 
 def reduce_case(N, G, seed=3):
     rng = np.random.default_rng(seed + N)
-    acc = (rng.normal(0, 1, (GO2NN_EVAL_NUM, N)) * np.exp(rng.normal(0, 3, (GO2NN_EVAL_NUM, N)))).astype(np.float32)
+    acc = lognormal_table(rng, GO2NN_EVAL_NUM, N)
     acc[9] = (rng.random(N) < 0.3) * rng.integers(1, 4, N)
-    group = rng.integers(-2, G + 2, N).astype(np.int32)          # ids outside [0, G) are ignored
-    group[group == 1] = 0                                        # group 1 stays empty
-    return acc, group
+    return acc, reduce_groups(rng, N, G)
 
 
 def check_reduce(out, acc, group, G, N, what):
@@ -163,14 +161,8 @@ def check_reduce(out, acc, group, G, N, what):
 @pytest.mark.parametrize("N,G", [(1, 3), (17, 3), (257, 5), (4096, 7)])
 def test_reduce_against_fsum(emu, N, G):
     acc, group = reduce_case(N, G)
-    outs = []
-    for _ in range(2):
-        out = np.full((G, GO2NN_EVAL_NUM + 2), -1.0)
-        assert emu.go2nn_eval_reduce(C.c_void_p(acc.ctypes.data), C.c_void_p(group.ctypes.data), N, G, C.c_void_p(out.ctypes.data), None) == 0
-        outs.append(out)
-    assert outs[0].tobytes() == outs[1].tobytes()
-    check_reduce(outs[0], acc, group, G, N, "host N=%d" % N)
-    assert emu.go2nn_eval_reduce(C.c_void_p(acc.ctypes.data), C.c_void_p(group.ctypes.data), N, 0, C.c_void_p(outs[0].ctypes.data), None) != 0
+    out = reduce_twice(lambda *a: emu.go2nn_eval_reduce(*a, None), acc, group, G, GO2NN_EVAL_NUM + 2)
+    check_reduce(out, acc, group, G, N, "host N=%d" % N)
 
 
 def test_eval_symbols_and_struct_within_abi_7(emu, tmp_path):

@@ -12,7 +12,7 @@ import types
 import numpy as np
 import pytest
 
-from helpers import ROOT, load_nn_emu
+from helpers import ROOT, load_nn_emu, reduce_groups, reduce_twice
 import test_eval_host as th
 from test_robust_host import HostMemory
 from go2_rl_gym_amd import _nn
@@ -310,9 +310,7 @@ def reduce_case(N, G, seed=5):
     for f in range(4):
         for k in FLOAT_COLS:
             table[gait_row(f, k)] = rng.normal(0, 30, N)          # (both signs, as clearance_sum can have)
-    group = rng.integers(-2, G + 2, N).astype(np.int32)          # ids outside [0, G) are ignored; groups of unequal size
-    group[group == 1] = 0                                        # group 1 stays empty
-    return table, group
+    return table, reduce_groups(rng, N, G)
 
 
 def reduce_rows():
@@ -350,13 +348,12 @@ def emu_reduce(emu, table, group, G):
 def test_reduce_against_fsum(emu, N, G):
     from go2_rl_gym_amd.utils.evaluator import GAIT_KEYS, PolicyEvaluator
     table, group = reduce_case(N, G)
-    outs = [emu_reduce(emu, table, group, G) for _ in range(2)]
-    assert outs[0].tobytes() == outs[1].tobytes()
+    out = reduce_twice(lambda *a: emu.go2nn_gait_reduce(*a, None), table, group, G, GO2NN_GAIT_OUT_NUM)
     if N >= 17:
-        check_reduce(outs[0], table, group, G, N, "host N=%d" % N)
+        check_reduce(out, table, group, G, N, "host N=%d" % N)
     # the empty group: zeros, and figures that do not exist rather than an exception
-    row = PolicyEvaluator._gait_row(types.SimpleNamespace(dt=DT, foot_names=["FL", "FR", "RL", "RR"]), outs[0][1])
-    assert not outs[0][1].any() and row["n_envs"] == 0 and all(math.isnan(v) for k, v in row.items() if k != "n_envs") and set(GAIT_KEYS) < set(row)
+    row = PolicyEvaluator._gait_row(types.SimpleNamespace(dt=DT, foot_names=["FL", "FR", "RL", "RR"]), out[1])
+    assert not out[1].any() and row["n_envs"] == 0 and all(math.isnan(v) for k, v in row.items() if k != "n_envs") and set(GAIT_KEYS) < set(row)
     assert "slip_speed/RL" in row and len(row) == 8 * 5 + 3 + 1
 
 

@@ -15,7 +15,7 @@ import pytest
 import torch
 import yaml
 
-from helpers import ROOT, load_nn_emu, load_oracle
+from helpers import ROOT, load_nn_emu, load_oracle, reduce_groups, reduce_twice
 import test_eval_host as th
 from test_robust_host import HostMemory, store
 from go2_rl_gym_amd import _nn
@@ -185,9 +185,7 @@ def reduce_case(N, G, seed=11):
     table[R["max_d2"]] = (DIST2_THR * np.exp(rng.normal(-1, 2, N))).astype(np.float32)          # on both sides of the threshold: the cap at 1 occurs
     table[R["clear_step"]] = rng.integers(1, 500, N)          # (also in rows that never cleared: the reduce must not add them)
     table[R["x0"]], table[R["y0"]], table[R["step"]] = rng.normal(0, 50, N), rng.normal(0, 50, N), 500
-    group = rng.integers(-2, G + 2, N).astype(np.int32)          # ids outside [0, G) are ignored
-    group[group == 1] = 0                                        # group 1 stays empty
-    return table, group
+    return table, reduce_groups(rng, N, G)
 
 
 def check_reduce(out, table, group, G, N, what):
@@ -210,13 +208,8 @@ def check_reduce(out, table, group, G, N, what):
 @pytest.mark.parametrize("N,G", [(1, 3), (17, 3), (300, 5), (4096, 7)])
 def test_reduce_against_fsum(emu, N, G):
     table, group = reduce_case(N, G)
-    outs = []
-    for _ in range(2):
-        out = np.full((G, GO2NN_LADDER_OUT_NUM), -1.0)
-        assert emu.go2nn_ladder_reduce(C.c_void_p(table.ctypes.data), C.c_void_p(group.ctypes.data), N, G, DIST2_THR, C.c_void_p(out.ctypes.data), None) == 0
-        outs.append(out)
-    assert outs[0].tobytes() == outs[1].tobytes()
-    check_reduce(outs[0], table, group, G, N, "host N=%d" % N)
+    out = reduce_twice(lambda t, g, n, groups, o: emu.go2nn_ladder_reduce(t, g, n, groups, DIST2_THR, o, None), table, group, G, GO2NN_LADDER_OUT_NUM)
+    check_reduce(out, table, group, G, N, "host N=%d" % N)
 
 
 def test_argument_checks(emu):

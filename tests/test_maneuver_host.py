@@ -22,7 +22,7 @@ import pytest
 import torch
 import yaml
 
-from helpers import ROOT, load_nn_emu, load_oracle
+from helpers import ROOT, load_nn_emu, load_oracle, lognormal_table, reduce_groups, reduce_twice
 import test_eval_host as th
 from test_robust_host import HostMemory, logical, store
 from go2_rl_gym_amd import _nn
@@ -276,10 +276,7 @@ def test_apply_and_accumulate_against_float64(emu, N, layout):
 
 def reduce_case(N, G, seed=9):
     rng = np.random.default_rng(seed + N)
-    table = (rng.normal(0, 1, (GO2NN_MANEUVER_NUM, N)) * np.exp(rng.normal(0, 3, (GO2NN_MANEUVER_NUM, N)))).astype(np.float32)
-    group = rng.integers(-2, G + 2, N).astype(np.int32)          # ids outside [0, G) are ignored
-    group[group == 1] = 0                                        # group 1 stays empty
-    return table, group
+    return lognormal_table(rng, GO2NN_MANEUVER_NUM, N), reduce_groups(rng, N, G)
 
 
 def reduce_reference(table, group, G):
@@ -307,13 +304,8 @@ def check_reduce(out, table, group, G, N, what):
 @pytest.mark.parametrize("N,G", [(1, 3), (17, 3), (300, 5), (4096, 7)])
 def test_reduce_against_fsum(emu, N, G):
     table, group = reduce_case(N, G)
-    outs = []
-    for _ in range(2):
-        out = np.full((G, GO2NN_MANEUVER_ACC_NUM + 1), -1.0)
-        assert emu.go2nn_maneuver_reduce(C.c_void_p(table.ctypes.data), C.c_void_p(group.ctypes.data), N, G, C.c_void_p(out.ctypes.data), None) == 0
-        outs.append(out)
-    assert outs[0].tobytes() == outs[1].tobytes()
-    check_reduce(outs[0], table, group, G, N, "host N=%d" % N)
+    out = reduce_twice(lambda *a: emu.go2nn_maneuver_reduce(*a, None), table, group, G, GO2NN_MANEUVER_ACC_NUM + 1)
+    check_reduce(out, table, group, G, N, "host N=%d" % N)
 
 
 def test_check_specs(emu):

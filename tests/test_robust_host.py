@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import ROOT, load_nn_emu, load_oracle
+from helpers import ROOT, load_nn_emu, load_oracle, lognormal_table, reduce_groups, reduce_twice
 import test_eval_host as th
 from go2_rl_gym_amd import _nn
 from go2_rl_gym_amd._nn import GO2NN_ROBUST_ACC_FIRST, GO2NN_ROBUST_ACC_NUM, GO2NN_ROBUST_NUM, ROBUST_FIELDS, ROBUST_MASK, ROBUST_ROWS, Go2nnRobustIn, Go2nnRobustSpec
@@ -269,10 +269,7 @@ def test_apply_and_accumulate_against_float64(emu, N, layout):
 
 def reduce_case(N, G, seed=5):
     rng = np.random.default_rng(seed + N)
-    table = (rng.normal(0, 1, (GO2NN_ROBUST_NUM, N)) * np.exp(rng.normal(0, 3, (GO2NN_ROBUST_NUM, N)))).astype(np.float32)
-    group = rng.integers(-2, G + 2, N).astype(np.int32)          # ids outside [0, G) are ignored
-    group[group == 1] = 0                                        # group 1 stays empty
-    return table, group
+    return lognormal_table(rng, GO2NN_ROBUST_NUM, N), reduce_groups(rng, N, G)
 
 
 def check_reduce(out, table, group, G, N, what):
@@ -292,14 +289,8 @@ def check_reduce(out, table, group, G, N, what):
 @pytest.mark.parametrize("N,G", [(17, 3), (300, 5), (4096, 7)])
 def test_reduce_against_fsum(emu, N, G):
     table, group = reduce_case(N, G)
-    outs = []
-    for _ in range(2):
-        out = np.full((G, GO2NN_ROBUST_ACC_NUM + 1), -1.0)
-        assert emu.go2nn_robust_reduce(C.c_void_p(table.ctypes.data), C.c_void_p(group.ctypes.data), N, G, C.c_void_p(out.ctypes.data), None) == 0
-        outs.append(out)
-    assert outs[0].tobytes() == outs[1].tobytes()
-    check_reduce(outs[0], table, group, G, N, "host N=%d" % N)
-    assert emu.go2nn_robust_reduce(C.c_void_p(table.ctypes.data), C.c_void_p(group.ctypes.data), N, 0, C.c_void_p(outs[0].ctypes.data), None) != 0
+    out = reduce_twice(lambda *a: emu.go2nn_robust_reduce(*a, None), table, group, G, GO2NN_ROBUST_ACC_NUM + 1)
+    check_reduce(out, table, group, G, N, "host N=%d" % N)
 
 
 def test_argument_checks(emu):

@@ -6,7 +6,7 @@ Measures, on cuda:0, with the task's default `evaluation` section (1024 robots, 
   * wall time of evaluate() run eagerly and with the captured chunk of steps replayed (simulator re-creation, capture and the final host copy included: it is what
     the training loop waits for), best and median of --reps;
   * go2nn_eval_accumulate per launch, from device events around 200 back-to-back launches on the evaluator's own buffers (for the kernel's own duration run this tool
-    under `rocprofv3 --kernel-trace --stats -- python tools/eval_bench.py --kernel_only` and read go2nn_eval_accumulate_kernel);
+    under `rocprofv3 --kernel-trace --stats -- python tools/eval_bench.py --kernel_only` and read eval_per_env_kernel<EvalAccumulate>);
   * the same ten per-step terms written as torch expressions on the same (strided) buffers, per step, eager and replayed from a HIP graph.
 --robust: the same with the default perturbations on (evaluation.perturbations = DEFAULT_PERTURBATIONS), plus go2nn_robust_apply + go2nn_robust_accumulate per pair of
 back-to-back launches; the torch-expression comparison is left out.
