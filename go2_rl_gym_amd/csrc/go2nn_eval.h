@@ -11,9 +11,13 @@
 //   eval_per_env(f, N)                       grid = ceil(N / 256), lane e calls f(e): eval_per_env_kernel<EvalAccumulate>, <LadderAccumulate>, ... in a kernel trace
 //   eval_table_begin(table, rows, N, start)  grid = ceil(rows N / 256), one float per lane: row 0 (a family's STEP row) = start, every other row = 0
 //   eval_reduce(term, group, N, G, cols)     grid = (G, cols), workgroup (g, c) writes out[g cols + c] = eval_group_sum of the Term at column c (eval_group_max for MAX_COL)
+//   eval_bootstrap<COLS>(term, cell_start, cell_envs, G, B, seed)   grid = (G, ceil(B / 256)), lane b writes replicate b of cell g: the Term's COLS columns summed over the
+//                                            cell's members redrawn with replacement (go2nn_bootstrap.h instantiates it for EvalTerm; any family's Term fits)
 // eval_field_fault is the one statement of what a Go2nnEvalField must satisfy; each family words its own messages around it.
 #ifndef GO2NN_EVAL_H
 #define GO2NN_EVAL_H
+
+#include "go2_math.h"          // philox4x32_10: eval_bootstrap's draws
 
 #ifdef GO2_EMU
 #define EVAL_FN static inline
@@ -202,6 +206,56 @@ template <int MAX_COL = -1, class Term> static int eval_reduce(Term term, const 
     for (term.c = 0; term.c < cols; ++term.c) out[(long long)g * cols + term.c] = eval_group_value<MAX_COL>(group, N, g, term);
 #else
   hipLaunchKernelGGL(HIP_KERNEL_NAME(eval_reduce_kernel<MAX_COL, Term>), dim3((unsigned)G, (unsigned)cols), dim3(EVAL_THREADS), 0, (hipStream_t)stream, term, group, N, cols, out);
+  HIPCHK(hipGetLastError());
+#endif
+  return 0;
+}
+
+// out[(b G + g) COLS + c] for every replicate b < B, cell g < G and column c < COLS: the sum of the Term at column c over n = cell_start[g + 1] - cell_start[g] members of the
+// cell drawn WITH replacement (a stratified bootstrap: every cell keeps its size), in fp64 in the order of the draws.  Draw k of (b, g) is member (x n) >> 32 of the cell's list
+// cell_envs[cell_start[g] ...], x = word (k & 3) of philox4x32_10(b, g, k >> 2, 0, seed, EVAL_TAG_BOOTSTRAP): integers only, so the host loops, the lanes and a restatement in
+// Python integers pick the same members, and a replicate depends on (b, g, seed) but not on B.  grid = (G, ceil(B / 256)), lane b walks its cell's draws — one Philox block per
+// four, the words picked by the unrolled loop's constant index, never by a dynamic one (that array would live in scratch) — and keeps the COLS sums in registers, which is why
+// COLS is a template argument and not one of the call; no LDS, no atomics.  n is uniform over a workgroup; the member loads are gathers from a table that fits the caches.
+#define EVAL_TAG_BOOTSTRAP 7u          // the key's second word; 1 .. 6 are the sensor kernels' (go2nn_sensor.h, go2nn_sensor_rand.h)
+template <int COLS, class Term> EVAL_FN void eval_bootstrap_replicate(Term term, const int32_t* cell_start, const int32_t* cell_envs, int G, int g, int b, uint32_t seed, double* out) {
+  const int s0 = cell_start[g], n = cell_start[g + 1] - s0;
+  double sum[COLS];
+#pragma unroll
+  for (int c = 0; c < COLS; ++c) sum[c] = 0.0;
+  for (int k0 = 0; k0 < n; k0 += 4) {
+    uint32_t w[4];
+    philox4x32_10((uint32_t)b, (uint32_t)g, (uint32_t)(k0 >> 2), 0u, seed, EVAL_TAG_BOOTSTRAP, w);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      if (k0 + q < n) {
+        const int e = cell_envs[s0 + (int)(((uint64_t)w[q] * (uint64_t)(uint32_t)n) >> 32)];
+#pragma unroll
+        for (int c = 0; c < COLS; ++c) {
+          term.c = c;
+          sum[c] += term(e);
+        }
+      }
+    }
+  }
+  double* row = out + ((long long)b * G + g) * COLS;
+#pragma unroll
+  for (int c = 0; c < COLS; ++c) row[c] = sum[c];
+}
+#ifndef GO2_EMU
+template <int COLS, class Term> __global__ void __launch_bounds__(EVAL_THREADS) eval_bootstrap_kernel(const Term term, const int32_t* cell_start, const int32_t* cell_envs, int G, int B, uint32_t seed, double* out) {
+  const int b = blockIdx.y * EVAL_THREADS + threadIdx.x;
+  if (b < B) eval_bootstrap_replicate<COLS>(term, cell_start, cell_envs, G, (int)blockIdx.x, b, seed, out);
+}
+#endif
+template <int COLS, class Term> static int eval_bootstrap(const Term& term, const int32_t* cell_start, const int32_t* cell_envs, int G, int B, uint32_t seed, double* out, void* stream) {
+#ifdef GO2_EMU
+  (void)stream;
+  for (int b = 0; b < B; ++b)
+    for (int g = 0; g < G; ++g) eval_bootstrap_replicate<COLS>(term, cell_start, cell_envs, G, g, b, seed, out);
+#else
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(eval_bootstrap_kernel<COLS, Term>), dim3((unsigned)G, (unsigned)((B + EVAL_THREADS - 1) / EVAL_THREADS)), dim3(EVAL_THREADS), 0, (hipStream_t)stream,
+                     term, cell_start, cell_envs, G, B, seed, out);
   HIPCHK(hipGetLastError());
 #endif
   return 0;

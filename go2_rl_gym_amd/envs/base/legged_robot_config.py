@@ -307,6 +307,10 @@ class LeggedRobotCfgPPO(BaseConfig):
         blackbox_seconds = 2.0  # [s] length of every robot's ring; memory = num_envs x steps x 448 bytes (1024 x 100: 46 MB)
         blackbox_max_bytes = 512 * 1024 * 1024  # a black box larger than this is refused
         asymmetry = False       # True (--asymmetry): also run the policy on the mirror image of every observation and report how far it is from equivariant (equivariance_rmse, per joint kind, relative, max) and, on steps whose command has vy = yaw = 0, how unequally the robot loads its left and right legs (action, torque, power, contact: left share and per-robot imbalance; utils/evaluator.py ASYM_KEYS); an add-on like `gait`, it works next to every mode above; feed-forward and CTS policies
+        bootstrap = 0           # B > 0 (--ci [B]): after the reduce, redraw every cell's robots with replacement B times on the device (go2nn_eval_bootstrap) and give every reported figure of RESULT_KEYS a percentile interval ("ci": {metric: [lo, hi]}, utils/evaluator.py CI_KEYS); the same replicates of two checkpoints are paired (utils/evaluator.py compare); 0: nothing is loaded, allocated or launched
+        bootstrap_seed = 2718   # the Philox seed of the redraws: the same seed, the same robots in replicate b of every evaluation
+        confidence = 0.95       # the intervals' level: the (1 - confidence) / 2 and (1 + confidence) / 2 quantiles of the replicates
+        bootstrap_max_bytes = 256 << 20  # the [B, cells, 12] fp64 table of replicates is refused above this
 
 
 class LeggedRobotCfgCTS(BaseConfig):
@@ -394,6 +398,10 @@ class LeggedRobotCfgCTS(BaseConfig):
         blackbox_seconds = 2.0  # [s] length of every robot's ring; memory = num_envs x steps x 448 bytes (1024 x 100: 46 MB)
         blackbox_max_bytes = 512 * 1024 * 1024  # a black box larger than this is refused
         asymmetry = False       # True (--asymmetry): also run the policy on the mirror image of every observation and report how far it is from equivariant (equivariance_rmse, per joint kind, relative, max) and, on steps whose command has vy = yaw = 0, how unequally the robot loads its left and right legs (action, torque, power, contact: left share and per-robot imbalance; utils/evaluator.py ASYM_KEYS); an add-on like `gait`, it works next to every mode above; feed-forward and CTS policies
+        bootstrap = 0           # B > 0 (--ci [B]): after the reduce, redraw every cell's robots with replacement B times on the device (go2nn_eval_bootstrap) and give every reported figure of RESULT_KEYS a percentile interval ("ci": {metric: [lo, hi]}, utils/evaluator.py CI_KEYS); the same replicates of two checkpoints are paired (utils/evaluator.py compare); 0: nothing is loaded, allocated or launched
+        bootstrap_seed = 2718   # the Philox seed of the redraws: the same seed, the same robots in replicate b of every evaluation
+        confidence = 0.95       # the intervals' level: the (1 - confidence) / 2 and (1 + confidence) / 2 quantiles of the replicates
+        bootstrap_max_bytes = 256 << 20  # the [B, cells, 12] fp64 table of replicates is refused above this
 
 
 class LeggedRobotCfgMoECTS(LeggedRobotCfgCTS):

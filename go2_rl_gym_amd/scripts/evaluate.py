@@ -21,7 +21,12 @@ feet drag least.
 equivariance_rmse compares a --symmetry run with a plain one.  left_share/* says WHICH side carries more and has no better direction: it is refused as a metric.
 --record N also records N robots of every (terrain x scenario) group and writes eval_results/trace_<checkpoint number>.npz into the run's directory.
 --blackbox [N] also keeps the last seconds before every robot's first fall (utils/recorder.py FallRecorder), prints per cell with falls how many robots fell and when,
-and writes those of N fallen robots per cell (default 2) to eval_results/falls_<checkpoint number>.npz; read_falls and fall_summary read it back."""
+and writes those of N fallen robots per cell (default 2) to eval_results/falls_<checkpoint number>.npz; read_falls and fall_summary read it back.
+--ci [B] also gives every figure a bootstrap confidence interval (utils/evaluator.py CI_KEYS; B resamplings of the robots within their cells, default 1000), next to any of
+the modes above; --metric must then be one of CI_KEYS.  After the best checkpoint is named as without it, every checkpoint is compared with the best one ON THE SAME
+RESAMPLINGS — an evaluation is deterministic per robot index, so the difference of the two metrics per resampling is a paired comparison —: the JSON line gains
+"comparison" (per checkpoint its value and interval, the difference to the best and that difference's interval) and "tied_with_best", the checkpoints whose paired interval
+contains 0; the same goes to eval_results/comparison_<metric>.yaml in the run's directory."""
 import json
 import math
 import os
@@ -30,7 +35,7 @@ from pathlib import Path
 
 from go2_rl_gym_amd.envs import *  # noqa: F401,F403
 from go2_rl_gym_amd.utils import get_args
-from go2_rl_gym_amd.utils.evaluator import PolicyEvaluator, format_table, results_dict
+from go2_rl_gym_amd.utils.evaluator import CI_KEYS, PolicyEvaluator, compare, format_table, interval, replicate_metrics, results_dict
 from go2_rl_gym_amd.utils.helpers import _checkpoint_number, get_load_path
 from go2_rl_gym_amd.utils.task_registry import ROOT_DIR, task_registry
 
@@ -78,11 +83,36 @@ def best_checkpoint(rows, metric):
     return (max if higher else min)(rows, key=rank)
 
 
+def comparison(rows, reps, best, metric, confidence):
+    """rows: the checkpoint rows;  reps: {checkpoint: the [B] replicates of its overall `metric`};  best: the best row -> the "comparison" block: every checkpoint against
+    the best one on the same replicates (utils/evaluator.py compare), and the names of those that cannot be told from it"""
+    out, tied = [], []
+    for r in rows:
+        name, value = r["checkpoint"], metric_value(r, metric)
+        c = compare(reps[name], reps[best["checkpoint"]], confidence)
+        out.append({"checkpoint": name, "value": value, "ci": interval(reps[name], confidence), "diff_to_best": value - metric_value(best, metric), "diff_ci": c["diff_ci"],
+                    "tied_with_best": c["tied"]})
+        if c["tied"]:
+            tied.append(name)
+    return {"metric": metric, "confidence": confidence, "replicates": int(len(reps[best["checkpoint"]])), "rows": out}, tied
+
+
+def format_comparison(comp):
+    lines = ["%-20s %12s %26s %14s %26s %6s" % ("checkpoint", comp["metric"][:12], "%g %% interval" % (100.0 * comp["confidence"]), "diff to best", "paired interval", "tied")]
+    for r in comp["rows"]:
+        lines.append("%-20s %12.4f %26s %14.4f %26s %6s" % (r["checkpoint"], r["value"], "[%.4f, %.4f]" % tuple(r["ci"]), r["diff_to_best"], "[%.4f, %.4f]" % tuple(r["diff_ci"]),
+                                                            "yes" if r["tied_with_best"] else "no"))
+    return "\n".join(lines)
+
+
 def evaluate(argv=None, log_root="default", env_kwargs=None, evaluator_kwargs=None):
     """env_kwargs / evaluator_kwargs: extra arguments of the env / of PolicyEvaluator (tests hand in host libraries, as through runner.evaluator_kwargs)"""
     own, rest = _own_flags(list(sys.argv[1:] if argv is None else argv))
     check_metric(own["metric"])
     args = get_args(rest)
+    if args.ci is not None and own["metric"] not in CI_KEYS:          # refused before anything runs: the comparison needs the metric's replicates
+        raise ValueError("--ci --metric %s: the bootstrap resamples the figures %s; the modes' own figures, the gait and the asymmetry sections have no replicates"
+                         % (own["metric"], ", ".join(CI_KEYS)))
     env_cfg, train_cfg = task_registry.get_cfgs(name=args.task)
     env_cfg.env.num_envs = min(env_cfg.env.num_envs, 64)          # the runner's own env only carries the model's shapes here; the evaluator brings its own simulator
     env_cfg.env.test = True
@@ -99,12 +129,14 @@ def evaluate(argv=None, log_root="default", env_kwargs=None, evaluator_kwargs=No
     if env.lib.go2sim_is_device_library() != 1:
         kw.setdefault("lib", env.lib)
     ev = PolicyEvaluator(env.cfg, ev_cfg, task_class=type(env), sim_params=env.sim_params, device=env.sim_device, **kw)
-    rows = []
+    rows, reps = [], {}
     for p in paths:
         runner.load(str(p), load_optimizer=False)
         res = ev.evaluate(runner.alg.actor_critic)
         print("== %s (%s)\n%s" % (p.name, res["mode"], format_table(res)))
         rows.append({"checkpoint": p.name, "overall": res["overall"], "groups": res["groups"]})
+        if res.get("bootstrap") is not None and own["metric"] in CI_KEYS:          # the [B] replicates of the overall metric: what the paired comparison below reads
+            reps[p.name] = replicate_metrics(res["bootstrap"]["overall"])[own["metric"]]
         if res.get("perturbations") is not None:
             rows[-1]["perturbations"] = res["perturbations"]
         if res.get("maneuvers") is not None:
@@ -134,6 +166,15 @@ def evaluate(argv=None, log_root="default", env_kwargs=None, evaluator_kwargs=No
     key = lambda r: metric_value(r, metric)
     best = best_checkpoint(rows, metric)
     out = {"task": args.task, "metric": metric, "best": best["checkpoint"], "best_value": key(best), "checkpoints": rows}
+    if reps:          # every checkpoint against the best one, on the same replicates
+        import yaml
+        out["comparison"], out["tied_with_best"] = comparison(rows, reps, best, metric, ev.confidence)
+        print(format_comparison(out["comparison"]))
+        path = os.path.join(str(paths[0].parent), "eval_results", "comparison_%s.yaml" % metric)
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+        with open(path, "w") as f:
+            yaml.safe_dump({"best": best["checkpoint"], "comparison": out["comparison"], "tied_with_best": out["tied_with_best"]}, f)
+        print("comparison: %s" % path)
     print(json.dumps(out))
     ev.close()
     env.close()

@@ -87,6 +87,16 @@ the robots of each robot's own |L - R| / (L + R).  ASYM_KEYS are pooled ratios o
 res["asymmetry"] only — res["overall"] and every other result are those of the flag-off run.  The mirrored forward shares the weights and nothing else with act(); a
 recurrent policy is refused (its mirrored stream needs a twin hidden state).  With `asymmetry = False` nothing of this is loaded, allocated or launched.
 
+How sure a figure is: with `evaluation.bootstrap = B > 0` (--ci [B]) ONE more launch after go2nn_eval_reduce, on the same accumulators and the same cells, redraws every
+cell's robots with replacement B times (go2nn_eval_bootstrap: csrc/go2nn_bootstrap.h, the rule in include/go2nn.h; Philox seed `bootstrap_seed`) and one more device ->
+host copy brings the [B, cells, 12] fp64 table of resampled reduce rows: res["bootstrap"] = {"replicates", "seed", "confidence", "table", "overall" ([B, 12]: the overall
+row per replicate)}.  A partition's replicate rows are the sums of its cells' (the reshapes and sums of _results), a figure's replicates are _row() of them, and every leaf
+dict _row() makes — "overall", "groups", "cells", "perturbations", "sensors", "maneuvers", the ladder's per-level leaves — gains "ci": {metric: [lo, hi]} for CI_KEYS, the
+(1 - confidence) / 2 and (1 + confidence) / 2 quantiles ([nan, nan] where every replicate is NaN).  The cells are strata: every replicate keeps the design's robots per
+cell.  An evaluation is deterministic per robot index, so the same replicates of two checkpoints' evaluations are PAIRED: compare() below.  The modes' own figures
+(push_falls, settle_time_s, cleared, ...) and the gait and asymmetry sections get NO interval.  An add-on like `gait`: it reads only the accumulators and the cell
+assignment and works next to every mode; the table is refused above `bootstrap_max_bytes`; with bootstrap = 0 nothing is loaded, allocated or launched.
+
 Isolated: nothing of the training env, the model, the optimizer or torch's generators is written; policy state the evaluation needs (the CTS observation history, the
 recurrent memory's hidden state) lives in buffers of the evaluator."""
 import copy
@@ -111,6 +121,7 @@ DEFAULT_SCENARIOS = [["forward_1.0", 1.0, 0.0, 0.0], ["forward_2.0", 2.0, 0.0, 0
                      ["turn_1.0", 0.0, 0.0, 1.0], ["stand", 0.0, 0.0, 0.0]]
 MEAN_METRICS = EVAL_METRICS[1:9]          # reported as per-step means; `falls` per robot, `survival`, `n_envs` next to them
 RESULT_KEYS = MEAN_METRICS + ("falls", "survival", "n_envs")
+CI_KEYS = MEAN_METRICS + ("falls", "survival")          # what `evaluation.bootstrap` puts an interval on: the figures _row() makes of ONE reduce row
 # name, {field: value}; fields: dv [m/s: forward, left, up in the heading frame] and the dynamics values of ROBUST_MASK.  `nominal` is the sham push: the same windows, dv = 0
 DEFAULT_PERTURBATIONS = [["nominal", {}], ["push_front_1.0", {"dv": [1.0, 0.0, 0.0]}], ["push_side_1.0", {"dv": [0.0, 1.0, 0.0]}], ["payload_3kg", {"added_mass": 3.0}],
                          ["motor_0.8", {"strength": 0.8}], ["kp_0.8", {"kp_mul": 0.8}], ["friction_0.3", {"friction": 0.3}]]
@@ -145,6 +156,48 @@ EVAL_SOURCE = {"last_actions": "last_last_actions"}
 
 def _get(section, key, default=None):
     return section.get(key, default) if isinstance(section, dict) else getattr(section, key, default)
+
+
+def replicate_metrics(rows):
+    """rows: float64 [B, GO2NN_EVAL_NUM + 2], one reduce row per bootstrap replicate -> {metric: float64 [B]} for CI_KEYS: PolicyEvaluator._row's arithmetic on every row
+    at once (one IEEE division each: the same bits), NaN where _row reports NaN"""
+    rows = np.asarray(rows, np.float64)
+    n, steps = rows[:, GO2NN_EVAL_NUM], rows[:, 0]
+    per = lambda x, d: np.divide(x, d, out=np.full(x.shape, np.nan), where=d > 0)
+    out = {m: per(rows[:, 1 + i], steps) for i, m in enumerate(MEAN_METRICS)}
+    out["falls"], out["survival"] = per(rows[:, EVAL_METRICS.index("falls")], n), per(rows[:, GO2NN_EVAL_NUM + 1], n)
+    return out
+
+
+def interval(replicates, confidence):
+    """the percentile interval of a figure's replicates -> [lo, hi] (plain floats); [nan, nan] where every replicate is NaN"""
+    x = np.asarray(replicates, np.float64)
+    if x.size == 0 or np.isnan(x).all():
+        return [float("nan"), float("nan")]
+    lo, hi = np.nanquantile(x, [(1.0 - confidence) / 2.0, (1.0 + confidence) / 2.0])
+    return [float(lo), float(hi)]
+
+
+def intervals(rows, confidence):
+    """rows: float64 [B, 12], a leaf's reduce row per replicate -> its "ci" entry {metric: [lo, hi]} for CI_KEYS: interval() of every figure's replicates — taken in one
+    call where no replicate is NaN (the quantile of numbers is nanquantile's), figure by figure otherwise"""
+    reps = replicate_metrics(rows)
+    mat = np.stack([reps[m] for m in CI_KEYS], 1)
+    if np.isnan(mat).any():
+        return {m: interval(reps[m], confidence) for m in CI_KEYS}
+    q = np.quantile(mat, [(1.0 - confidence) / 2.0, (1.0 + confidence) / 2.0], axis=0)
+    return {m: [float(q[0, i]), float(q[1, i])] for i, m in enumerate(CI_KEYS)}
+
+
+def compare(reps_a, reps_b, confidence=0.95):
+    """The paired comparison of two evaluations of ONE evaluator (same robots, same `bootstrap_seed`): replicate b of both redrew the same robots, so d_b = a_b - b_b
+    is a replicate of the difference — common random numbers, far tighter than two marginal intervals side by side.
+    -> {"diff_ci": [lo, hi] of d, "tied": lo <= 0 <= hi}; a difference that does not exist (every d_b NaN) is [nan, nan] and not tied: nothing can be said of it"""
+    a, b = np.asarray(reps_a, np.float64), np.asarray(reps_b, np.float64)
+    if a.shape != b.shape or a.ndim != 1:
+        raise ValueError("compare: two replicate vectors of one length are needed, got shapes %s and %s" % (a.shape, b.shape))
+    lo, hi = interval(a - b, confidence)
+    return {"diff_ci": [lo, hi], "tied": bool(lo <= 0.0 <= hi)}
 
 
 def evaluation_env_cfg(env_cfg, ev):
@@ -433,6 +486,11 @@ class PolicyEvaluator:
             raise ValueError("evaluation.blackbox: robots kept per cell, >= 0 (0 = off), got %r" % (_get(evaluation, "blackbox"),))
         if self.blackbox > 0:
             self._build_blackbox()
+        self.bootstrap = int(_get(evaluation, "bootstrap", 0) or 0)
+        if self.bootstrap < 0:
+            raise ValueError("evaluation.bootstrap: replicates, >= 0 (0 = off), got %r" % (_get(evaluation, "bootstrap"),))
+        if self.bootstrap > 0:
+            self._build_bootstrap()
         self.evaluations = 0
         self.last_mode = None          # "eager" / "graph": how the latest evaluation's steps ran
 
@@ -770,6 +828,26 @@ class PolicyEvaluator:
         assert len(names) == self.num_cells == (T_ * S * (len(self.levels) if self.ladder else P))
         self.cell_names = names
 
+    def _build_bootstrap(self):
+        """the bootstrap's device side: the cells' member lists (CSR, env indices ascending within a cell; checked on the host, the launch cannot report a bad index) and
+        the [B, cells, 12] fp64 table, refused before anything is allocated when it is larger than `bootstrap_max_bytes`"""
+        B, cols = self.bootstrap, GO2NN_EVAL_NUM + 2
+        self.confidence = float(_get(self.ev, "confidence", 0.95))
+        if not 0.0 < self.confidence < 1.0:
+            raise ValueError("evaluation.confidence: an interval level inside (0, 1), got %r" % (_get(self.ev, "confidence"),))
+        self.bootstrap_seed = int(_get(self.ev, "bootstrap_seed", 2718)) & 0xFFFFFFFF
+        need, cap = B * self.num_cells * cols * 8, int(_get(self.ev, "bootstrap_max_bytes", 256 << 20))
+        if need > cap or B * self.num_cells * cols >= 2 ** 31:
+            raise ValueError("evaluation.bootstrap: %d replicates x %d cells x %d columns x 8 bytes = %d bytes, more than evaluation.bootstrap_max_bytes = %d (or 2^31 values); "
+                             "lower evaluation.bootstrap" % (B, self.num_cells, cols, need, cap))
+        sizes = np.bincount(self.cell_host, minlength=self.num_cells)
+        self.cell_start_host = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
+        self.cell_envs_host = np.argsort(self.cell_host, kind="stable").astype(np.int32)
+        self._check(self.nn.go2nn_eval_bootstrap_check(C.c_void_p(self.cell_start_host.ctypes.data), C.c_void_p(self.cell_envs_host.ctypes.data), self.num_envs, self.num_cells),
+                    "go2nn_eval_bootstrap_check")
+        self.cell_start, self.cell_envs = torch.from_numpy(self.cell_start_host).to(self.device), torch.from_numpy(self.cell_envs_host).to(self.device)
+        self.boot_out = torch.zeros(B, self.num_cells, cols, dtype=torch.float64, device=self.device)
+
     def _keep_fallen(self, fell):
         """of the fallen robots, per cell of the finest partition the mode reports, the `blackbox` lowest env indices"""
         cells = self.cell_host[fell]
@@ -966,6 +1044,9 @@ class PolicyEvaluator:
         per tracked robot), "terrain_names" and "scenarios".
         With `evaluation.blackbox` also "falls": FallRecorder.fetch() of the kept fallen robots plus the labels a trace gets, "cell_names", "cell_of_robot",
         "fell_per_cell" (robots that fell per cell, kept or not) and "kept_per_cell".
+        With `evaluation.bootstrap` also "bootstrap": {"replicates", "seed", "confidence", "table" (go2nn_eval_bootstrap's raw output, float64 [B, cells, 12]), "overall"
+        (float64 [B, 12]: the overall row of every replicate; replicate_metrics() turns it into the figures' replicates)}, and every leaf dict with RESULT_KEYS gains
+        "ci": {metric: [lo, hi]} for CI_KEYS.
         use_graph: None = eager, or with `evaluation.replay` eager the first time and a captured chunk afterwards (on the GPU); True / False force it."""
         with torch.inference_mode():
             if self.evaluations > 0:
@@ -1021,6 +1102,10 @@ class PolicyEvaluator:
             self.last_mode = "graph" if done else "eager"
             self._check(self.nn.go2nn_eval_reduce(C.c_void_p(self.acc.data_ptr()), C.c_void_p(self.group.data_ptr()), self.num_envs, self.num_cells,
                                                   C.c_void_p(self.out.data_ptr()), self._stream()), "go2nn_eval_reduce")
+            if self.bootstrap > 0:          # the same accumulators, the same cells: B resampled reduce tables (after the replayed chunks, never inside a capture)
+                self._check(self.nn.go2nn_eval_bootstrap(C.c_void_p(self.acc.data_ptr()), C.c_void_p(self.cell_start.data_ptr()), C.c_void_p(self.cell_envs.data_ptr()),
+                                                         self.num_envs, self.num_cells, self.bootstrap, self.bootstrap_seed, C.c_void_p(self.boot_out.data_ptr()), self._stream()),
+                            "go2nn_eval_bootstrap")
             rtable = None
             if rin is not None:
                 self._check(self.nn.go2nn_robust_reduce(C.c_void_p(self.rtable.data_ptr()), C.c_void_p(self.group.data_ptr()), self.num_envs, self.num_cells,
@@ -1048,11 +1133,14 @@ class PolicyEvaluator:
                 atable = self.aout.cpu().numpy().copy()
                 self.asym_last = None
             table = self.out.cpu().numpy().copy()          # the device -> host copy (and synchronisation) of an evaluation
+            btable = self.boot_out.cpu().numpy().copy() if self.bootstrap > 0 else None
             trace = self.recorder.fetch() if self.recorder is not None else None
             falls = self.fall_recorder.fetch(self._keep_fallen) if self.fall_recorder is not None else None
             self._graph = None
             self.evaluations += 1
         res = self._results(table, rtable, ltable, mtable)
+        if btable is not None:
+            self._bootstrap_results(res, btable)
         if gtable is not None:
             self._gait_results(res, gtable)
         if atable is not None:
@@ -1211,6 +1299,41 @@ class PolicyEvaluator:
         asym, axes = self._addon_tree(acells, self._asym_row, self._asym_pool)
         res.update(asymmetry=asym, asymmetry_table=acells, asymmetry_cells=axes, asymmetry_contact_threshold=self.asym_threshold)
 
+    def _bootstrap_results(self, res, bcells):
+        """bcells: go2nn_eval_bootstrap's table [B, cells, 12] -> "ci" in every leaf dict _row() made, and res["bootstrap"].  A partition's replicate rows are the sums of
+        its cells' replicate rows: _results' own reshapes and sums, one axis further in"""
+        B, conf = bcells.shape[0], self.confidence
+        T, S, G, P = len(self.terrain_names), len(self.scenarios), len(self.groups), len(self.perturbations or self.sensors or [None])
+        ci = lambda rows: intervals(rows, conf)
+        if self.ladder:
+            c5 = bcells.reshape(B, T, len(self.levels), S, -1)
+            table = c5.sum(2).reshape(B, G, -1)
+        else:
+            c4 = bcells.reshape(B, G, P, -1)
+            table = c4.sum(2)
+        overall = table.sum(1)
+        res["overall"]["ci"] = ci(overall)
+        for ti, t in enumerate(self.terrain_names):
+            for si, s in enumerate(self.scenarios):
+                res["groups"][t][s[0]]["ci"] = ci(table[:, ti * S + si])
+        if self.perturbations is not None or self.sensors is not None:
+            axis = "perturbations" if self.perturbations is not None else "sensors"
+            for pi, (n, _) in enumerate(self.perturbations or self.sensors):
+                res[axis][n]["ci"] = ci(c4[:, :, pi].sum(1))
+                for ti, t in enumerate(self.terrain_names):
+                    for si, s in enumerate(self.scenarios):
+                        res["cells"][t][s[0]][n]["ci"] = ci(c4[:, ti * S + si, pi])
+        if self.ladder:
+            for ti, t in enumerate(self.terrain_names):
+                for li, lv in enumerate(self.levels):
+                    for si, s in enumerate(self.scenarios):
+                        res["ladder"][t][lv][s[0]]["ci"] = ci(c5[:, ti, li, si])
+        if self.maneuvers is not None:          # (a "scenario" is a maneuver there)
+            t3 = table.reshape(B, T, S, -1)
+            for mi, m in enumerate(self.maneuvers):
+                res["maneuvers"][m[0]]["ci"] = ci(t3[:, :, mi].sum(1))
+        res["bootstrap"] = {"replicates": B, "seed": self.bootstrap_seed, "confidence": conf, "table": bcells, "overall": overall}
+
     def _results(self, cells, rcells=None, lcells=None, mcells=None):
         """cells: the eval reduce table per (terrain, scenario, perturbation) cell; rcells: the robust one (None without perturbations: a cell is a group then);
         lcells: the ladder's (None without the ladder), cells being per (terrain, level, scenario) then;  mcells: the maneuvers' (None without maneuvers), per
@@ -1266,7 +1389,7 @@ class PolicyEvaluator:
 # ---------------------------------------------------------------------------------------------------------------------------------------------------------------
 def scalars(res):
     """[(tag, value)]: with gait 'Eval/gait/<key>' and 'Eval/gait/<terrain>/<scenario>/<key>'; with asymmetry 'Eval/asymmetry/<key>' and 'Eval/asymmetry/<terrain>/<scenario>/<key>'; 'Eval/<metric>' for the overall figures, 'Eval/<terrain>/<scenario>/<metric>' per group, with perturbations 'Eval/robust/<name>/<metric>', with
-    maneuvers 'Eval/maneuver/<name>/<metric>', with sensor conditions 'Eval/sensors/<name>/<metric>' and, with the ladder, 'Eval/ladder/<terrain>/{level_cleared,mean_level_cleared}' and 'Eval/ladder/mean_level_cleared'; with the black box 'Eval/falls/robots_fell'"""
+    maneuvers 'Eval/maneuver/<name>/<metric>', with sensor conditions 'Eval/sensors/<name>/<metric>' and, with the ladder, 'Eval/ladder/<terrain>/{level_cleared,mean_level_cleared}' and 'Eval/ladder/mean_level_cleared'; with the black box 'Eval/falls/robots_fell'; with the bootstrap 'Eval/ci_low/<metric>' and 'Eval/ci_high/<metric>' (overall only)"""
     out = [("Eval/" + k, res["overall"][k]) for k in RESULT_KEYS]
     for t, per in res["groups"].items():
         for s, d in per.items():
@@ -1293,6 +1416,9 @@ def scalars(res):
                 out += [("Eval/asymmetry/%s/%s/%s" % (t, s, k), d[k]) for k in ASYM_KEYS]
     if res.get("falls") is not None:          # with the black box: how many robots fell on a counted step
         out.append(("Eval/falls/robots_fell", res["falls"]["fell_total"]))
+    if res.get("bootstrap") is not None:          # with the bootstrap: 'Eval/ci_low/<metric>' and 'Eval/ci_high/<metric>', the overall figures only
+        for k in CI_KEYS:
+            out += [("Eval/ci_low/" + k, res["overall"]["ci"][k][0]), ("Eval/ci_high/" + k, res["overall"]["ci"][k][1])]
     return out
 
 
@@ -1319,6 +1445,8 @@ def results_dict(res, it=None):
     if res.get("asymmetry") is not None:          # as the gait section: every partition the mode reports
         d["asymmetry"] = plain(res["asymmetry"])
         d["asymmetry_contact_threshold"] = float(res["asymmetry_contact_threshold"])
+    if res.get("bootstrap") is not None:          # how the "ci" entries of the leaves above were made
+        d["bootstrap"] = {k: res["bootstrap"][k] for k in ("replicates", "seed", "confidence")}
     return d
 
 
@@ -1376,6 +1504,11 @@ def format_table(res):
             lines.append("%-44s " % falls["cell_names"][c] + "%17d %17d " % (falls["fell_per_cell"][c], int(k.sum()))
                          + " ".join("%17.4f" % median(sm[key][k]) for key in ("time_s", "tilt", "feet_in_contact")))
         lines.append("%-44s " % "all" + "%17d %17d" % (falls["fell_total"], len(falls["env_ids"])))
+    if res.get("bootstrap") is not None:          # one more block: the overall row again, every figure with its interval
+        bs, cols = res["bootstrap"], ("lin_vel_err", "ang_vel_err", "speed_along_cmd", "tilt", "power", "falls", "survival")
+        head = "%g %% interval, %d replicates" % (100.0 * bs["confidence"], bs["replicates"])
+        lines += ["", "%-36s " % head + " ".join("%34s" % c for c in cols)]
+        lines.append("%-36s " % "all" + " ".join("%34s" % ("%.4f [%.4f, %.4f]" % ((res["overall"][c],) + tuple(res["overall"]["ci"][c]))) for c in cols))
     return "\n".join(lines)
 
 

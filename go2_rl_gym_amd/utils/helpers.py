@@ -93,7 +93,7 @@ _RUNNER_OVERRIDES = ("max_iterations", "experiment_name", "run_name", "load_run"
 def update_cfg_from_args(env_cfg, cfg_train, args):
     """Command-line overrides onto the config objects (legged_gym/utils/helpers.py update_cfg_from_args): --num_envs onto the env config;
     --seed, --resume and the runner fields above onto the train config; the RoboGauge switches when the train config has that section (parsed and ignored: the service is
-    out of scope), --symmetry onto algorithm.symmetry, and next to them --evaluate / --eval_interval / --record / --robust / --ladder / --maneuvers / --sensors / --gait / --blackbox / --asymmetry onto the `evaluation` section."""
+    out of scope), --symmetry onto algorithm.symmetry, and next to them --evaluate / --eval_interval / --record / --robust / --ladder / --maneuvers / --sensors / --gait / --blackbox / --asymmetry / --ci onto the `evaluation` section."""
     if env_cfg is not None and args.num_envs is not None:
         env_cfg.env.num_envs = args.num_envs
     if cfg_train is None:
@@ -139,6 +139,8 @@ def update_cfg_from_args(env_cfg, cfg_train, args):
             ev.blackbox = args.blackbox
         if getattr(args, "asymmetry", False):
             ev.asymmetry = True
+        if getattr(args, "ci", None) is not None:
+            ev.bootstrap = args.ci
     return env_cfg, cfg_train
 
 
@@ -176,6 +178,9 @@ def get_args(argv=None):
     p.add_argument("--asymmetry", action="store_true", default=False, help="score left-right asymmetry too: how far the policy is from mirror-equivariant on the states it "
                    "visits, and how unequally the robot loads its left and right legs under mirror-symmetric commands (works next to every mode above; not for recurrent "
                    "policies): evaluation.asymmetry = True")
+    p.add_argument("--ci", type=int, nargs="?", const=1000, help="give every evaluated figure a bootstrap confidence interval from B resamplings of the robots within their "
+                   "cells (default 1000; works next to every mode above), and let evaluate.py --all_checkpoints compare every checkpoint with the best one on the same "
+                   "resamplings: evaluation.bootstrap = B")
     p.add_argument("--symmetry", action="store_true", default=False, help="train every PPO mini-batch on its left-right mirror image too (feed-forward PPO only): "
                    "algorithm.symmetry = True")
     p.add_argument("--record_steps", type=int, default=500, help="play.py --record: the last S steps of the rollout are kept")

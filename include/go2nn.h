@@ -811,6 +811,24 @@ int go2nn_asym_accumulate(const Go2nnAsymIn* in, const float* actions, const flo
 /* GO2NN_EINVAL for null pointers, N < 1, G outside 1 .. 65535; the host build also for a group id outside [0, G). */
 int go2nn_asym_reduce(const float* table, const int32_t* group, int32_t N, int32_t G, double* out, void* stream);
 
+/* ---- the evaluator's confidence intervals: bootstrap replicates of go2nn_eval_reduce's table (go2_rl_gym_amd/utils/evaluator.py, `evaluation.bootstrap`;
+ * csrc/go2nn_bootstrap.h, the launch in csrc/go2nn_eval.h).
+ * ADDED WITHIN ABI 7: two new entry points, nothing existing changes, GO2NN_ABI_VERSION stays 7.
+ * One plain launch (capturable) after go2nn_eval_reduce, on the same acc [GO2NN_EVAL_NUM, N]: a STRATIFIED bootstrap — the robots are redrawn with replacement inside
+ * their cells, every cell keeps its size.  The cells' members come as a CSR list: cell_start int32 [G + 1], cell_envs int32 [cell_start[G]], the envs of cell g at
+ * cell_envs[cell_start[g] .. cell_start[g + 1]) (the evaluator lists them ascending), both in acc's memory space.  With n = cell_start[g + 1] - cell_start[g]:
+ *   out[(b G + g) 12 + c] = sum over k = 0 .. n - 1 of term(cell_envs[cell_start[g] + j(b, g, k)], c)                     out: fp64 [B, G, GO2NN_EVAL_NUM + 2] row-major
+ *   j(b, g, k) = ((uint64) x * n) >> 32,   x = word (k & 3) of philox4x32_10(counter (b, g, k >> 2, 0), key (seed, 7))
+ * term(e, c) is go2nn_eval_reduce's: acc[c, e] for c < GO2NN_EVAL_NUM, 1 for c = GO2NN_EVAL_NUM, acc[FALLS, e] == 0 for the last column.  The sum runs in fp64 in
+ * increasing k and the index is integer arithmetic, so the device, the host build and a restatement in Python integers agree bit for bit; an empty cell gives twelve
+ * zeros; replicate b does not depend on B.  Key word 7 is the bootstrap's: 1 .. 6 belong to the sensor kernels.  One lane per (replicate, cell), no LDS, no atomics.
+ * go2nn_eval_bootstrap_check looks at the list in HOST memory before the upload (the launch cannot report a bad index): GO2NN_EINVAL for a null pointer, N < 1, G outside
+ * [1, 65535], cell_start[0] != 0, a decreasing cell_start, cell_start[G] > N, an env outside [0, N).
+ * go2nn_eval_bootstrap: GO2NN_EINVAL, with nothing written, for a null pointer, N < 1, G outside [1, 65535], B outside [1, 2^20], B G 12 >= 2^31; the host build also for
+ * what go2nn_eval_bootstrap_check refuses. */
+int go2nn_eval_bootstrap_check(const int32_t* host_cell_start, const int32_t* host_cell_envs, int32_t N, int32_t G);
+int go2nn_eval_bootstrap(const float* acc, const int32_t* cell_start, const int32_t* cell_envs, int32_t N, int32_t G, int32_t B, uint32_t seed, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

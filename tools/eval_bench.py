@@ -1,6 +1,6 @@
 """What one policy evaluation costs (utils/evaluator.py), and what the metric kernel saves over torch expressions.
 
-    python tools/eval_bench.py [--task go2_flat] [--reps 3] [--robust] [--ladder] [--maneuvers] [--sensors] [--blackbox] [--asymmetry] [--out profiles/eval_bench.json]
+    python tools/eval_bench.py [--task go2_flat] [--reps 3] [--robust] [--ladder] [--maneuvers] [--sensors] [--blackbox] [--asymmetry] [--ci] [--out profiles/eval_bench.json]
 
 Measures, on cuda:0, with the task's default `evaluation` section (1024 robots, 1 s + 10 s):
   * wall time of evaluate() run eagerly and with the captured chunk of steps replayed (simulator re-creation, capture and the final host copy included: it is what
@@ -22,6 +22,10 @@ back-to-back call with no robot frozen, by the same method.
 --asymmetry: a measurement of its own, ADDED to profiles/asymmetry_bench.json under the task's name: evaluate() run eagerly with evaluation.asymmetry off and on,
 alternating, --reps runs each (at least five) in this one session — best, median, spread and every run —, and per back-to-back call on the evaluator's own buffers the
 three extra pieces of a step: the mirror launch, the policy's second forward and go2nn_asym_accumulate.
+--ci: a measurement of its own, written to profiles/bootstrap_bench.json: evaluate() run eagerly with evaluation.bootstrap off and at 1000 replicates, alternating, --reps
+runs each (at least five) in this one session — best, median, spread, every run and the difference of the medians —, and go2nn_eval_bootstrap alone per back-to-back call
+on the evaluation's own accumulators at the plain cells, at --robust's cells and at seven times as many (--robust on a terrain task), each next to the same resampling
+written in numpy on the host with the copy of the accumulators it would need.
 Writes one JSON file and prints it."""
 import argparse
 import ctypes as C
@@ -200,6 +204,98 @@ def asymmetry_main(a):
         e.close()
 
 
+def numpy_bootstrap(acc, start, envs, B, seed):
+    """go2nn_eval_bootstrap's resampling on the host: the same Philox words and index rule (include/go2nn.h) on uint64 arrays, the gathered terms summed by numpy (pairwise:
+    the same replicates to the last bits, not the same bits) -> [B, G, 12]"""
+    import numpy as np
+    from go2_rl_gym_amd._nn import EVAL_METRICS
+    m32, s32 = np.uint64(0xFFFFFFFF), np.uint64(32)
+    N, G = acc.shape[1], len(start) - 1
+    terms = np.concatenate([acc.astype(np.float64), np.ones((1, N)), (acc[EVAL_METRICS.index("falls")] == 0).astype(np.float64)[None]]).T.copy()          # [N, 12]
+    out = np.zeros((B, G, terms.shape[1]))
+    for g in range(G):
+        s0, n = int(start[g]), int(start[g + 1] - start[g])
+        if n == 0:
+            continue
+        blocks = (n + 3) // 4
+        c0, c2 = np.broadcast_arrays(np.arange(B, dtype=np.uint64)[:, None], np.arange(blocks, dtype=np.uint64)[None, :])
+        c1, c3, k0, k1 = np.full_like(c0, g), np.zeros_like(c0), np.uint64(seed), np.uint64(7)
+        for _ in range(10):
+            p0, p1 = np.uint64(0xD2511F53) * c0, np.uint64(0xCD9E8D57) * c2
+            c0, c1, c2, c3 = (p1 >> s32) ^ c1 ^ k0, p1 & m32, (p0 >> s32) ^ c3 ^ k1, p0 & m32
+            k0, k1 = (k0 + np.uint64(0x9E3779B9)) & m32, (k1 + np.uint64(0xBB67AE85)) & m32
+        x = np.stack([c0, c1, c2, c3], 2).reshape(B, blocks * 4)[:, :n]
+        j = ((x * np.uint64(n)) >> s32).astype(np.int64)
+        out[:, g] = terms[envs[s0 + j]].sum(1)
+    return out
+
+
+def bootstrap_main(a):
+    """--ci: what the bootstrap costs one evaluation, next to the option-off evaluation of the same commit in the same session, and the launch alone next to the same
+    resampling in numpy on the host -> profiles/bootstrap_bench.json"""
+    import numpy as np
+    B = 1000
+    env_cfg, train_cfg = task_registry.get_cfgs(a.task)
+    ev_cfg = class_to_dict(train_cfg.evaluation)
+    make = lambda **over: PolicyEvaluator(env_cfg, dict(ev_cfg, **over), task_class=task_registry.get_task_class(a.task), device="cuda:0")
+    evs = {"off": make(bootstrap=0), "on": make(bootstrap=B)}
+    from go2_rl_gym_amd.rsl_rl.modules import ActorCritic
+    torch.manual_seed(0)
+    ac = ActorCritic(45, 263, 12, **{k: v for k, v in class_to_dict(train_cfg.policy).items() if k in ("actor_hidden_dims", "critic_hidden_dims", "activation", "init_noise_std")}).to("cuda:0")
+    res = {k: ev.evaluate(ac, use_graph=False) for k, ev in evs.items()}
+    assert res["on"]["table"].tobytes() == res["off"]["table"].tobytes() and "bootstrap" not in res["off"]
+    ev = evs["on"]
+    N, st, p = ev.num_envs, ev._stream(), lambda t: C.c_void_p(t.data_ptr())
+    entry = {"task": a.task, "device": torch.cuda.get_device_name(0), "num_envs": N, "steps": ev.warmup_steps + ev.steps, "replicates": B, "confidence": ev.confidence,
+             "overall": {k: [res["on"]["overall"][k]] + res["on"]["overall"]["ci"][k] for k in res["on"]["overall"]["ci"]}, "launch": {}}
+    # the launch alone, on the evaluation's own accumulators: the plain cells, --robust's cells of this task, and as many cells as --robust has on the terrain task (7 kinds)
+    robust = make(perturbations=[[n, dict(f)] for n, f in DEFAULT_PERTURBATIONS])
+    layouts = {"plain": ev.cell_host, "robust": robust.cell_host, "robust_7_terrain_kinds": (np.arange(N) % (7 * robust.num_cells)).astype(np.int32)}
+    robust.close()
+    acc_host = ev.acc.cpu().numpy()
+    for name, cell in layouts.items():
+        G = int(cell.max()) + 1
+        start = np.concatenate([[0], np.cumsum(np.bincount(cell, minlength=G))]).astype(np.int32)
+        envs = np.argsort(cell, kind="stable").astype(np.int32)
+        assert ev.nn.go2nn_eval_bootstrap_check(C.c_void_p(start.ctypes.data), C.c_void_p(envs.ctypes.data), N, G) == 0
+        s_d, e_d = torch.from_numpy(start).to("cuda:0"), torch.from_numpy(envs).to("cuda:0")
+        out = torch.zeros(B, G, 12, dtype=torch.float64, device="cuda:0")
+        fn = lambda: ev.nn.go2nn_eval_bootstrap(p(ev.acc), p(s_d), p(e_d), N, G, B, ev.bootstrap_seed, p(out), st)
+        assert fn() == 0
+        timed(fn, 20)
+        dev_us, wall_us = timed(fn, 200)
+        host = []
+        for _ in range(3):          # the same resampling on the host, with the copies it would need: the accumulators down, nothing up
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            ref = numpy_bootstrap(ev.acc.cpu().numpy(), start, envs, B, ev.bootstrap_seed)
+            host.append((time.perf_counter() - t0) * 1e3)
+        t0 = time.perf_counter()
+        got = out.cpu().numpy()
+        copy_ms = (time.perf_counter() - t0) * 1e3
+        scale = np.abs(ref).max((0, 1))
+        entry["launch"][name] = {"cells": G, "robots_per_cell": [int(np.diff(start).min()), int(np.diff(start).max())], "device_us_per_call_back_to_back": dev_us,
+                                 "host_us_per_call": wall_us, "table_bytes": got.nbytes, "table_copy_ms": copy_ms, "numpy_on_host_ms": {"best": min(host), "all": host},
+                                 "largest_gap_to_numpy_over_column_max": float((np.abs(got - ref).max((0, 1)) / np.maximum(scale, 1e-300)).max())}
+        assert np.array_equal(got[:, :, 10], ref[:, :, 10]) and np.array_equal(acc_host, ev.acc.cpu().numpy())
+    if not a.kernel_only:
+        walls = {k: [] for k in evs}
+        for _ in range(max(a.reps, 5)):          # alternating, in this one session
+            for k, e in evs.items():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                e.evaluate(ac, use_graph=False)
+                walls[k].append((time.perf_counter() - t0) * 1e3)
+        entry["evaluate_wall_ms_eager"] = {k: {"best": min(w), "median": statistics.median(w), "spread": max(w) - min(w), "all": w} for k, w in walls.items()}
+        entry["evaluate_wall_ms_eager"]["on_minus_off_median"] = statistics.median(walls["on"]) - statistics.median(walls["off"])
+        os.makedirs(os.path.dirname(a.out), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(entry, f, indent=1)
+    print(json.dumps(entry))
+    for e in evs.values():
+        e.close()
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--task", default="go2_flat")
@@ -211,9 +307,12 @@ def main():
     p.add_argument("--sensors", action="store_true")
     p.add_argument("--blackbox", action="store_true")
     p.add_argument("--asymmetry", action="store_true")
+    p.add_argument("--ci", action="store_true")
     p.add_argument("--out", default=None)
     a = p.parse_args()
-    a.out = a.out or os.path.join(ROOT, "profiles", "asymmetry_bench.json" if a.asymmetry else "blackbox_bench.json" if a.blackbox else "eval_bench.json")
+    a.out = a.out or os.path.join(ROOT, "profiles", "bootstrap_bench.json" if a.ci else "asymmetry_bench.json" if a.asymmetry else "blackbox_bench.json" if a.blackbox else "eval_bench.json")
+    if a.ci:
+        return bootstrap_main(a)
     if a.asymmetry:
         return asymmetry_main(a)
     if a.blackbox:
