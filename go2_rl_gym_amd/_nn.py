@@ -215,6 +215,23 @@ class Go2nnMirrorJob(C.Structure):          # (within ABI 7) perm and sign None:
 GO2NN_MIRROR_MAX_JOBS = 16
 
 
+class Go2nnMirrorLoss(C.Structure):          # (within ABI 7) perm and sign None: the identity table
+    _fields_ = [("y_a", C.c_void_p), ("w_mu", C.c_void_p), ("b_mu", C.c_void_p), ("perm", C.c_void_p), ("sign", C.c_void_p), ("gz_a", C.c_void_p), ("partials", C.c_void_p),
+                ("B", C.c_int32), ("A", C.c_int32), ("K", C.c_int32), ("coef", C.c_float)]
+
+
+def mirror_loss_table_tensors(lib, table, device):
+    """The action table of the mirror loss — an involution with sign[perm[j]] == sign[j] —, checked on the host (go2nn_mirror_loss_check_table) and uploaded
+    -> (int16 tensor [A], float32 tensor [A]) on `device`"""
+    import numpy as np
+    perm, sign = np.ascontiguousarray(table[0], np.int16), np.ascontiguousarray(table[1], np.float32)
+    if perm.ndim != 1 or perm.shape != sign.shape:
+        raise ValueError("a mirror table is a pair of 1-d arrays of one length, got shapes %s and %s" % (perm.shape, sign.shape))
+    if lib.go2nn_mirror_loss_check_table(perm.ctypes.data, sign.ctypes.data, perm.shape[0]) != 0:
+        raise ValueError(lib.go2nn_last_error().decode())
+    return torch.from_numpy(perm).to(device), torch.from_numpy(sign).to(device)
+
+
 def mirror_table_tensors(lib, table, device):
     """A (perm, sign) table of utils/symmetry.py, checked on the host (go2nn_mirror_check_table: the launch cannot report a bad index) and uploaded
     -> (int16 tensor [W], float32 tensor [W]) on `device`"""
@@ -346,6 +363,10 @@ def bind(path):
     lib.go2nn_sensor_rand_apply.argtypes = [C.POINTER(Go2nnSensorIn), C.POINTER(Go2nnSensorRand), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
     lib.go2nn_mirror_check_table.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
     lib.go2nn_mirror_rows.argtypes = [C.POINTER(Go2nnMirrorJob), C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
+    lib.go2nn_mirror_loss_rows.argtypes = [C.c_int32] * 3
+    lib.go2nn_mirror_loss_cols.argtypes = [C.c_int32] * 2
+    lib.go2nn_mirror_loss_check_table.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+    lib.go2nn_mirror_loss.argtypes = [C.POINTER(Go2nnMirrorLoss), C.c_void_p]
     if lib.go2nn_abi_version() != GO2NN_ABI_VERSION:
         raise RuntimeError("%s: ABI version %d, expected %d" % (path, lib.go2nn_abi_version(), GO2NN_ABI_VERSION))
     return lib

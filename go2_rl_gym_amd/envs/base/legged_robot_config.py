@@ -253,6 +253,7 @@ class LeggedRobotCfgPPO(BaseConfig):
         desired_kl = 0.01
         max_grad_norm = 1.0
         symmetry = False          # train every mini-batch on its left-right mirror image too (utils/symmetry.py; feed-forward PPO only; --symmetry)
+        mirror_loss_coef = 0.0    # > 0 (--mirror_loss COEF, needs symmetry): add COEF x mean((pi(o) - M_a pi(M_o o))^2) over the mini-batch to the PPO loss; feed-forward PPO only
 
     class runner:
         policy_class_name = "ActorCritic"

@@ -18,6 +18,7 @@ The env's observation buffers are persistent device buffers that the step kernel
 rebinds `obs_buf` to fresh tensors every step), so `act()` copies the observations into the rollout storage immediately
 instead of keeping a reference until `process_env_step`.
 """
+import math
 import os
 
 import torch
@@ -31,7 +32,10 @@ from ._graph import CapturedStep, GradBucket, all_captured
 class PPO(_RolloutHeads):
     def __init__(self, actor_critic, num_learning_epochs=1, num_mini_batches=1, clip_param=0.2, gamma=0.998, lam=0.95, value_loss_coef=1.0,
                  entropy_coef=0.0, learning_rate=1e-3, max_grad_norm=1.0, use_clipped_value_loss=True, schedule="fixed", desired_kl=0.01,
-                 device="cpu", lib=None, use_graphs=None, fused_loss=None, fused_rollout=None, symmetry=False):
+                 device="cpu", lib=None, use_graphs=None, fused_loss=None, fused_rollout=None, symmetry=False, mirror_loss_coef=0.0):
+        mirror_loss_coef = 0.0 if mirror_loss_coef is None else float(mirror_loss_coef)
+        if not (math.isfinite(mirror_loss_coef) and mirror_loss_coef >= 0.0):
+            raise ValueError("PPO(mirror_loss_coef=...) takes a finite weight >= 0, got %r" % (mirror_loss_coef,))
         self.desired_kl, self.schedule, self.learning_rate = desired_kl, schedule, learning_rate
         self.actor_critic = actor_critic
         self.actor_critic.to(device)
@@ -58,6 +62,14 @@ class PPO(_RolloutHeads):
         self._sym, self._sym_t, self._aug = self._symmetry_tables(symmetry), None, None
         if self._sym is not None and self._rnn:
             raise NotImplementedError("symmetry augmentation with a recurrent policy is not implemented (the mirrored hidden state is a different piece of work)")
+        # the mirror (equivariance) loss on the augmented mini-batches (the `mirror loss` section below): 0 = off, and then nothing is loaded, allocated or launched.
+        # mirror_loss: the last update's mean of L_mirror / coef (= equivariance_rmse^2 of its mini-batches) over its mini-batch steps
+        self.mirror_loss_coef, self.mirror_loss, self._ml, self._ml_dev = mirror_loss_coef, 0.0, None, None
+        if mirror_loss_coef > 0.0 and self._rnn:
+            raise NotImplementedError("the mirror loss with a recurrent policy is not implemented (it is a term on the mini-batches of symmetry augmentation)")
+        if mirror_loss_coef > 0.0 and self._sym is None:
+            raise ValueError("PPO(mirror_loss_coef > 0) is a term on the mirror-augmented mini-batches: it needs symmetry=mirror_tables(env_cfg) (algorithm.symmetry = True; "
+                             "--mirror_loss sets both)")
         self._sync_replicas(self.actor_critic)
 
     def rebind_lr(self):
@@ -158,15 +170,19 @@ class PPO(_RolloutHeads):
         if self.fused_loss:
             mu_b, val_b = ac.actor(obs_b), self._value(cobs_b)          # under autograd: one node per network (modules/fused.py:_FusedMLP)
             loss, stats = _FusedPPOLoss.apply(mu_b, ac.std, val_b, self, act_b, tv_b, adv_b, ret_b, old_lp_b, old_mu_b, old_sig_b)
+            if self.mirror_loss_coef > 0.0:
+                loss = loss + self._mirror_term(mu_b)
             return loss, stats[1], stats[0], stats[2]
         ac.update_distribution(obs_b)     # the reference calls act() here and discards the sample (ppo.py:131)
         lp_b = ac.get_actions_log_prob(act_b)
         val_b = self._value(cobs_b)
         loss, value_loss, surrogate_loss, _, kl_mean = self.ppo_terms(lp_b, val_b, ac.action_mean, ac.action_std, ac.entropy, tv_b, adv_b, ret_b, old_lp_b, old_mu_b, old_sig_b)
+        if self.mirror_loss_coef > 0.0:
+            loss = loss + self._mirror_term(ac.action_mean)
         return loss, value_loss, surrogate_loss, kl_mean
 
     def _update_eager(self):
-        mean_value_loss, mean_surrogate_loss = 0.0, 0.0
+        mean_value_loss, mean_surrogate_loss, mean_mirror = 0.0, 0.0, 0.0
         batches = self._rnn_batches() if self._rnn else self.storage.mini_batch_generator(self.num_mini_batches, self.num_learning_epochs)
         for batch in batches:
             if self._sym is not None:
@@ -175,7 +191,11 @@ class PPO(_RolloutHeads):
             self._eager_step(loss, self.optimizer, self._params, kl_mean)
             mean_value_loss += value_loss.item()
             mean_surrogate_loss += surrogate_loss.item()
+            if self.mirror_loss_coef > 0.0:
+                mean_mirror += self._ml.item()
         n = self.num_learning_epochs * self.num_mini_batches
+        if self.mirror_loss_coef > 0.0:
+            self.mirror_loss = mean_mirror / n
         return mean_value_loss / n, mean_surrogate_loss / n
 
     # ---- symmetry augmentation ---------------------------------------------------------------------------------
@@ -198,14 +218,18 @@ class PPO(_RolloutHeads):
         cobs = s.privileged_obs if (self.storage is None or self.storage.privileged_observations is not None) else s.obs
         return {"obs": s.obs, "cobs": cobs, "act": s.action, "mu": s.action, "sig": s.action_std}.get(key)
 
+    def _sym_tensors(self, dev):
+        """the tables as torch tensors (int64 perm, float32 sign) per _KEYS entry, made once"""
+        if self._sym_t is None:
+            self._sym_t = {k: (torch.as_tensor(self._sym_table(k)[0].astype("int64"), device=dev), torch.as_tensor(self._sym_table(k)[1], device=dev)) for k in ("obs", "cobs", "act", "mu", "sig")}
+        return self._sym_t
+
     def _sym_batch(self, batch):
         """The eager formulation (torch indexing), the numerical yardstick of the kernel path: batch of mini_batch_generator -> the same tuple at twice the rows"""
-        if self._sym_t is None:
-            dev = batch[0].device
-            self._sym_t = {k: (torch.as_tensor(self._sym_table(k)[0].astype("int64"), device=dev), torch.as_tensor(self._sym_table(k)[1], device=dev)) for k in ("obs", "cobs", "act", "mu", "sig")}
+        tabs = self._sym_tensors(batch[0].device)
         out = []
         for k, x in zip(self._KEYS, batch[:9]):
-            tab = self._sym_t.get(k)
+            tab = tabs.get(k)
             mirror = x if tab is None else x[:, tab[0]] if k == "sig" else x[:, tab[0]] * tab[1]
             out.append(torch.cat([x, mirror]))
         return tuple(out) + tuple(batch[9:])
@@ -229,6 +253,41 @@ class PPO(_RolloutHeads):
         self._sym_dev = tabs          # (kept alive: the captured launch reads them)
         self._mirror_jobs = _nn.mirror_jobs([(self._perm[k], self._aug[k], tabs.get(k)) for k in self._KEYS])
         return lambda: _nn.mirror_rows(lib, self._mirror_jobs, nmb, mb, self._stream(self._acc))
+
+    # ---- mirror loss -------------------------------------------------------------------------------------------
+    # Augmentation shows the network both images; this term (`mirror_loss_coef` > 0, needs `symmetry`) penalises the gap between its two answers.  Rows r and B + r of an
+    # augmented mini-batch are o and M_o o, so with the action table (perm, sign)
+    #     e[r, j] = mu[r, j] - sign[j] mu[B + r, perm[j]],        L_mirror = coef mean(e^2)
+    # costs no forward pass, and L_mirror / coef is what scripts/evaluate.py --asymmetry reports as equivariance_rmse^2, on the update's rows.  Both rows receive gradient:
+    # upstream rsl_rl detaches the mirrored side.  Eager mode: the torch expression below, the numerical yardstick.  Graph mode on the heads path:
+    # go2nn_mirror_loss (csrc/go2nn_mirror_loss.h), one launch behind go2nn_ppo_heads.  KL, the learning rate, clipping, Adam and the rank average do not know about it.
+    def _mirror_error(self, mu_b):
+        B = mu_b.shape[0] // 2
+        perm, sign = self._sym_tensors(mu_b.device)["act"]
+        return mu_b[:B] - mu_b[B:][:, perm] * sign
+
+    def _mirror_term(self, mu_b):
+        """-> the weighted term of the loss (under autograd); self._ml = L_mirror / coef of this mini-batch"""
+        ms = self._mirror_error(mu_b).square().mean()
+        self._ml = ms.detach()
+        return self.mirror_loss_coef * ms
+
+    def _mirror_grad(self, mu_b):
+        """-> d L_mirror / d mu [2 B, A] as a torch expression, for the branch that seeds autograd with the loss kernel's gradients; self._ml as _mirror_term"""
+        with torch.no_grad():
+            B, A = mu_b.shape[0] // 2, mu_b.shape[1]
+            perm, sign = self._sym_tensors(mu_b.device)["act"]
+            e = self._mirror_error(mu_b)
+            self._ml = e.square().mean()
+            g = (2.0 * self.mirror_loss_coef / (B * A)) * e
+            return torch.cat([g, -(g * sign)[:, perm]])          # (row B + r, column perm[j]: -sign[j] g[r, j])
+
+    def _mirror_kernel_args(self):
+        """-> (coef, perm int16 tensor, sign tensor) of go2nn_mirror_loss: the action table checked (an involution, sign[perm[j]] == sign[j]) and uploaded once"""
+        if self._ml_dev is None:
+            from ... import _nn
+            self._ml_dev = _nn.mirror_loss_table_tensors(self._nn_library(), self._sym_table("act"), self.device)
+        return (self.mirror_loss_coef,) + tuple(self._ml_dev)
 
     # ---- graph mode -------------------------------------------------------------------------------------------
     _KEYS = ("obs", "cobs", "act", "val", "adv", "ret", "logp", "mu", "sig")
@@ -255,8 +314,9 @@ class PPO(_RolloutHeads):
             # grouped hidden layers, go2nn_ppo_heads (heads forward + loss + heads backward in one pass), ONE go2nn_sum_rows; .grad of every parameter is set
             from ..modules import fused
             self.optimizer.zero_grad(set_to_none=True)
+            mirror = self._mirror_kernel_args() if self.mirror_loss_coef > 0.0 else None          # (go2nn_mirror_loss behind go2nn_ppo_heads; its weighted loss is added to acc[2])
             stats = fused.ppo_pair_grads(ac, batch[0], batch[1], batch[2], batch[3], batch[4], batch[5], batch[6], batch[7], batch[8], self.clip_param, self.value_loss_coef,
-                                         self.entropy_coef, self.use_clipped_value_loss, acc=self._acc)          # (the running loss sums: added by the pass's go2nn_sum_rows launch)
+                                         self.entropy_coef, self.use_clipped_value_loss, acc=self._acc, mirror=mirror)          # (the running loss sums: added by the pass's go2nn_sum_rows launch)
             kl_mean = stats[2]
         elif self.fused_loss:
             # the loss kernel already holds d loss / d (mu, std, value): seed the backward pass of the two networks with them directly
@@ -264,7 +324,11 @@ class PPO(_RolloutHeads):
             mu_b, val_b = ac.actor(batch[0]), self._value(batch[1])
             stats, gmu, gstd, gval = _FusedPPOLoss.kernel(self, mu_b, ac.std, val_b, *batch[2:])
             self.optimizer.zero_grad(set_to_none=True)
-            self._acc.add_(stats[:2])             # [surrogate, value loss]; read back swapped in _update_graphs (issued before the backward pass: off its tail)
+            if self.mirror_loss_coef > 0.0:       # the mirror term's gradient joins the kernel's; acc = [surrogate, value loss, L_mirror]
+                gmu = gmu + self._mirror_grad(mu_b)
+                self._acc.add_(torch.cat([stats[:2], self.mirror_loss_coef * self._ml.reshape(1)]))
+            else:
+                self._acc.add_(stats[:2])         # [surrogate, value loss]; read back swapped in _update_graphs (issued before the backward pass: off its tail)
             # std a leaf: the kernel's gradient IS its .grad (autograd would copy it there with one more launch).  The recurrent update has always left that copy to
             # autograd; its captured graph keeps that launch.
             if ac.std.requires_grad and ac.std.grad_fn is None and not self._rnn:
@@ -277,7 +341,7 @@ class PPO(_RolloutHeads):
             loss, value_loss, surrogate_loss, kl_mean = self._losses(*batch)
             self.optimizer.zero_grad(set_to_none=True)
             loss.backward()
-            self._acc.add_(torch.stack([surrogate_loss.detach(), value_loss.detach()]))
+            self._acc.add_(torch.stack([surrogate_loss.detach(), value_loss.detach()] + ([self.mirror_loss_coef * self._ml] if self.mirror_loss_coef > 0.0 else [])))
         if split:
             if self._bucket is None:
                 self._bucket = GradBucket(self._params, 1 if self._adaptive() else 0)
@@ -310,9 +374,9 @@ class PPO(_RolloutHeads):
                           "mu": flat(st.mu), "sig": flat(st.sigma)}
             self._mb = mb
             self._perm = {k: torch.empty((nmb * mb,) + tuple(v.shape[1:]), device=self.device, dtype=v.dtype) for k, v in self._flat.items()}
-            self._acc = torch.zeros(2, device=self.device)
+            self._acc = torch.zeros(3 if self.mirror_loss_coef > 0.0 else 2, device=self.device)          # [surrogate, value loss(, the weighted mirror loss)]
             self._bucket = None
-            mirror = self._sym_setup(nmb, mb) if self._sym is not None else None
+            mirror =self._sym_setup(nmb, mb) if self._sym is not None else None
             if _collectives_on():
                 self._graph = self._reduced_steps(self._graph_front, self._graph_back, (lambda: self._bucket), "PPO mini-batch")
             else:
@@ -352,7 +416,9 @@ class PPO(_RolloutHeads):
         for _ in range(self._graph_reps):
             for g in self._graph:
                 g()
-        surrogate, value = self._read_back(self._acc, self.num_learning_epochs * nmb)
+        surrogate, value, *rest = self._read_back(self._acc, self.num_learning_epochs * nmb)
+        if rest:
+            self.mirror_loss = rest[0] / self.mirror_loss_coef
         return value, surrogate
 
     def graphs_captured(self):

@@ -342,8 +342,11 @@ class OnPolicyRunner:
         w = self.writer
         for (name, tag, _), v in zip(self._LOSS_NAMES, locs["losses"]):
             w.add_scalar(tag, v, locs["it"])
+        mirror = self.alg.mirror_loss if getattr(self.alg, "mirror_loss_coef", 0.0) > 0.0 else None          # (the mirror loss: L_mirror / coef = equivariance_rmse^2 of the update's rows)
+        if mirror is not None:
+            w.add_scalar("Loss/mirror", mirror, locs["it"])
         w.add_scalar("Loss/learning_rate", self.alg.learning_rate, locs["it"])
-        if hasattr(ac, "std"):         # not for the MCP actor, whose std is an output of the network (on_policy_runner_cts.py:239-240)
+        if hasattr(ac, "std"):        # not for the MCP actor, whose std is an output of the network (on_policy_runner_cts.py:239-240)
             w.add_scalar("Policy/mean_noise_std", mean_std.item(), locs["it"])
         w.add_scalar("Perf/total_fps", fps, locs["it"])
         w.add_scalar("Perf/collection time", locs["collection_time"], locs["it"])
@@ -360,6 +363,8 @@ class OnPolicyRunner:
              )
         for (_, _, label), v in zip(self._LOSS_NAMES, locs["losses"]):
             s += f"""{label:>{pad}} {v:.4f}\n"""
+        if mirror is not None:
+            s += f"""{'Mirror loss:':>{pad}} {mirror:.6f}\n"""
         s += f"""{'Mean action noise std:':>{pad}} {mean_std.item():.2f}\n"""
         for _, label, rb, lb in groups:
             s += (f"""{'Mean %sreward:' % label:>{pad}} {statistics.mean(rb):.2f}\n"""

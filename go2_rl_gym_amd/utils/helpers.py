@@ -114,6 +114,9 @@ def update_cfg_from_args(env_cfg, cfg_train, args):
                 setattr(gauge, field, given)
     if getattr(args, "symmetry", False):
         cfg_train.algorithm.symmetry = True          # (a CTS task's algorithm then refuses at construction: feed-forward PPO only)
+    if getattr(args, "mirror_loss", None) is not None:          # the mirror loss is a term on the augmented mini-batches: the flag switches augmentation on too
+        cfg_train.algorithm.mirror_loss_coef = args.mirror_loss
+        cfg_train.algorithm.symmetry = True
     ev = getattr(cfg_train, "evaluation", None)
     if ev is not None:
         if getattr(args, "evaluate", False):
@@ -183,6 +186,8 @@ def get_args(argv=None):
                    "resamplings: evaluation.bootstrap = B")
     p.add_argument("--symmetry", action="store_true", default=False, help="train every PPO mini-batch on its left-right mirror image too (feed-forward PPO only): "
                    "algorithm.symmetry = True")
+    p.add_argument("--mirror_loss", type=float, default=None, metavar="COEF", help="add COEF x the mean squared gap between the policy's answer to an observation and the "
+                   "mirrored answer to its mirror image to the PPO loss (feed-forward PPO only; switches --symmetry on): algorithm.mirror_loss_coef = COEF")
     p.add_argument("--record_steps", type=int, default=500, help="play.py --record: the last S steps of the rollout are kept")
     # flags contributed by isaacgym.gymutil.parse_arguments in the reference
     p.add_argument("--sim_device", type=str, default="cuda:0")

@@ -750,6 +750,34 @@ typedef struct Go2nnMirrorJob {
 int go2nn_mirror_check_table(const int16_t* host_perm, const float* host_sign, int32_t width);
 int go2nn_mirror_rows(const Go2nnMirrorJob* jobs, int32_t n_jobs, int32_t chunks, int32_t chunk_rows, void* stream);
 
+/* ---- the mirror (equivariance) loss of symmetry-augmented PPO (go2_rl_gym_amd/rsl_rl/algorithms/ppo.py, `algorithm.mirror_loss_coef`; csrc/go2nn_mirror_loss.h).
+ * ADDED WITHIN ABI 7: four new entry points and one struct, nothing existing changes, GO2NN_ABI_VERSION stays 7.
+ * An augmented mini-batch is [B originals | B mirror images]; with the involutive (perm, sign) table of the action vector, for pair r:
+ *   e[r, j] = mu[r, j] - sign[j] mu[B + r, perm[j]]           mu = y_a W_mu^T + b_mu (the fp32 dot products of go2nn_ppo_heads)
+ *   L = coef / (B A) sum_r sum_j e[r, j]^2                    (L / coef is the batch's equivariance_rmse^2)
+ *   g[r, j] = 2 coef / (B A) e[r, j],   g[B + r, perm[j]] = -sign[j] g[r, j]          (both halves receive gradient)
+ * Two plain launches (capturable) behind go2nn_ppo_heads on the same stream — the pass, then one block that adds the workgroups' fp64 sums of e^2 and leaves L,
+ * rounded once, in the first partial row —: (g W_mu) * ELU'(y_a) (ELU' from the output: y > 0 ? 1 : y + 1) is ADDED to gz_a, and
+ * `partials` receives go2nn_mirror_loss_rows(B, A, K) rows of go2nn_mirror_loss_cols(A, K) columns whose column sums (go2nn_sum_rows) are
+ *   [ L, 0, 0, 0 | dW_mu [A, K] | gb_a [K] = the column sums of what was added to gz_a | db_mu [A] ]
+ * Fixed summation order, no atomics: two launches give the same bits.  perm == sign == NULL: the identity table.  perm (int16 [A]) and sign (fp32 [A]) live in the
+ * buffers' memory space; the launch cannot read them back, so go2nn_mirror_loss_check_table checks them in HOST memory before the upload: GO2NN_EINVAL for a null
+ * pointer, A outside [1, 16], perm[j] outside [0, A), a sign that is neither +1 nor -1, perm[perm[j]] != j, sign[perm[j]] != sign[j].
+ * go2nn_mirror_loss: GO2NN_EINVAL, with nothing written, for a null struct or pointer (y_a, w_mu, b_mu, gz_a, partials; perm without sign or sign without perm),
+ * B < 1, A outside [1, 16], K not a multiple of 4 in [4, 256]; the host build also for a table go2nn_mirror_loss_check_table refuses. */
+typedef struct Go2nnMirrorLoss {
+  const float* y_a;            /* [2B, K] last hidden activations of the actor: row r and row B + r are a pair */
+  const float *w_mu, *b_mu;    /* head [A, K], [A] */
+  const int16_t* perm; const float* sign;   /* [A] */
+  float* gz_a;                 /* [2B, K]: ADDED to (go2nn_ppo_heads has written it on the same stream) */
+  float* partials;             /* go2nn_mirror_loss_rows x go2nn_mirror_loss_cols */
+  int32_t B, A, K; float coef;
+} Go2nnMirrorLoss;
+int32_t go2nn_mirror_loss_rows(int32_t B, int32_t A, int32_t K);
+int32_t go2nn_mirror_loss_cols(int32_t A, int32_t K);
+int go2nn_mirror_loss_check_table(const int16_t* host_perm, const float* host_sign, int32_t A);
+int go2nn_mirror_loss(const Go2nnMirrorLoss* a, void* stream);
+
 /* ---- the evaluator's left-right asymmetry scores: how far is the policy from equivariant on the states it visits, and does the robot load its left and right legs
  * equally (go2_rl_gym_amd/utils/evaluator.py, `evaluation.asymmetry`; the tables: go2_rl_gym_amd/utils/symmetry.py; csrc/go2nn_asym.h).
  * ADDED WITHIN ABI 7: three new entry points, nothing existing changes, GO2NN_ABI_VERSION stays 7.
