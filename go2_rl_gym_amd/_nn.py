@@ -262,6 +262,41 @@ def mirror_rows(lib, jobs, chunks, chunk_rows, stream=None):
         raise RuntimeError("go2nn_mirror_rows failed: %s" % lib.go2nn_last_error().decode())
 
 
+class Go2nnObsNormJob(C.Structure):          # (within ABI 7) y may be x; partials None: normalise only
+    _fields_ = [("x", C.c_void_p), ("y", C.c_void_p), ("mean", C.c_void_p), ("inv", C.c_void_p), ("partials", C.c_void_p), ("D", C.c_int32), ("clip", C.c_float)]
+
+
+GO2NN_OBS_NORM_MAX_JOBS = 4
+
+
+def obs_norm_jobs(items):
+    """items: (x [N, D], y [N, D] (may be x), mean32 [D], inv32 [D], partials fp64 [partial_rows(N), D, 2] or None, clip) -> the ctypes job array of go2nn_obs_norm_apply"""
+    jobs = []
+    for x, y, mean, inv, partials, clip in items:
+        D = int(x.shape[-1])
+        for t in (x, y, mean, inv):
+            assert t.is_contiguous() and t.dtype == torch.float32 and t.device == x.device, "contiguous fp32 tensors on one device"
+        assert x.dim() == 2 and y.shape == x.shape and mean.numel() == inv.numel() == D, "x and y [N, D], mean and inv [D]"
+        if partials is not None:
+            assert partials.is_contiguous() and partials.dtype == torch.float64 and partials.device == x.device and partials.numel() == -(-x.shape[0] // 64) * D * 2, \
+                "partials: fp64 [partial_rows(N), D, 2]"
+        jobs.append(Go2nnObsNormJob(x.data_ptr(), y.data_ptr(), mean.data_ptr(), inv.data_ptr(), partials.data_ptr() if partials is not None else None, D, float(clip)))
+    return (Go2nnObsNormJob * len(jobs))(*jobs)
+
+
+def obs_norm_apply(lib, jobs, N, stream=None):
+    if lib.go2nn_obs_norm_apply(jobs, len(jobs), int(N), stream) != 0:
+        raise RuntimeError("go2nn_obs_norm_apply failed: %s" % lib.go2nn_last_error().decode())
+
+
+def obs_norm_update(lib, table, state, n, eps, mean32, inv32, stream=None):
+    """table fp64 [steps, rows, D, 2], state fp64 [1 + 2 D]: the iteration's moments merged into the state, mean32 / inv32 rewritten (go2nn_obs_norm_update)"""
+    steps, rows, D = (int(v) for v in table.shape[:3])
+    assert table.is_contiguous() and table.dtype == state.dtype == torch.float64 and state.numel() == 1 + 2 * D and mean32.numel() == inv32.numel() == D
+    if lib.go2nn_obs_norm_update(table.data_ptr(), steps, rows, D, state.data_ptr(), float(n), float(eps), mean32.data_ptr(), inv32.data_ptr(), stream) != 0:
+        raise RuntimeError("go2nn_obs_norm_update failed: %s" % lib.go2nn_last_error().decode())
+
+
 def trace_env_ids(env_ids, num_envs):
     """the tracked robots of go2nn_trace_record as the kernel needs them -> int32 numpy [K], strictly increasing, each in [0, num_envs).  The kernel cannot report a bad
     index (it would read outside the buffers), so anything else raises here."""
@@ -367,6 +402,9 @@ def bind(path):
     lib.go2nn_mirror_loss_cols.argtypes = [C.c_int32] * 2
     lib.go2nn_mirror_loss_check_table.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
     lib.go2nn_mirror_loss.argtypes = [C.POINTER(Go2nnMirrorLoss), C.c_void_p]
+    lib.go2nn_obs_norm_partial_rows.argtypes = [C.c_int32]          # (within ABI 7) empirical observation normalisation
+    lib.go2nn_obs_norm_apply.argtypes = [C.POINTER(Go2nnObsNormJob), C.c_int32, C.c_int32, C.c_void_p]
+    lib.go2nn_obs_norm_update.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]
     if lib.go2nn_abi_version() != GO2NN_ABI_VERSION:
         raise RuntimeError("%s: ABI version %d, expected %d" % (path, lib.go2nn_abi_version(), GO2NN_ABI_VERSION))
     return lib

@@ -1262,3 +1262,4 @@ int go2nn_moe_mix_forward(const float* logits, const float* outs, const float* b
 #include "go2nn_asym.h"         // (within ABI 7) the evaluator's left-right asymmetry scores: equivariance error of the policy, left / right load of the robot
 #include "go2nn_bootstrap.h"    // (within ABI 7) the evaluator's confidence intervals: bootstrap replicates of the reduce table, robots redrawn within their cells
 #include "go2nn_mirror_loss.h"  // (within ABI 7) the mirror (equivariance) loss of symmetry-augmented PPO: one pass over the actor's last hidden activations
+#include "go2nn_obs_norm.h"     // (within ABI 7) empirical observation normalisation of feed-forward PPO: one apply launch per policy step, one merge per iteration

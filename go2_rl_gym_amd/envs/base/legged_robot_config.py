@@ -267,6 +267,10 @@ class LeggedRobotCfgPPO(BaseConfig):
         load_run = -1
         checkpoint = -1
         resume_path = None
+        empirical_normalization = False          # running mean / std normalisation of both observation streams (upstream's switch; --normalize_obs; rsl_rl/modules/normalizer.py); feed-forward PPO only
+        empirical_normalization_eps = 1e-2       # y = (x - mean) / (std + eps)
+        empirical_normalization_clip = 10.0      # y clamped to [-clip, clip]; <= 0: no clamp (upstream has none)
+        empirical_normalization_until = None     # no batch is merged once this many samples have been seen; None: never stops
 
     class robogauge:
         enabled = False
@@ -358,6 +362,10 @@ class LeggedRobotCfgCTS(BaseConfig):
         load_run = -1
         checkpoint = -1
         resume_path = None
+        empirical_normalization = False          # (--normalize_obs) feed-forward PPO only: the CTS runner refuses it
+        empirical_normalization_eps = 1e-2
+        empirical_normalization_clip = 10.0
+        empirical_normalization_until = None
 
     class robogauge:
         enabled = False

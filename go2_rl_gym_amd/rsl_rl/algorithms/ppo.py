@@ -14,6 +14,11 @@ every rank takes the same branch; advantage statistics are all-reduc
 Symmetry augmentation (`symmetry=`, off by default; feed-forward policies only): every mini-batch is followed by its left-right mirror image — torch indexing in
 eager mode, ONE go2nn_mirror_rows launch per update inside the captured permutation step in graph mode (the `symmetry augmentation` section below; utils/symmetry.py).
 
+Empirical observation normalisation (children `obs_normalizer` / `critic_obs_normalizer` of the actor-critic, attached by the runner for
+`runner.empirical_normalization`; feed-forward policies only): act() normalises storage row s in place — ONE go2nn_obs_norm_apply launch per policy step for both
+streams, inside the replayed rollout —, so the update reads normalised rows and does not change; the statistics move once per iteration, at the end of update()
+(the `observation normalisation` section below; modules/normalizer.py).
+
 The env's observation buffers are persistent device buffers that the step kernel overwrites IN PLACE (the reference
 rebinds `obs_buf` to fresh tensors every step), so `act()` copies the observations into the rollout storage immediately
 instead of keeping a reference until `process_env_step`.
@@ -70,6 +75,10 @@ class PPO(_RolloutHeads):
         if mirror_loss_coef > 0.0 and self._sym is None:
             raise ValueError("PPO(mirror_loss_coef > 0) is a term on the mirror-augmented mini-batches: it needs symmetry=mirror_tables(env_cfg) (algorithm.symmetry = True; "
                              "--mirror_loss sets both)")
+        # empirical observation normalisation: present iff the actor-critic has the children (the runner attaches them; a checkpoint that carries them too).  Absent:
+        # nothing is loaded, allocated or launched.
+        self._on_state, self._on_merged = None, False
+        self._obs_norm()
         self._sync_replicas(self.actor_critic)
 
     def rebind_lr(self):
@@ -113,6 +122,9 @@ class PPO(_RolloutHeads):
         st, ac = self.storage, self.actor_critic
         s = self._begin_step()
         self._store_obs_rows(obs, critic_obs, s)
+        on = self._obs_norm()
+        if on is not None:          # storage row s becomes the normalised row, whoever wrote it (the env's step kernel, the sensor kernel, the copy above)
+            obs, critic_obs = self._obs_norm_rows(on, s)
         x_a, x_c = self._rnn_step(obs, critic_obs, s) if self._rnn else (obs, critic_obs)
         if not self.fused_rollout:
             return self._transition_to_rows(ac, self._sample(x_a), self._value(x_c), s)
@@ -156,6 +168,9 @@ class PPO(_RolloutHeads):
         else:
             # (a recurrent policy: the critic memory's extra step, as the reference's evaluate() — its state carries on)
             x_c = rm.step([last_critic_obs.contiguous()], which=(1,))[0] if self._rnn else last_critic_obs
+            on = self._obs_norm()
+            if on is not None:          # (this observation has no storage row: normalised into a scratch buffer, the env's buffer keeps the raw frame)
+                x_c = self._obs_norm_last(on, x_c)
             pk = self._kernel()
             if pk is not None and self._pk_packed and x_c.is_contiguous() and x_c.dtype == torch.float32:
                 last_values = pk.critic.forward(x_c)          # the bootstrap value as ONE launch on the weights packed for this rollout (they have not changed since)
@@ -234,12 +249,15 @@ class PPO(_RolloutHeads):
             out.append(torch.cat([x, mirror]))
         return tuple(out) + tuple(batch[9:])
 
-    def _nn_library(self):
-        """the policy-side library (go2nn_mirror_rows): the one the tests handed in, else the device library — missing is an error, there is no torch fallback in graph mode"""
+    def _nn_library(self, required="symmetry augmentation in graph mode runs go2nn_mirror_rows"):
+        """the policy-side library: the one the tests handed in, else the device library on a GPU — missing there is an error, there is no quiet torch fallback.  On the
+        CPU with none handed in: raises with `required` as the reason, or -> None when `required` is None (the caller has a torch formulation)"""
         if self.nn_lib is not None:
             return self.nn_lib
         if not str(self.device).startswith("cuda"):
-            raise RuntimeError("symmetry augmentation in graph mode runs go2nn_mirror_rows: on the CPU hand in the host build (nn_lib), or use the eager mode")
+            if required is None:
+                return None
+            raise RuntimeError("%s: on the CPU hand in the host build (nn_lib), or use the eager mode" % required)
         from ... import _nn
         return _nn.load_nn()
 
@@ -416,6 +434,7 @@ class PPO(_RolloutHeads):
         for _ in range(self._graph_reps):
             for g in self._graph:
                 g()
+        self._obs_norm_finish()          # (enqueued behind the last optimizer step and in front of the read-back's host synchronisation: no idle gap in front of it)
         surrogate, value, *rest = self._read_back(self._acc, self.num_learning_epochs * nmb)
         if rest:
             self.mirror_loss = rest[0] / self.mirror_loss_coef
@@ -431,14 +450,121 @@ class PPO(_RolloutHeads):
 
     def update(self):
         self.parameters_changed()          # the optimizer steps below change the parameters: the next rollout re-packs
+        self._on_merged = False
         if self._rnn and self.use_graphs and self._rnn_memory() is not None:
             out = self._rnn_update_graphs()
         elif self.use_graphs and not self._rnn:
             out = self._update_graphs()
         else:
             out = self._update_eager()
+        self._obs_norm_finish()
         self.storage.clear()
         return out
+
+    # ---- observation normalisation -----------------------------------------------------------------------------
+    # Statistics k serve the rollout AND the update of iteration k — upstream updates them before every forward —, so old_log_prob, mu, sigma and
+    # values in the storage are what the update's forward computes from the stored rows, no host state enters the captured graphs, and a run is deterministic.  The
+    # storage holds NORMALISED rows; the raw moments of the rollout (sums of x - mean32 and of its square, fp64, one table row per step and 64 storage rows) are merged
+    # into the state by one go2nn_obs_norm_update launch per stream at the end of update(), a plain launch behind the captured update.  With fused_rollout off, or no
+    # library, modules/normalizer.py does the same job in torch (forward / merge on a kept copy of the raw rows): the numerical yardstick.
+    def _obs_norm(self):
+        """-> (actor stream's normaliser, critic stream's or None: one normaliser for the shared rows), or None (off)"""
+        ac = self.actor_critic
+        na = getattr(ac, "obs_normalizer", None)
+        if na is None:
+            return None
+        nc = getattr(ac, "critic_obs_normalizer", None)
+        if self._on_state is None or self._on_state["norms"] != (id(na), id(nc)):
+            if self._sym is not None or self.mirror_loss_coef > 0.0:
+                raise NotImplementedError("empirical observation normalisation with symmetry augmentation or the mirror loss is not implemented (the mirror image of a "
+                                          "normalised row is the normalised mirror image only under symmetrised statistics)")
+            if self._rnn:
+                raise NotImplementedError("empirical observation normalisation with a recurrent policy is not implemented (the hidden state that crosses an iteration "
+                                          "boundary was computed under the old statistics)")
+            if _world() > 1 or _collectives_on():
+                raise NotImplementedError("empirical observation normalisation trains on one rank only (the moments would need an fp64 all-reduce)")
+            self._on_state = {"norms": (id(na), id(nc))}
+        return na, nc
+
+    def normalizers_changed(self):
+        """the normalisers' eps / clip may have changed (a checkpoint was loaded): the job arrays, which hold the clip by value, are rebuilt at the next step — the caller
+        drops the captured rollout with them (the runner does)"""
+        if self._on_state is not None:
+            self._on_state.pop("storage", None)
+
+    def _obs_norm_setup(self, on):
+        """The streams [(normaliser, storage tensor [T, N, D])], and per formulation: the partial tables and the job array of every step (the pointers are fixed: the
+        captured rollout bakes one launch per step, the step's table row chosen here on the host), or the raw copies the torch merge reads."""
+        st, os_ = self.storage, self._on_state
+        if os_.get("storage") is st:
+            return os_
+        na, nc = on
+        if (nc is None) != (st.privileged_observations is None):
+            raise ValueError("observation normalisation: the actor-critic has %s normaliser for the privileged observation, the rollout storage %s such rows"
+                             % (("no", "has") if nc is None else ("a", "no")))
+        streams = [(na, st.observations)] + ([(nc, st.privileged_observations)] if nc is not None else [])
+        for n, x in streams:
+            if n.num_features != x.shape[-1] or x.dtype != torch.float32 or not x.is_contiguous():
+                raise ValueError("observation normalisation: a normaliser of %d columns for contiguous fp32 rows of %d" % (n.num_features, x.shape[-1]))
+        T, N = st.num_transitions_per_env, st.num_envs
+        lib = self._nn_library(required=None) if self.fused_rollout else None          # (None: the torch formulation)
+        os_.update(storage=st, streams=streams, lib=lib)
+        if lib is not None:
+            from ... import _nn
+            rows = int(lib.go2nn_obs_norm_partial_rows(N))
+            os_["tables"] = [torch.zeros(T, rows, n.num_features, 2, dtype=torch.float64, device=x.device) for n, x in streams]
+            os_["jobs"] = [_nn.obs_norm_jobs([(x[s], x[s], n.mean32, n.inv32, tab[s], n.clip) for (n, x), tab in zip(streams, os_["tables"])]) for s in range(T)]
+        else:
+            os_["raw"] = [torch.empty_like(x) for _, x in streams]
+        return os_
+
+    def _obs_norm_rows(self, on, s):
+        """storage row s of both streams, raw -> normalised in place.  -> (actor rows, critic rows) of step s"""
+        os_ = self._obs_norm_setup(on)
+        if os_["lib"] is not None:
+            from ... import _nn
+            _nn.obs_norm_apply(os_["lib"], os_["jobs"][s], self.storage.num_envs, self._stream(os_["streams"][0][1]))
+        else:
+            for (n, x), raw in zip(os_["streams"], os_["raw"]):
+                raw[s].copy_(x[s])
+                x[s].copy_(n(raw[s]))
+        rows = [x[s] for _, x in os_["streams"]]
+        return rows[0], rows[-1]
+
+    def _obs_norm_last(self, on, x):
+        """the bootstrap value's observation (raw, no storage row) -> normalised, in a scratch buffer"""
+        os_ = self._obs_norm_setup(on)
+        n = os_["streams"][-1][0]
+        if os_["lib"] is None or not (x.is_contiguous() and x.dtype == torch.float32):
+            return n(x)
+        from ... import _nn
+        if os_.get("last") is None or os_["last"].shape != x.shape or os_["last"].device != x.device:
+            os_["last"] = torch.empty_like(x)
+        os_["last_jobs"] = _nn.obs_norm_jobs([(x, os_["last"], n.mean32, n.inv32, None, n.clip)])
+        _nn.obs_norm_apply(os_["lib"], os_["last_jobs"], x.shape[0], self._stream(x))
+        return os_["last"]
+
+    def _obs_norm_finish(self):
+        """once per update(), after its last optimizer step: the rollout and the update of this iteration both ran on the statistics the iteration began with"""
+        on = self._obs_norm()
+        if on is not None and not self._on_merged:
+            self._on_merged = True
+            self._obs_norm_merge(on)
+
+    def _obs_norm_merge(self, on):
+        """the rollout's raw moments into the statistics (the `until` cap is the host's decision: count grows by N T per iteration, no device read)"""
+        os_ = self._obs_norm_setup(on)
+        st = self.storage
+        samples = st.num_envs * st.num_transitions_per_env
+        for i, (n, x) in enumerate(os_["streams"]):
+            if not n.accepts():
+                continue
+            if os_["lib"] is not None:
+                from ... import _nn
+                _nn.obs_norm_update(os_["lib"], os_["tables"][i], n.state, samples, n.eps, n.mean32, n.inv32, self._stream(x))
+                n.note_merged(samples)
+            else:
+                n.merge(os_["raw"][i].flatten(0, 1))
 
     # ------------------------------------------------------------------ recurrent policies (the reference's is_recurrent branches)
     # Rollout: the memories' step (the state before it into storage slot s), then the heads as for a feed-forward policy (go2nn_policy_act on the memories' h);

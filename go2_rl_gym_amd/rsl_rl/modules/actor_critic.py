@@ -79,7 +79,9 @@ class ActorCritic(nn.Module):
         return self.distribution.log_prob(actions).sum(dim=-1)
 
     def act_inference(self, observations):
-        return self.actor(observations)
+        # empirical normalisation (modules/normalizer.py): the child exists only when the run, or the checkpoint loaded, has it; raw observations in
+        norm = getattr(self, "obs_normalizer", None)
+        return self.actor(observations if norm is None else norm(observations))
 
     def evaluate(self, critic_observations, **kwargs):
         return self.critic(critic_observations)

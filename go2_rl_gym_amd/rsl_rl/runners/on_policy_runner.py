@@ -155,11 +155,25 @@ class OnPolicyRunner:
     def _build_algorithm(self, train_cfg, use_graphs):
         num_critic_obs = self.env.num_privileged_obs if self.env.num_privileged_obs is not None else self.env.num_obs
         actor_critic = _POLICIES[self.cfg["policy_class_name"]](self.env.num_obs, num_critic_obs, self.env.num_actions, **self.policy_cfg).to(self.device)
+        if self.cfg.get("empirical_normalization", False):          # before the algorithm is built: it refuses what normalisation does not go with, and its optimizer
+            self._attach_normalizers(actor_critic)                  # never sees the statistics (buffers, not parameters)
         alg_cfg = dict(self.alg_cfg)
         if alg_cfg.get("symmetry"):          # algorithm.symmetry = True: the task's mirror tables, from the env's own config (any layout but the Go2 tasks' raises)
             from ...utils.symmetry import mirror_tables
             alg_cfg["symmetry"] = mirror_tables(self.env.cfg)
         self.alg = _ALGS[self.cfg["algorithm_class_name"]](actor_critic, device=self.device, lib=self.lib, use_graphs=use_graphs, **alg_cfg)
+
+    def _attach_normalizers(self, actor_critic, shared=None):
+        """runner.empirical_normalization: the children obs_normalizer / critic_obs_normalizer of the actor-critic (rsl_rl/modules/normalizer.py); a task without a
+        privileged observation has one normaliser for the shared rows"""
+        from ..modules.normalizer import attach_normalizers
+        if getattr(actor_critic, "is_recurrent", False):
+            raise NotImplementedError("empirical observation normalisation with a recurrent policy is not implemented (the hidden state that crosses an iteration boundary "
+                                      "was computed under the old statistics)")
+        c = self.cfg
+        shared = self.env.num_privileged_obs is None if shared is None else shared
+        attach_normalizers(actor_critic, self.env.num_obs, self.env.num_obs if shared else self.env.num_privileged_obs, eps=c.get("empirical_normalization_eps", 1e-2),
+                           clip=c.get("empirical_normalization_clip", 10.0), until=c.get("empirical_normalization_until"), shared=shared)
 
     def _begin_learn(self):
         pass
@@ -413,7 +427,7 @@ class OnPolicyRunner:
 
     def load(self, path, load_optimizer=True):
         d = torch.load(path, map_location=self.device)
-        self.alg.actor_critic.load_state_dict(d["model_state_dict"])
+        self._load_model(d["model_state_dict"])
         self.alg.parameters_changed()          # (what the rollout's kernels hold packed is stale now)
         if load_optimizer:
             load_optimizer_state(self.alg.optimizer, d["optimizer_state_dict"])
@@ -421,6 +435,36 @@ class OnPolicyRunner:
         self.current_learning_iteration = d["iter"]
         getattr(self.alg, "set_shuffle_counter", lambda it: None)(d["iter"])          # graph mode's keyed permutation continues at the checkpoint's iteration
         return d["infos"]
+
+    def _load_model(self, sd):
+        """model_state_dict into the actor-critic.  A checkpoint that carries observation statistics brings them along whatever this run's switch says (the children are
+        attached first: it carries what it needs to run); one without them, loaded while the switch is on, starts from the initial statistics; else as ever."""
+        from ..modules.normalizer import normalizer_widths
+        ac = self.alg.actor_critic
+        has, w = getattr(ac, "obs_normalizer", None) is not None, normalizer_widths(sd)
+        if w is not None and not has:
+            self._attach_normalizers(ac, shared=w[1] is None)
+            self._rollout_graph, self._returns_graph, self._eager_rollouts = None, None, 0          # (a captured rollout has no normalisation launches)
+        if w is None and has:
+            print("[go2_rl_gym_amd] the checkpoint carries no observation statistics: empirical normalisation starts from its initial state (count 0, mean 0, var 1)")
+            res = ac.load_state_dict(sd, strict=False)
+            bad = [k for k in res.missing_keys if not k.startswith(("obs_normalizer.", "critic_obs_normalizer."))] + list(res.unexpected_keys)
+            if bad:
+                raise RuntimeError("Error(s) in loading state_dict for %s: missing or unexpected keys %s" % (type(ac).__name__, bad))
+            for n in (ac.obs_normalizer, getattr(ac, "critic_obs_normalizer", None)):
+                if n is not None:
+                    n.set_state(0.0, 0.0, 1.0)
+        else:
+            ac.load_state_dict(sd)
+        if getattr(ac, "obs_normalizer", None) is not None:
+            # eps and clip travel in the checkpoint and win over this run's config: say so when they differ.  The job arrays hold the clip by value and a captured
+            # rollout holds the job arrays: both are rebuilt after any load.
+            c, n = self.cfg, ac.obs_normalizer
+            want = (float(c.get("empirical_normalization_eps", 1e-2)), float(c.get("empirical_normalization_clip", 10.0) or 0.0))
+            if self.cfg.get("empirical_normalization", False) and (n.eps, n.clip) != want:
+                print("[go2_rl_gym_amd] the checkpoint's observation normalisation has eps = %g, clip = %g; the config's eps = %g, clip = %g are not used" % (n.eps, n.clip, *want))
+            self.alg.normalizers_changed()
+            self._rollout_graph, self._returns_graph, self._eager_rollouts = None, None, 0
 
     def get_inference_policy(self, device=None):
         self.alg.actor_critic.eval()

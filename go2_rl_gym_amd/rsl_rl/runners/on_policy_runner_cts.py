@@ -30,6 +30,9 @@ class OnPolicyRunnerCTS(OnPolicyRunner):
 
     def _build_algorithm(self, train_cfg, use_graphs):
         env = self.env
+        if self.cfg.get("empirical_normalization", False):
+            raise NotImplementedError("empirical observation normalisation for the CTS family is not implemented (the runner's history ring would carry frames normalised "
+                                      "under the old statistics across an iteration boundary)")
         if env.num_privileged_obs is None:
             raise ValueError("CTS needs privileged observations (on_policy_runner_cts.py:127)")
         if self.lib is None:

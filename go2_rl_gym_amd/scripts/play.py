@@ -40,9 +40,10 @@ def play(args, steps=None, log_root="default", export_policy=None):
         root = os.path.join(ROOT_DIR, "logs", train_cfg.runner.experiment_name) if log_root == "default" else log_root
         path = os.path.join(root, "exported", "policies")
         model = runner.alg.actor_critic
-        exported = [export_policy_as_jit(model, path), export_policy_as_pkl(model, path)]
+        normalizer = getattr(model, "obs_normalizer", None)          # (empirical observation normalisation: the exported module takes raw observations, like act_inference)
+        exported = [export_policy_as_jit(model, path, normalizer=normalizer), export_policy_as_pkl(model, path)]
         try:
-            exported.append(export_policy_as_onnx(model, path))
+            exported.append(export_policy_as_onnx(model, path, normalizer=normalizer))
         except Exception as e:      # the ONNX exporter needs the `onnx` package
             print("ONNX export skipped:", type(e).__name__, e)
         print("Exported policy to: ", path)

@@ -262,15 +262,35 @@ class _MlpPolicy(_Policy):
     def __init__(self, ev, model):
         super().__init__(ev, model)
         self.actor = PackedMlp(ev.nn, model.actor)
+        # empirical observation normalisation (rsl_rl/modules/normalizer.py): a model that has the child gets one go2nn_obs_norm_apply launch (no partial table: the
+        # statistics never change during an evaluation) into a scratch buffer in front of the forward kernel — of the raw observation's mirror image too, and of the
+        # frame the sensor model delivered.  No child: nothing is allocated or launched.
+        self.norm, self._norm_stats, self._norm_out = None, None, {}
 
     def begin(self, obs):
         self.actor.pack()
+        self.norm = getattr(self.model, "obs_normalizer", None)
+        if self.norm is not None:          # the CURRENT statistics, on the evaluator's device
+            self._norm_stats = (self.norm.mean32.detach().to(obs.device, copy=True), self.norm.inv32.detach().to(obs.device, copy=True), float(self.norm.clip))
+
+    def _normalised(self, obs, key):
+        if self.norm is None:
+            return obs
+        from .._nn import obs_norm_apply, obs_norm_jobs
+        mean32, inv32, clip = self._norm_stats
+        obs = obs if (obs.is_contiguous() and obs.dtype == torch.float32) else obs.contiguous().float()
+        out = self._norm_out.get(key)
+        if out is None or out[0].shape != obs.shape:
+            out = self._norm_out[key] = [torch.empty_like(obs), None]
+        out[1] = obs_norm_jobs([(obs, out[0], mean32, inv32, None, clip)])          # (kept alive with the buffer)
+        obs_norm_apply(self.ev.nn, out[1], obs.shape[0], self._stream())
+        return out[0]
 
     def act(self, obs):
-        return self.actor.forward(obs)
+        return self.actor.forward(self._normalised(obs, "obs"))
 
     def act_mirrored(self, obs_m, hist_m=None):
-        return self.actor.forward(obs_m)
+        return self.actor.forward(self._normalised(obs_m, "mirror"))
 
 
 class _CtsPolicy(_Policy):

@@ -857,6 +857,39 @@ int go2nn_asym_reduce(const float* table, const int32_t* group, int32_t N, int32
 int go2nn_eval_bootstrap_check(const int32_t* host_cell_start, const int32_t* host_cell_envs, int32_t N, int32_t G);
 int go2nn_eval_bootstrap(const float* acc, const int32_t* cell_start, const int32_t* cell_envs, int32_t N, int32_t G, int32_t B, uint32_t seed, double* out, void* stream);
 
+/* ---- empirical (running mean / std) normalisation of the observations of feed-forward PPO (go2_rl_gym_amd/rsl_rl/modules/normalizer.py, rsl_rl/algorithms/ppo.py,
+ * `runner.empirical_normalization`; csrc/go2nn_obs_norm.h).
+ * ADDED WITHIN ABI 7: three new entry points and one struct, nothing existing changes, GO2NN_ABI_VERSION stays 7.
+ * go2nn_obs_norm_apply: one plain launch (capturable) per policy step for up to GO2NN_OBS_NORM_MAX_JOBS row-major fp32 [N, D] tensors; the job index sits in the grid.
+ *   y[r, c] = (x[r, c] - mean[c]) * inv[c]                 one fp32 subtraction, one fp32 product (no FMA can form): the device, the host build and numpy agree bit for bit
+ *   clip > 0:  y = y < -clip ? -clip : (y > clip ? clip : y)
+ * y may BE x (in place); otherwise the two must not overlap.  mean, inv: fp32 [D] in the buffers' memory space.  partials == NULL: normalise only.  Otherwise partials is
+ * fp64 [go2nn_obs_norm_partial_rows(N), D, 2]: row b receives, per column, the sums of d and of d * d over rows [b * GO2NN_OBS_NORM_ROWS, (b + 1) * GO2NN_OBS_NORM_ROWS)
+ * of x, d = (double) x - (double) mean: centred on the frozen mean, so S2 - S1^2 / n does not cancel later.  Fixed summation order (a wave's rows in increasing order, then
+ * the four waves in order through LDS), no atomics: two launches give the same bits.
+ * GO2NN_EINVAL, with nothing written, for a null pointer (jobs, x, y, mean, inv), n_jobs outside [1, GO2NN_OBS_NORM_MAX_JOBS], N < 1, D outside [1, 4096], a clip that
+ * is not finite.
+ * go2nn_obs_norm_update: one plain launch (capturable), one block, one lane per column.  table: fp64 [steps, rows, D, 2], the partial tables of the iteration's apply
+ * launches; state: fp64 [1 + 2 D] = count | mean [D] | M2 [D] (M2: the sum of squared deviations; var = M2 / count, the population variance; at count 0 M2 is not read —
+ * the initial var = 1 is forgotten at the first batch); n: the table's samples.  Per column, reading its old mean32 first: S1, S2 = the table's sums in increasing
+ * (step, row) order; batch mean = mean32_old + S1 / n, batch M2 = S2 - S1^2 / n (floored at 0); Chan's pooled update into the state; mean32 = (float) mean,
+ * inv32 = (float) (1 / (sqrt(M2 / count) + eps)).
+ * GO2NN_EINVAL, with nothing written, for a null pointer, steps, rows or D below 1 (D above 4096), n or eps not finite and above 0. */
+#define GO2NN_OBS_NORM_MAX_JOBS 4
+#define GO2NN_OBS_NORM_ROWS 64
+typedef struct Go2nnObsNormJob {
+  const float* x;
+  float* y;
+  const float* mean;
+  const float* inv;
+  double* partials;
+  int32_t D;
+  float clip;
+} Go2nnObsNormJob;
+int32_t go2nn_obs_norm_partial_rows(int32_t N);          /* ceil(N / GO2NN_OBS_NORM_ROWS); 0 for N < 1 */
+int go2nn_obs_norm_apply(const Go2nnObsNormJob* jobs, int32_t n_jobs, int32_t N, void* stream);
+int go2nn_obs_norm_update(const double* table, int32_t steps, int32_t rows, int32_t D, double* state, double n, double eps, float* mean32, float* inv32, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
