@@ -90,7 +90,7 @@ recurrent policy is refused (its mirrored stream needs a twin hidden state).  Wi
 How sure a figure is: with `evaluation.bootstrap = B > 0` (--ci [B]) ONE more launch after go2nn_eval_reduce, on the same accumulators and the same cells, redraws every
 cell's robots with replacement B times (go2nn_eval_bootstrap: csrc/go2nn_bootstrap.h, the rule in include/go2nn.h; Philox seed `bootstrap_seed`) and one more device ->
 host copy brings the [B, cells, 12] fp64 table of resampled reduce rows: res["bootstrap"] = {"replicates", "seed", "confidence", "table", "overall" ([B, 12]: the overall
-row per replicate)}.  A partition's replicate rows are the sums of its cells' (the reshapes and sums of _results), a figure's replicates are _row() of them, and every leaf
+row per replicate)}.  A partition's replicate rows are the sums of its cells' (_cell_views: the reshapes and sums of _results, with the replicate axis in front), a figure's replicates are _row() of them, and every leaf
 dict _row() makes — "overall", "groups", "cells", "perturbations", "sensors", "maneuvers", the ladder's per-level leaves — gains "ci": {metric: [lo, hi]} for CI_KEYS, the
 (1 - confidence) / 2 and (1 + confidence) / 2 quantiles ([nan, nan] where every replicate is NaN).  The cells are strata: every replicate keeps the design's robots per
 cell.  An evaluation is deterministic per robot index, so the same replicates of two checkpoints' evaluations are PAIRED: compare() below.  The modes' own figures
@@ -156,6 +156,27 @@ EVAL_SOURCE = {"last_actions": "last_last_actions"}
 
 def _get(section, key, default=None):
     return section.get(key, default) if isinstance(section, dict) else getattr(section, key, default)
+
+
+def _field_views(a, buf, names, source=None, last=False):
+    """fill the (pointer, env stride, component stride) triples `names` of the ctypes input struct `a` from the simulator's buffers `buf`, in elements from the torch views'
+    own strides -> a.  source: field name -> buffer name where they differ;  last: the component stride is that of the LAST dimension (per-body fields, whose body stride
+    the struct carries separately), not of dimension 1"""
+    for name in names:
+        t, f = buf[(source or {}).get(name, name)], getattr(a, name)
+        f.p, f.env_stride, f.comp_stride = t.data_ptr(), t.stride(0), (t.stride(t.dim() - 1 if last else 1) if t.dim() > 1 else 0)
+    return a
+
+
+class _ScoreTable:
+    """One per-env score table `table` [rows, N]: begun once per evaluation (go2nn_<name>_begin), advanced once per step (go2nn_<name>_accumulate; robust and maneuver also
+    go2nn_<name>_apply before the simulator steps) and reduced once into `out` [cells, cols] (go2nn_<name>_reduce).  make_in: -> the kernels' input struct on the current
+    simulator;  args: the tensors a step's launches take between the input and the table (the specs and the env -> spec map);  reduce_args: what the reduce takes in front
+    of `out`.  The evaluator's attributes stay the owners of every tensor"""
+
+    def __init__(self, name, make_in, table, out, args=(), reduce_args=()):
+        self.name, self.make_in, self.table, self.out, self.reduce_args = name, make_in, table, out, tuple(reduce_args)
+        self.args = tuple(C.c_void_p(t.data_ptr()) for t in args)
 
 
 def replicate_metrics(rows):
@@ -234,13 +255,7 @@ def evaluation_env_cfg(env_cfg, ev):
 class _Policy:
     def __init__(self, ev, model):
         self.ev, self.model = ev, model
-
-    def _stream(self):
-        return self.ev._stream()
-
-    def _check(self, rc, what):
-        if rc != 0:
-            raise RuntimeError("%s failed: %s" % (what, self.ev.nn.go2nn_last_error().decode()))
+        self._stream, self._check = ev._stream, ev._check          # the evaluator's own: one stream, one way to fail
 
     def begin(self, obs):
         """once per evaluation, after the reset: read the CURRENT weights (packed images are rebuilt here, so an evaluation after an update never sees stale ones)"""
@@ -479,6 +494,7 @@ class PolicyEvaluator:
         N = self.num_envs
         self.acc = torch.zeros(GO2NN_EVAL_NUM, N, device=self.device)
         self.out = torch.zeros(self.num_cells, GO2NN_EVAL_NUM + 2, dtype=torch.float64, device=self.device)
+        self.tables = []          # the active _ScoreTable records in begin / reduce order: robust, ladder, maneuver, gait, asym
         if self.perturbations is not None:
             self._build_robust()
         if self.sensors is not None:
@@ -490,6 +506,8 @@ class PolicyEvaluator:
         self.gait = bool(_get(evaluation, "gait", False))
         if self.gait:
             self._build_gait()
+        if self.axis_key is not None or self.gait:
+            self._warn_small_cells()
         self.asymmetry = bool(_get(evaluation, "asymmetry", False))
         if self.asymmetry:
             self._build_asymmetry()
@@ -618,10 +636,7 @@ class PolicyEvaluator:
         self.man = torch.from_numpy(self.man_host).to(self.device)
         self.mtable = torch.zeros(GO2NN_MANEUVER_NUM, self.num_envs, device=self.device)
         self.mout = torch.zeros(self.num_cells, GO2NN_MANEUVER_ACC_NUM + 1, dtype=torch.float64, device=self.device)
-        sizes = np.bincount(self.cell_host, minlength=self.num_cells)
-        if sizes.min() < 4:
-            print("[go2_rl_gym_amd] evaluation: %d of %d (terrain x maneuver) cells have fewer than 4 robots (smallest: %d); raise evaluation.num_envs"
-                  % (int((sizes < 4).sum()), self.num_cells, int(sizes.min())))
+        self.tables.append(_ScoreTable("maneuver", self._maneuver_in, self.mtable, self.mout, args=(self.mspecs, self.man)))
 
     def _place_on_levels(self):
         """the ladder's env placement on the current simulator: every env on its cell's row of the terrain grid, in the column the simulator gave it"""
@@ -635,19 +650,27 @@ class PolicyEvaluator:
         self.dist2_thr = float(np.float32(self.ladder_distance) * np.float32(self.ladder_distance))
         self.ltable = torch.zeros(GO2NN_LADDER_NUM, self.num_envs, device=self.device)
         self.lout = torch.zeros(self.num_cells, GO2NN_LADDER_OUT_NUM, dtype=torch.float64, device=self.device)
-        sizes = np.bincount(self.cell_host, minlength=self.num_cells)
-        if sizes.min() < 4:
-            print("[go2_rl_gym_amd] evaluation: %d of %d (terrain x level x scenario) cells have fewer than 4 robots (smallest: %d); raise evaluation.num_envs"
-                  % (int((sizes < 4).sum()), self.num_cells, int(sizes.min())))
+        self.tables.append(_ScoreTable("ladder", self._ladder_in, self.ltable, self.lout, reduce_args=(self.dist2_thr,)))
 
     def _build_groups(self):
         """env -> (terrain kind x scenario) group, built once on the host: the kinds are those of the columns the envs stand in (one kind, 'plane', without a terrain mesh);
         within a kind the envs take the scenarios in turn, so the groups of a kind differ by at most one env.  With P perturbations (or P sensor conditions) they take the (scenario, perturbation)
         CELLS in turn; cell index = (terrain * S + scenario) * P + perturbation — the kernels' group —, and a group is the union of its P cells (P = 1 without).
-        With the ladder's L levels they take the (level, scenario) cells in turn; cell index = (terrain * L + level) * S + scenario, a group is the union of its L cells"""
+        With the ladder's L levels they take the (level, scenario) cells in turn; cell index = (terrain * L + level) * S + scenario, a group is the union of its L cells.
+        The layout is kept for everything that reshapes a cell table or names a cell: T, S, P, L, the extra axis's result key `axis_key`, its values' names `axis_names`
+        and `cell_axes`, what a cell is"""
         from .terrain import KIND_NAMES
         N, S, P = self.num_envs, len(self.scenarios), len(self.perturbations or self.sensors or [None])
         L = len(self.levels) if self.ladder else 1
+        if self.ladder:
+            self.axis_key, self.axis_names, self.cell_axes = "ladder", list(self.levels), ["terrain", "level", "scenario"]
+        elif self.maneuvers is not None:          # (a "scenario" is a maneuver there)
+            self.axis_key, self.axis_names, self.cell_axes = "maneuvers", [m[0] for m in self.maneuvers], ["terrain", "maneuver"]
+        elif self.perturbations is not None or self.sensors is not None:
+            self.axis_key, self.cell_axes = ("perturbations", ["terrain", "scenario", "perturbation"]) if self.perturbations is not None else ("sensors", ["terrain", "scenario", "sensor"])
+            self.axis_names = [p[0] for p in (self.perturbations or self.sensors)]
+        else:
+            self.axis_key, self.axis_names, self.cell_axes = None, [], ["terrain", "scenario"]
         if self.env.custom_origins:
             kind_of_env = self.env.terrain_cols2id.cpu().numpy()[self.env.terrain_types.cpu().numpy()]
             kinds = [int(k) for k in sorted(set(kind_of_env.tolist()))]
@@ -666,6 +689,7 @@ class PolicyEvaluator:
                 scen[ids], pert[ids] = turn // P, turn % P
             group[ids] = ki * S + scen[ids]
         self.groups = [(t, s[0]) for t in self.terrain_names for s in self.scenarios]
+        self.T, self.S, self.P, self.L = len(self.terrain_names), S, P, L
         self.group_host, self.pert_host = group, pert
         self.cell_host, self.num_cells = group * P + pert, len(self.groups) * P
         if self.ladder:          # level_index_host: index into self.levels;  level_of_env: the row of the terrain grid itself
@@ -676,6 +700,24 @@ class PolicyEvaluator:
         cmd[:, :3] = np.asarray([s[1:4] for s in self.scenarios], np.float32)[scen]
         self.commands_host = cmd
         self.commands = torch.from_numpy(cmd).to(self.device)
+
+    def _warn_small_cells(self):
+        """said once per evaluator, of the finest cells the mode has — or, without a mode, of the groups the gait figures are pooled over"""
+        sizes = np.bincount(self.cell_host, minlength=self.num_cells)
+        if sizes.min() < 4:
+            axes = " x ".join(self.cell_axes) + (" condition" if self.axis_key == "sensors" else "")
+            what = "cells have fewer than 4 robots (smallest: %d)" if self.axis_key is not None else "groups have fewer than 4 robots (smallest: %d) for the gait figures"
+            print("[go2_rl_gym_amd] evaluation: %d of %d (%s) %s; raise evaluation.num_envs" % (int((sizes < 4).sum()), self.num_cells, axes, what % int(sizes.min())))
+
+    def _cell_views(self, cells, pool=np.sum):
+        """cells [..., num_cells, cols]: a reduce table per cell (the bootstrap's with its replicate axis in front);  pool(a, axis): stacked rows -> the row of their union
+        -> (the per-group table [..., T * S, cols]: the cells pooled over the extra axis, the per-cell view: [..., T, L, S, cols] with the ladder, [..., T * S, P, cols] without)"""
+        lead = cells.shape[:-2]
+        if self.ladder:
+            view = cells.reshape(lead + (self.T, self.L, self.S, -1))
+            return pool(view, len(lead) + 1).reshape(lead + (self.T * self.S, -1)), view
+        view = cells.reshape(lead + (self.T * self.S, self.P, -1))          # P = 1: the cells' rows themselves
+        return pool(view, len(lead) + 1), view
 
     def _build_robust(self):
         """the perturbations as the kernels read them: P specs and the env -> perturbation map in device memory, the per-env table and the reduce output"""
@@ -707,10 +749,7 @@ class PolicyEvaluator:
         self.pert = torch.from_numpy(self.pert_host).to(self.device)
         self.rtable = torch.zeros(GO2NN_ROBUST_NUM, self.num_envs, device=self.device)
         self.rout = torch.zeros(self.num_cells, GO2NN_ROBUST_ACC_NUM + 1, dtype=torch.float64, device=self.device)
-        sizes = np.bincount(self.cell_host, minlength=self.num_cells)
-        if sizes.min() < 4:
-            print("[go2_rl_gym_amd] evaluation: %d of %d (terrain x scenario x perturbation) cells have fewer than 4 robots (smallest: %d); raise evaluation.num_envs"
-                  % (int((sizes < 4).sum()), self.num_cells, int(sizes.min())))
+        self.tables.append(_ScoreTable("robust", self._robust_in, self.rtable, self.rout, args=(self.specs, self.pert)))
 
     def _build_sensors(self):
         """the sensor conditions as the kernel reads them: P specs (observation scales folded in), the env -> condition map, the observation's layout (kind, the task's noise
@@ -744,10 +783,6 @@ class PolicyEvaluator:
         self.sstate = torch.zeros(int(self.nn.go2nn_sensor_state_bytes(self.num_envs, D)), dtype=torch.uint8, device=self.device)
         self.delivered = torch.zeros(self.num_envs, D, device=self.device)
         self.sensor_clip, self.sensor_seed = float(self.cfg.normalization.clip_observations), int(_get(self.ev, "seed", 12345)) & 0xFFFFFFFF
-        sizes = np.bincount(self.cell_host, minlength=self.num_cells)
-        if sizes.min() < 4:
-            print("[go2_rl_gym_amd] evaluation: %d of %d (terrain x scenario x sensor condition) cells have fewer than 4 robots (smallest: %d); raise evaluation.num_envs"
-                  % (int((sizes < 4).sum()), self.num_cells, int(sizes.min())))
 
     def _build_gait(self):
         """the gait scorer's device side: the per-env table, the reduce output per cell, the feet in foot_body order and the two diagonal pairs among them by NAME"""
@@ -766,10 +801,7 @@ class PolicyEvaluator:
         self.gait_diagonal = masks
         self.gtable = torch.zeros(GO2NN_GAIT_NUM, self.num_envs, device=self.device)
         self.gout = torch.zeros(self.num_cells, GO2NN_GAIT_OUT_NUM, dtype=torch.float64, device=self.device)
-        sizes = np.bincount(self.cell_host, minlength=self.num_cells)
-        if sizes.min() < 4 and self.perturbations is None and self.sensors is None and not self.ladder and self.maneuvers is None:          # (those modes say it of the same cells themselves)
-            print("[go2_rl_gym_amd] evaluation: %d of %d (terrain x scenario) groups have fewer than 4 robots (smallest: %d) for the gait figures; raise evaluation.num_envs"
-                  % (int((sizes < 4).sum()), self.num_cells, int(sizes.min())))
+        self.tables.append(_ScoreTable("gait", self._gait_in, self.gtable, self.gout))
 
     def _build_asymmetry(self):
         """the asymmetry scorer's device side: the mirror tables of the task's layout (any other layout raises mirror_tables' ValueError), the sides of the feet by NAME,
@@ -797,14 +829,12 @@ class PolicyEvaluator:
         self.aout = torch.zeros(self.num_cells, GO2NN_ASYM_OUT_NUM, dtype=torch.float64, device=self.device)
         self.asym_obs = torch.zeros(2, N, len(self.asym_tables.obs[0]), device=self.device)          # [0]: the copy half of go2nn_mirror_rows, [1]: the mirror image
         self.asym_hist = self.asym_hist_table = self.asym_last = None
+        self.tables.append(_ScoreTable("asym", self._asym_in, self.atable, self.aout))
 
     def _asym_in(self):
         """the asymmetry kernel's view of the simulator's buffers (as _gait_in) and its small tables, by value"""
-        b, a = self.env._buf, Go2nnAsymIn()
-        for name in ASYM_FIELDS:
-            t, f = b[name], getattr(a, name)
-            f.p, f.env_stride, f.comp_stride = t.data_ptr(), t.stride(0), (t.stride(t.dim() - 1) if t.dim() > 1 else 0)
-        d = b["dof_state"]
+        b = self.env._buf
+        a, d = _field_views(Go2nnAsymIn(), b, ASYM_FIELDS, last=True), b["dof_state"]
         a.dof_state.comp_stride, a.dof_vel_offset, a.contact_body_stride = d.stride(1), d.stride(2), b["contact_forces"].stride(1)
         a.foot_body[:], a.foot_side[:], a.joint_side[:], a.joint_kind[:] = self.asym_feet, self.asym_foot_side, self.asym_joint_side, self.asym_joint_kind
         a.action_perm[:], a.action_sign[:] = [int(p) for p in self.asym_tables.action[0]], [float(s) for s in self.asym_tables.action[1]]
@@ -839,13 +869,12 @@ class PolicyEvaluator:
             raise ValueError("evaluation.blackbox: %d robots x %d steps x %d bytes per frame = %d bytes, more than evaluation.blackbox_max_bytes = %d; shorten "
                              "evaluation.blackbox_seconds or lower evaluation.num_envs" % (self.num_envs, T, GO2NN_TRACE_WIDTH * 4, need, cap))
         self.fall_recorder = FallRecorder(self.env, T, nn_lib=self.nn)
-        T_, S, P = len(self.terrain_names), len(self.scenarios), len(self.perturbations or self.sensors or [None])
         if self.ladder:
             names = ["%s/level_%d/%s" % (t, lv, s[0]) for t in self.terrain_names for lv in self.levels for s in self.scenarios]
         else:
-            axis = self.perturbations or self.sensors
-            names = ["%s/%s" % (t, s[0]) + ("/" + p[0] if axis else "") for t in self.terrain_names for s in self.scenarios for p in (axis or [None])]
-        assert len(names) == self.num_cells == (T_ * S * (len(self.levels) if self.ladder else P))
+            axis = self.axis_names if self.axis_key in ("perturbations", "sensors") else [None]          # (a maneuver is the cell's scenario itself)
+            names = ["%s/%s" % (t, s[0]) + ("/" + p if p is not None else "") for t in self.terrain_names for s in self.scenarios for p in axis]
+        assert len(names) == self.num_cells == self.T * self.S * self.L * self.P
         self.cell_names = names
 
     def _build_bootstrap(self):
@@ -876,34 +905,33 @@ class PolicyEvaluator:
     def _label(self, d, ids):
         """what a trace and a falls dict say about their robots `ids`: group, and with the mode's extra axis its value per robot and its schedule"""
         d.update(group_of_robot=self.group_host[ids].copy(), terrain_names=list(self.terrain_names), scenarios=[s[0] for s in self.scenarios])
-        if self.ladder:
-            d.update(levels=list(self.levels), level_of_robot=self.level_of_env[ids].copy())
-        if self.perturbations is not None:          # push_steps: the counted steps (= frame indices) whose go2nn_robust_apply pushed; the frame holds the state AFTER that step
-            d.update(perturbations=[p[0] for p in self.perturbations], pert_of_robot=self.pert_host[ids].copy(), push_steps=self.push_steps.copy())
-        if self.sensors is not None:
-            d.update(sensors=[c[0] for c in self.sensors], sensor_of_robot=self.sensor_host[ids].copy())
-        if self.maneuvers is not None:
+        key, names = self.axis_key, list(self.axis_names)
+        if key == "ladder":
+            d.update(levels=names, level_of_robot=self.level_of_env[ids].copy())
+        elif key == "perturbations":          # push_steps: the counted steps (= frame indices) whose go2nn_robust_apply pushed; the frame holds the state AFTER that step
+            d.update(perturbations=names, pert_of_robot=self.pert_host[ids].copy(), push_steps=self.push_steps.copy())
+        elif key == "sensors":
+            d.update(sensors=names, sensor_of_robot=self.sensor_host[ids].copy())
+        elif key == "maneuvers":
             # switch_steps [M, GO2NN_MANEUVER_MAX_SEGS - 1] int32: per maneuver the counted steps (= frame indices) at which a new segment begins — that frame carries the
             # new command —, padded with -1 (a rectangular array: maneuvers differ in their number of switches, and the trace goes to an .npz)
             steps = np.full((len(self.maneuvers), GO2NN_MANEUVER_MAX_SEGS - 1), -1, np.int32)
             for mi, m in enumerate(self.maneuvers):
                 steps[mi, :len(self.switch_steps[m[0]])] = self.switch_steps[m[0]]
-            d.update(maneuvers=[m[0] for m in self.maneuvers], maneuver_of_robot=self.man_host[ids].copy(), switch_steps=steps)
+            d.update(maneuvers=names, maneuver_of_robot=self.man_host[ids].copy(), switch_steps=steps)
 
     def _gait_in(self):
         """the gait kernel's view of the simulator's buffers (as TrajectoryRecorder.bind: component and body strides of the two per-body fields)"""
-        b, a = self.env._buf, Go2nnGaitIn()
-        for name in GAIT_FIELDS:
-            t, f = b[name], getattr(a, name)
-            f.p, f.env_stride, f.comp_stride = t.data_ptr(), t.stride(0), (t.stride(t.dim() - 1) if t.dim() > 1 else 0)
+        b = self.env._buf
+        a = _field_views(Go2nnGaitIn(), b, GAIT_FIELDS, last=True)
         a.rigid_body_stride, a.contact_body_stride = b["rigid_body_states"].stride(1), b["contact_forces"].stride(1)
         a.foot_body[:], a.diagonal_mask[:], a.contact_threshold = self.gait_feet, self.gait_diagonal, self.gait_threshold
         return a
 
     def _sensor_in(self):
         """the sensor kernel's view of the current simulator: its observation and reset flags, and the evaluator's own layout tensors"""
-        t, a = self.env.obs_buf, Go2nnSensorIn()
-        a.obs.p, a.obs.env_stride, a.obs.comp_stride = t.data_ptr(), t.stride(0), t.stride(1)
+        t = self.env.obs_buf
+        a = _field_views(Go2nnSensorIn(), {"obs": t}, ("obs",))
         a.dones, a.scale, a.kind = self.env._buf["reset_buf"].data_ptr(), self.sensor_scale.data_ptr(), self.sensor_kind.data_ptr()
         a.D, a.num_specs, a.clip, a.seed = t.shape[1], len(self.sensors), self.sensor_clip, self.sensor_seed
         return a
@@ -921,86 +949,62 @@ class PolicyEvaluator:
 
     def _robust_in(self):
         """the perturbation kernels' view of the simulator's buffers (as _eval_in)"""
-        b, a = self.env._buf, Go2nnRobustIn()
-        for name in ROBUST_FIELDS:
-            t, f = b[name], getattr(a, name)
-            f.p, f.env_stride, f.comp_stride = t.data_ptr(), t.stride(0), (t.stride(1) if t.dim() > 1 else 0)
+        a = _field_views(Go2nnRobustIn(), self.env._buf, ROBUST_FIELDS)
         a.num_specs = len(self.perturbations)
         return a
 
-    def _robust(self, fn, what, rin):
-        self._check(fn(C.byref(rin), C.c_void_p(self.specs.data_ptr()), C.c_void_p(self.pert.data_ptr()), C.c_void_p(self.rtable.data_ptr()), self.num_envs, self._stream()), what)
-
     def _ladder_in(self):
         """the ladder kernel's view of the simulator's buffers (as _eval_in)"""
-        b, a = self.env._buf, Go2nnLadderIn()
-        for name in LADDER_FIELDS:
-            t, f = b[name], getattr(a, name)
-            f.p, f.env_stride, f.comp_stride = t.data_ptr(), t.stride(0), (t.stride(1) if t.dim() > 1 else 0)
+        a = _field_views(Go2nnLadderIn(), self.env._buf, LADDER_FIELDS)
         a.dist2_thr = self.dist2_thr
         return a
 
     def _maneuver_in(self):
         """the maneuver kernels' view of the simulator's buffers (as _eval_in)"""
-        b, a = self.env._buf, Go2nnManeuverIn()
-        for name in MANEUVER_FIELDS:
-            t, f = b[name], getattr(a, name)
-            f.p, f.env_stride, f.comp_stride = t.data_ptr(), t.stride(0), (t.stride(1) if t.dim() > 1 else 0)
-        a.num_specs, a.num_commands = len(self.maneuvers), b["commands"].shape[1]
+        a = _field_views(Go2nnManeuverIn(), self.env._buf, MANEUVER_FIELDS)
+        a.num_specs, a.num_commands = len(self.maneuvers), self.env._buf["commands"].shape[1]
         return a
 
-    def _maneuver(self, fn, what, min_):
-        self._check(fn(C.byref(min_), C.c_void_p(self.mspecs.data_ptr()), C.c_void_p(self.man.data_ptr()), C.c_void_p(self.mtable.data_ptr()), self.num_envs, self._stream()), what)
-
     def _eval_in(self):
-        """the accumulate kernel's view of the simulator's buffers: (pointer, env stride, component stride) in elements from the torch views' own strides"""
-        env, a = self.env, Go2nnEvalIn()
-        b = env._buf
-        for name in EVAL_FIELDS:
-            t = b[EVAL_SOURCE.get(name, name)]
-            f = getattr(a, name)
-            f.p, f.env_stride, f.comp_stride = t.data_ptr(), t.stride(0), (t.stride(1) if t.dim() > 1 else 0)
-        a.dof_vel_offset = b["dof_state"].stride(2)
+        """the accumulate kernel's view of the simulator's buffers (_field_views; its `last_actions` is EVAL_SOURCE's buffer)"""
+        a = _field_views(Go2nnEvalIn(), self.env._buf, EVAL_FIELDS, source=EVAL_SOURCE)
+        a.dof_vel_offset = self.env._buf["dof_state"].stride(2)
         a.dof_limits, a.dt = self.dof_limits.data_ptr(), self.dt
         return a
 
+    def _table_launch(self, what, t, tin, *extra):
+        """one launch of a score table's step: go2nn_<name>_<what>(input, the table's own arguments, [extra,] table, N, stream), `what` being "apply" or "accumulate" """
+        name = "go2nn_%s_%s" % (t.name, what)
+        self._check(getattr(self.nn, name)(C.byref(tin), *t.args, *extra, C.c_void_p(t.table.data_ptr()), self.num_envs, self._stream()), name)
+
     # ------------------------------------------------------------------ one env step of the evaluation (pure enqueue)
-    def _step(self, pol, ein, rin=None, k=None, lin=None, min_=None, sin=None, gin=None, ain=None):
-        """rin: the perturbation kernels' input (None without perturbations);  k: the step's index in an eager run (None inside a capture: no callback there);
-        lin: the ladder kernel's input (None without the ladder);  min_: the maneuver kernels' input (None without maneuvers);  sin: the sensor kernel's input (None without
-        sensors: the policy then reads the simulator's observation itself);  gin: the gait kernel's input (None without gait);  ain: (the asymmetry kernel's input, the
-        mirror launch's jobs, the mirrored history or None) (None without asymmetry)"""
+    def _step(self, pol, run, k=None):
+        """run: what evaluate() made for this evaluation — `ein`, `sin` (the eval and sensor kernels' inputs; sin None without sensors: the policy then reads the simulator's
+        observation itself), the active score tables as (record, input) pairs: `applied` (maneuver or robust: the one that acts before the simulator steps), `maneuver`,
+        `scored` (robust, ladder, gait), `asym` (each None / empty when off), and for the asymmetry `jobs` (the mirror launch's) and `hist_m` (the mirrored history or None);
+        k: the step's index in an eager run (None inside a capture: no callback there)"""
         env = self.env
-        obs = env.obs_buf if sin is None else self.delivered
+        obs = env.obs_buf if run.sin is None else self.delivered
         actions = pol.act(obs)
-        if ain is not None:          # the mirror image of what act() has just read, and the same weights on it; nothing act() owns moves
-            mirror_rows(self.nn, ain[1], 1, self.num_envs, self._stream())
-            mirrored = pol.act_mirrored(self.asym_obs[1], ain[2])
-        if min_ is not None:
-            self._maneuver(self.nn.go2nn_maneuver_apply, "go2nn_maneuver_apply", min_)
-            if k is not None and self.apply_callback is not None:
-                self.apply_callback(self, k, k >= self.warmup_steps)
-        if rin is not None:
-            self._robust(self.nn.go2nn_robust_apply, "go2nn_robust_apply", rin)
+        if run.asym is not None:          # the mirror image of what act() has just read, and the same weights on it; nothing act() owns moves
+            mirror_rows(self.nn, run.jobs, 1, self.num_envs, self._stream())
+            mirrored = pol.act_mirrored(self.asym_obs[1], run.hist_m)
+        if run.applied is not None:
+            self._table_launch("apply", *run.applied)
             if k is not None and self.apply_callback is not None:
                 self.apply_callback(self, k, k >= self.warmup_steps)
         _abi.check(env.lib, env.lib.go2sim_step(env.handle, C.c_void_p(actions.data_ptr()), self._stream()), "go2sim_step")
-        if min_ is not None:          # (it rewrites the command row itself: the maneuver's command at this step)
-            self._maneuver(self.nn.go2nn_maneuver_accumulate, "go2nn_maneuver_accumulate", min_)
+        if run.maneuver is not None:          # (it rewrites the command row itself: the maneuver's command at this step)
+            self._table_launch("accumulate", *run.maneuver)
         else:
             env.commands.copy_(self.commands)          # a robot that fell was reset by the step and drew a new command: the scenario's command holds
-        if sin is not None:          # the frame the policy gets NEXT step, and what its history / memory is fed below
-            self._sensor_apply(sin)
-        self._check(self.nn.go2nn_eval_accumulate(C.byref(ein), C.c_void_p(self.acc.data_ptr()), self.num_envs, self._stream()), "go2nn_eval_accumulate")
-        if rin is not None:
-            self._robust(self.nn.go2nn_robust_accumulate, "go2nn_robust_accumulate", rin)
-        if lin is not None:
-            self._check(self.nn.go2nn_ladder_accumulate(C.byref(lin), C.c_void_p(self.ltable.data_ptr()), self.num_envs, self._stream()), "go2nn_ladder_accumulate")
-        if gin is not None:
-            self._check(self.nn.go2nn_gait_accumulate(C.byref(gin), C.c_void_p(self.gtable.data_ptr()), self.num_envs, self._stream()), "go2nn_gait_accumulate")
-        if ain is not None:
-            self._check(self.nn.go2nn_asym_accumulate(C.byref(ain[0]), C.c_void_p(actions.data_ptr()), C.c_void_p(mirrored.data_ptr()), C.c_void_p(self.atable.data_ptr()),
-                                                      self.num_envs, self._stream()), "go2nn_asym_accumulate")
+        if run.sin is not None:          # the frame the policy gets NEXT step, and what its history / memory is fed below
+            self._sensor_apply(run.sin)
+        self._check(self.nn.go2nn_eval_accumulate(C.byref(run.ein), C.c_void_p(self.acc.data_ptr()), self.num_envs, self._stream()), "go2nn_eval_accumulate")
+        for pair in run.scored:
+            self._table_launch("accumulate", *pair)
+        if run.asym is not None:
+            self._table_launch("accumulate", *run.asym, C.c_void_p(actions.data_ptr()), C.c_void_p(mirrored.data_ptr()))
             self.asym_last = (actions, mirrored)          # (what a step_callback of a test reads next to asym_obs)
         if self.recorder is not None:
             self.recorder.record()
@@ -1013,15 +1017,15 @@ class PolicyEvaluator:
         if self.recorder is not None:
             self.recorder.clear()
 
-    def _run_eager(self, pol, ein, rin, lin=None, min_=None, sin=None, gin=None, ain=None):
+    def _run_eager(self, pol, run):
         for k in range(self.warmup_steps + self.steps):
             if k == self.warmup_steps:
                 self._clear()
-            self._step(pol, ein, rin, k, lin, min_, sin, gin, ain)
+            self._step(pol, run, k)
             if self.step_callback is not None:
                 self.step_callback(self, k, k >= self.warmup_steps)
 
-    def _run_graph(self, pol, ein, rin, lin=None, min_=None, sin=None, gin=None, ain=None):
+    def _run_graph(self, pol, run):
         """capture `chunk` steps on this evaluation's simulator, replay them for the whole horizon -> False if the capture failed (nothing has run then)"""
         from ..rsl_rl.algorithms._graph import no_gc, strict_graphs
         torch.cuda.synchronize(self.device)
@@ -1029,7 +1033,7 @@ class PolicyEvaluator:
         try:
             with no_gc(), torch.cuda.graph(g):
                 for _ in range(self.chunk):
-                    self._step(pol, ein, rin, lin=lin, min_=min_, sin=sin, gin=gin, ain=ain)
+                    self._step(pol, run)
         except Exception as e:      # noqa: BLE001
             if strict_graphs():
                 raise RuntimeError("HIP-graph capture of the evaluation failed (%s: %s)" % (type(e).__name__, e)) from e
@@ -1090,35 +1094,24 @@ class PolicyEvaluator:
             if self.recorder is not None:
                 self.recorder.bind(env)
             self._clear()
-            ein, rin = self._eval_in(), None
-            if self.perturbations is not None:          # the table's step counter starts at -warmup_steps: nothing is pushed or counted before step 0, no clear at the boundary
-                rin = self._robust_in()
-                self._check(self.nn.go2nn_robust_begin(C.c_void_p(self.rtable.data_ptr()), self.num_envs, -self.warmup_steps, self._stream()), "go2nn_robust_begin")
-            lin = None
-            if self.ladder:          # as above: the table's step counter starts at -warmup_steps, the origin of the distance is taken at step 0 by the kernel itself
-                lin = self._ladder_in()
-                self._check(self.nn.go2nn_ladder_begin(C.c_void_p(self.ltable.data_ptr()), self.num_envs, -self.warmup_steps, self._stream()), "go2nn_ladder_begin")
-            min_ = None
-            if self.maneuvers is not None:          # as above; segment 0 of every maneuver also covers the warm-up, so the kernels run from the first warm-up step on
-                min_ = self._maneuver_in()
-                self._check(self.nn.go2nn_maneuver_begin(C.c_void_p(self.mtable.data_ptr()), self.num_envs, -self.warmup_steps, self._stream()), "go2nn_maneuver_begin")
-            gin = None
-            if self.gait:          # as above: the step counter starts at -warmup_steps; the first counted step opens every foot's first segment
-                gin = self._gait_in()
-                self._check(self.nn.go2nn_gait_begin(C.c_void_p(self.gtable.data_ptr()), self.num_envs, -self.warmup_steps, self._stream()), "go2nn_gait_begin")
-            ain = None
-            if self.asymmetry:          # as above: the step counter starts at -warmup_steps and the kernel advances it
-                jobs, hist_m = self._asym_jobs(pol, env.obs_buf if sin is None else self.delivered)
-                ain = (self._asym_in(), jobs, hist_m)
-                self._check(self.nn.go2nn_asym_begin(C.c_void_p(self.atable.data_ptr()), self.num_envs, -self.warmup_steps, self._stream()), "go2nn_asym_begin")
+            # every score table's step counter starts at -warmup_steps and its kernels advance it: nothing is pushed, switched or counted before step 0 (the ladder takes the
+            # distance's origin there, the gait opens every foot's first segment there), and no table is cleared at the boundary
+            pairs = [(t, t.make_in()) for t in self.tables]
+            by = {t.name: (t, tin) for t, tin in pairs}
+            run = types.SimpleNamespace(ein=self._eval_in(), sin=sin, tables=pairs, maneuver=by.get("maneuver"), applied=by.get("maneuver") or by.get("robust"),
+                                        scored=[by[n] for n in ("robust", "ladder", "gait") if n in by], asym=by.get("asym"), jobs=None, hist_m=None)
+            if run.asym is not None:
+                run.jobs, run.hist_m = self._asym_jobs(pol, env.obs_buf if sin is None else self.delivered)
+            for t, _ in pairs:
+                self._check(getattr(self.nn, "go2nn_%s_begin" % t.name)(C.c_void_p(t.table.data_ptr()), self.num_envs, -self.warmup_steps, self._stream()), "go2nn_%s_begin" % t.name)
             if self.fall_recorder is not None:          # as above; NOT cleared at the warm-up boundary: a ring's history runs through it
                 self.fall_recorder.bind(env)
                 self.fall_recorder.begin(-self.warmup_steps)
             replay = bool(_get(self.ev, "replay", False))
             graph = (replay and self.on_device and self.evaluations > 0 and self.step_callback is None) if use_graph is None else bool(use_graph and self.on_device)
-            done = graph and self._run_graph(pol, ein, rin, lin, min_, sin, gin, ain)
+            done = graph and self._run_graph(pol, run)
             if not done:
-                self._run_eager(pol, ein, rin, lin, min_, sin, gin, ain)
+                self._run_eager(pol, run)
             self.last_mode = "graph" if done else "eager"
             self._check(self.nn.go2nn_eval_reduce(C.c_void_p(self.acc.data_ptr()), C.c_void_p(self.group.data_ptr()), self.num_envs, self.num_cells,
                                                   C.c_void_p(self.out.data_ptr()), self._stream()), "go2nn_eval_reduce")
@@ -1126,31 +1119,12 @@ class PolicyEvaluator:
                 self._check(self.nn.go2nn_eval_bootstrap(C.c_void_p(self.acc.data_ptr()), C.c_void_p(self.cell_start.data_ptr()), C.c_void_p(self.cell_envs.data_ptr()),
                                                          self.num_envs, self.num_cells, self.bootstrap, self.bootstrap_seed, C.c_void_p(self.boot_out.data_ptr()), self._stream()),
                             "go2nn_eval_bootstrap")
-            rtable = None
-            if rin is not None:
-                self._check(self.nn.go2nn_robust_reduce(C.c_void_p(self.rtable.data_ptr()), C.c_void_p(self.group.data_ptr()), self.num_envs, self.num_cells,
-                                                        C.c_void_p(self.rout.data_ptr()), self._stream()), "go2nn_robust_reduce")
-                rtable = self.rout.cpu().numpy().copy()
-            ltable = None
-            if lin is not None:
-                self._check(self.nn.go2nn_ladder_reduce(C.c_void_p(self.ltable.data_ptr()), C.c_void_p(self.group.data_ptr()), self.num_envs, self.num_cells, self.dist2_thr,
-                                                        C.c_void_p(self.lout.data_ptr()), self._stream()), "go2nn_ladder_reduce")
-                ltable = self.lout.cpu().numpy().copy()
-            mtable = None
-            if min_ is not None:
-                self._check(self.nn.go2nn_maneuver_reduce(C.c_void_p(self.mtable.data_ptr()), C.c_void_p(self.group.data_ptr()), self.num_envs, self.num_cells,
-                                                          C.c_void_p(self.mout.data_ptr()), self._stream()), "go2nn_maneuver_reduce")
-                mtable = self.mout.cpu().numpy().copy()
-            gtable = None
-            if gin is not None:
-                self._check(self.nn.go2nn_gait_reduce(C.c_void_p(self.gtable.data_ptr()), C.c_void_p(self.group.data_ptr()), self.num_envs, self.num_cells,
-                                                      C.c_void_p(self.gout.data_ptr()), self._stream()), "go2nn_gait_reduce")
-                gtable = self.gout.cpu().numpy().copy()
-            atable = None
-            if ain is not None:
-                self._check(self.nn.go2nn_asym_reduce(C.c_void_p(self.atable.data_ptr()), C.c_void_p(self.group.data_ptr()), self.num_envs, self.num_cells,
-                                                      C.c_void_p(self.aout.data_ptr()), self._stream()), "go2nn_asym_reduce")
-                atable = self.aout.cpu().numpy().copy()
+            host = {}
+            for t, _ in pairs:
+                self._check(getattr(self.nn, "go2nn_%s_reduce" % t.name)(C.c_void_p(t.table.data_ptr()), C.c_void_p(self.group.data_ptr()), self.num_envs, self.num_cells,
+                                                                         *t.reduce_args, C.c_void_p(t.out.data_ptr()), self._stream()), "go2nn_%s_reduce" % t.name)
+                host[t.name] = t.out.cpu().numpy().copy()
+            if run.asym is not None:
                 self.asym_last = None
             table = self.out.cpu().numpy().copy()          # the device -> host copy (and synchronisation) of an evaluation
             btable = self.boot_out.cpu().numpy().copy() if self.bootstrap > 0 else None
@@ -1158,13 +1132,13 @@ class PolicyEvaluator:
             falls = self.fall_recorder.fetch(self._keep_fallen) if self.fall_recorder is not None else None
             self._graph = None
             self.evaluations += 1
-        res = self._results(table, rtable, ltable, mtable)
+        res = self._results(table, host.get("robust"), host.get("ladder"), host.get("maneuver"))
         if btable is not None:
             self._bootstrap_results(res, btable)
-        if gtable is not None:
-            self._gait_results(res, gtable)
-        if atable is not None:
-            self._asym_results(res, atable)
+        if "gait" in host:
+            self._gait_results(res, host["gait"])
+        if "asym" in host:
+            self._asym_results(res, host["asym"])
         if trace is not None:
             self._label(trace, trace["env_ids"])
             res["trace"] = trace
@@ -1209,8 +1183,7 @@ class PolicyEvaluator:
 
     def _ladder_results(self, res, cells, lcells):
         """cells / lcells: the eval / ladder reduce tables per (terrain, level, scenario) cell -> the ladder's entries of the result"""
-        T, L, S = len(self.terrain_names), len(self.levels), len(self.scenarios)
-        c4, l4 = cells.reshape(T, L, S, -1), lcells.reshape(T, L, S, -1)
+        c4, l4 = self._cell_views(cells)[1], self._cell_views(lcells)[1]
         res["ladder"] = {t: {lv: {s[0]: dict(self._row(c4[ti, li, si]), **self._ladder_row(l4[ti, li, si])) for si, s in enumerate(self.scenarios)}
                              for li, lv in enumerate(self.levels)} for ti, t in enumerate(self.terrain_names)}
         first = self.scenarios[0][0]
@@ -1255,29 +1228,17 @@ class PolicyEvaluator:
     def _addon_tree(self, cells, row, pool=np.sum):
         """cells: an add-on's reduce table per cell of the active mode;  pool(a, axis): stacked rows -> the row of their union (a sum in fp64);  row: such a row -> its figures.
         -> ({"overall", "groups" and the mode's own keys: `row` of every partition the mode reports}, what a cell is: its axes' names)"""
-        T, S = len(self.terrain_names), len(self.scenarios)
-        P = len(self.perturbations or self.sensors or [None])
-        if self.ladder:
-            L = len(self.levels)
-            g4 = cells.reshape(T, L, S, -1)
-            table = pool(g4, 1).reshape(T * S, -1)
-        else:
-            g3 = cells.reshape(T * S, P, -1)
-            table = pool(g3, 1)
+        T, S, key, names = self.T, self.S, self.axis_key, self.axis_names
+        table, view = self._cell_views(cells, pool)
         tree = {"overall": row(pool(table, 0)), "groups": {t: {s[0]: row(table[ti * S + si]) for si, s in enumerate(self.scenarios)} for ti, t in enumerate(self.terrain_names)}}
-        axes = ["terrain", "scenario"]
-        if self.perturbations is not None or self.sensors is not None:
-            names = [p[0] for p in (self.perturbations or self.sensors)]
-            tree["cells"] = {t: {s[0]: {n: row(g3[ti * S + si, pi]) for pi, n in enumerate(names)} for si, s in enumerate(self.scenarios)} for ti, t in enumerate(self.terrain_names)}
-            tree["perturbations" if self.perturbations is not None else "sensors"] = {n: row(pool(g3[:, pi], 0)) for pi, n in enumerate(names)}
-            axes.append("perturbation" if self.perturbations is not None else "sensor")
-        if self.ladder:
-            tree["ladder"] = {t: {lv: {s[0]: row(g4[ti, li, si]) for si, s in enumerate(self.scenarios)} for li, lv in enumerate(self.levels)} for ti, t in enumerate(self.terrain_names)}
-            axes = ["terrain", "level", "scenario"]
-        if self.maneuvers is not None:          # (a "scenario" is a maneuver there)
-            tree["maneuvers"] = {s[0]: row(pool(table.reshape(T, S, -1)[:, si], 0)) for si, s in enumerate(self.scenarios)}
-            axes = ["terrain", "maneuver"]
-        return tree, axes
+        if key in ("perturbations", "sensors"):
+            tree["cells"] = {t: {s[0]: {n: row(view[ti * S + si, pi]) for pi, n in enumerate(names)} for si, s in enumerate(self.scenarios)} for ti, t in enumerate(self.terrain_names)}
+            tree[key] = {n: row(pool(view[:, pi], 0)) for pi, n in enumerate(names)}
+        elif key == "ladder":
+            tree["ladder"] = {t: {lv: {s[0]: row(view[ti, li, si]) for si, s in enumerate(self.scenarios)} for li, lv in enumerate(names)} for ti, t in enumerate(self.terrain_names)}
+        elif key == "maneuvers":          # (a "scenario" is a maneuver there)
+            tree["maneuvers"] = {n: row(pool(table.reshape(T, S, -1)[:, si], 0)) for si, n in enumerate(names)}
+        return tree, list(self.cell_axes)
 
     def _gait_results(self, res, gcells):
         """gcells: go2nn_gait_reduce's table per cell of the active mode -> res["gait"]: the cells' rows summed in fp64 for every partition the mode reports"""
@@ -1321,55 +1282,45 @@ class PolicyEvaluator:
 
     def _bootstrap_results(self, res, bcells):
         """bcells: go2nn_eval_bootstrap's table [B, cells, 12] -> "ci" in every leaf dict _row() made, and res["bootstrap"].  A partition's replicate rows are the sums of
-        its cells' replicate rows: _results' own reshapes and sums, one axis further in"""
+        its cells' replicate rows: _cell_views, which gives _results its reshapes and sums, one axis further in"""
         B, conf = bcells.shape[0], self.confidence
-        T, S, G, P = len(self.terrain_names), len(self.scenarios), len(self.groups), len(self.perturbations or self.sensors or [None])
+        T, S, key, names = self.T, self.S, self.axis_key, self.axis_names
         ci = lambda rows: intervals(rows, conf)
-        if self.ladder:
-            c5 = bcells.reshape(B, T, len(self.levels), S, -1)
-            table = c5.sum(2).reshape(B, G, -1)
-        else:
-            c4 = bcells.reshape(B, G, P, -1)
-            table = c4.sum(2)
+        table, view = self._cell_views(bcells)
         overall = table.sum(1)
         res["overall"]["ci"] = ci(overall)
         for ti, t in enumerate(self.terrain_names):
             for si, s in enumerate(self.scenarios):
                 res["groups"][t][s[0]]["ci"] = ci(table[:, ti * S + si])
-        if self.perturbations is not None or self.sensors is not None:
-            axis = "perturbations" if self.perturbations is not None else "sensors"
-            for pi, (n, _) in enumerate(self.perturbations or self.sensors):
-                res[axis][n]["ci"] = ci(c4[:, :, pi].sum(1))
+        if key in ("perturbations", "sensors"):
+            for pi, n in enumerate(names):
+                res[key][n]["ci"] = ci(view[:, :, pi].sum(1))
                 for ti, t in enumerate(self.terrain_names):
                     for si, s in enumerate(self.scenarios):
-                        res["cells"][t][s[0]][n]["ci"] = ci(c4[:, ti * S + si, pi])
-        if self.ladder:
+                        res["cells"][t][s[0]][n]["ci"] = ci(view[:, ti * S + si, pi])
+        elif key == "ladder":
             for ti, t in enumerate(self.terrain_names):
-                for li, lv in enumerate(self.levels):
+                for li, lv in enumerate(names):
                     for si, s in enumerate(self.scenarios):
-                        res["ladder"][t][lv][s[0]]["ci"] = ci(c5[:, ti, li, si])
-        if self.maneuvers is not None:          # (a "scenario" is a maneuver there)
+                        res["ladder"][t][lv][s[0]]["ci"] = ci(view[:, ti, li, si])
+        elif key == "maneuvers":          # (a "scenario" is a maneuver there)
             t3 = table.reshape(B, T, S, -1)
-            for mi, m in enumerate(self.maneuvers):
-                res["maneuvers"][m[0]]["ci"] = ci(t3[:, :, mi].sum(1))
+            for mi, n in enumerate(names):
+                res["maneuvers"][n]["ci"] = ci(t3[:, :, mi].sum(1))
         res["bootstrap"] = {"replicates": B, "seed": self.bootstrap_seed, "confidence": conf, "table": bcells, "overall": overall}
 
     def _results(self, cells, rcells=None, lcells=None, mcells=None):
         """cells: the eval reduce table per (terrain, scenario, perturbation) cell; rcells: the robust one (None without perturbations: a cell is a group then);
         lcells: the ladder's (None without the ladder), cells being per (terrain, level, scenario) then;  mcells: the maneuvers' (None without maneuvers), per
         (terrain, maneuver) cell = group"""
-        S, P = len(self.scenarios), len(self.perturbations or self.sensors or [None])
-        if lcells is not None:
-            table = cells.reshape(len(self.terrain_names), len(self.levels), S, -1).sum(1).reshape(len(self.groups), -1)
-        else:
-            table = cells.reshape(len(self.groups), P, -1).sum(1)          # P = 1: the cells' rows themselves
+        S = self.S
+        table, c3 = self._cell_views(cells)          # (c3: the per-cell view [groups, P, cols] of the modes without a ladder)
         groups = {t: {s[0]: self._row(table[ti * S + si]) for si, s in enumerate(self.scenarios)} for ti, t in enumerate(self.terrain_names)}
         res = {"overall": self._row(table.sum(0)), "groups": groups, "terrain_names": list(self.terrain_names), "scenarios": [s[0] for s in self.scenarios],
                "steps": self.steps, "dt": self.dt, "mode": self.last_mode, "table": table}
         if rcells is not None:
             both = lambda e, r: dict(self._row(e), **self._robust_row(r))
-            names = [p[0] for p in self.perturbations]
-            c3, r3 = cells.reshape(len(self.groups), P, -1), rcells.reshape(len(self.groups), P, -1)
+            names, r3 = list(self.axis_names), self._cell_views(rcells)[1]
             res["cells"] = {t: {s[0]: {n: both(c3[ti * S + si, pi], r3[ti * S + si, pi]) for pi, n in enumerate(names)} for si, s in enumerate(self.scenarios)}
                             for ti, t in enumerate(self.terrain_names)}
             res["perturbations"] = {n: both(c3[:, pi].sum(0), r3[:, pi].sum(0)) for pi, n in enumerate(names)}
@@ -1377,8 +1328,7 @@ class PolicyEvaluator:
             res.update(perturbation_names=names, cell_table=cells, robust_table=rcells, push_steps=self.push_steps.tolist(),
                        push={"first": self.push_first, "period": self.push_period, "window": self.push_window, "hold": self.push_hold, "count": self.push_count})
         if self.sensors is not None:
-            names = [c[0] for c in self.sensors]
-            c3 = cells.reshape(len(self.groups), P, -1)
+            names = list(self.axis_names)
             res["cells"] = {t: {s[0]: {n: self._row(c3[ti * S + si, pi]) for pi, n in enumerate(names)} for si, s in enumerate(self.scenarios)}
                             for ti, t in enumerate(self.terrain_names)}
             res["sensors"] = {n: self._row(c3[:, pi].sum(0)) for pi, n in enumerate(names)}
@@ -1387,8 +1337,7 @@ class PolicyEvaluator:
         if lcells is not None:
             self._ladder_results(res, cells, lcells)
         if mcells is not None:
-            T, M = len(self.terrain_names), len(self.maneuvers)
-            names = [m[0] for m in self.maneuvers]
+            T, M, names = self.T, self.S, self.axis_names
             for ti, t in enumerate(self.terrain_names):
                 for mi, n in enumerate(names):
                     groups[t][n].update(self._maneuver_row(mcells[ti * M + mi]))

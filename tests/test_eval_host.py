@@ -1,5 +1,5 @@
 """The policy evaluator on the CPU: the host build of the go2nn_eval_* kernels (include/go2nn.h) against float64 restatements written here, PolicyEvaluator on the
-oracle + the host build, its isolation from a training run, and the runner hook / CLI."""
+oracle + the host build, the calls an evaluation makes by name and order in every mode, its isolation from a training run, and the runner hook / CLI."""
 import ctypes as C
 import math
 import os
@@ -271,6 +271,86 @@ def test_evaluator_groups_on_a_terrain_task(emu):
     assert (env.terrain_levels == 3).all()
     assert abs(float((env.root_states[:, :2] - env.env_origins[:, :2]).abs().max())) < 4.0
     assert all(d["n_envs"] > 0 and np.isfinite(d["lin_vel_err"]) for per in res["groups"].values() for d in per.values())
+    ev.close()
+
+
+class Recording:
+    """a library (the go2sim oracle or the go2nn host build) with the name of every call an evaluation's steps, begins and reduces are made of appended to one shared list"""
+    NAMES = ("go2sim_step", "go2nn_mirror_rows", "go2nn_trace_record", "go2nn_blackbox_record")
+    PREFIXES = ("go2nn_eval_", "go2nn_robust_", "go2nn_ladder_", "go2nn_maneuver_", "go2nn_sensor_", "go2nn_gait_", "go2nn_asym_")
+
+    def __init__(self, lib, log):
+        self._lib, self._log = lib, log
+
+    def __getattr__(self, name):
+        fn = getattr(self._lib, name)
+        if name not in self.NAMES and not name.startswith(self.PREFIXES):
+            return fn
+
+        def recorded(*a):
+            self._log.append(name)
+            return fn(*a)
+        return recorded
+
+
+ADDONS = dict(gait=True, asymmetry=True, record=1, blackbox=1, blackbox_seconds=0.1)
+ADDON_BEGINS, ADDON_REDUCES = ["go2nn_gait_begin", "go2nn_asym_begin"], ["go2nn_gait_reduce", "go2nn_asym_reduce"]
+ADDON_STEP = ["go2nn_gait_accumulate", "go2nn_asym_accumulate", "go2nn_trace_record", "go2nn_blackbox_record"]
+# name -> (task, the mode's options, its calls before the first step, ONE step, its calls after the last): the step sequences of utils/evaluator.py's docstring, written out.
+# Before the first step: the reset's zero-action go2sim_step [, the sensor's first frame], go2nn_eval_clear, the tables' begins;  after the last: go2nn_eval_reduce, the tables' reduces
+LAUNCH_ORDER = {
+    "bare": ("go2_flat", {}, ["go2sim_step", "go2nn_eval_clear"], ["go2sim_step", "go2nn_eval_accumulate"], ["go2nn_eval_reduce"]),
+    "plain": ("go2_flat", ADDONS,
+              ["go2sim_step", "go2nn_eval_clear"] + ADDON_BEGINS,
+              ["go2nn_mirror_rows", "go2sim_step", "go2nn_eval_accumulate"] + ADDON_STEP,
+              ["go2nn_eval_reduce"] + ADDON_REDUCES),
+    "perturbations": ("go2_flat", dict(ADDONS, perturbations=[["nominal", {}], ["push_front_0.5", {"dv": [0.5, 0.0, 0.0]}]], push_first_s=0.02, push_period_s=0.1, push_window_s=0.1,
+                                       recover_hold_s=0.04),
+                      ["go2sim_step", "go2nn_eval_clear", "go2nn_robust_begin"] + ADDON_BEGINS,
+                      ["go2nn_mirror_rows", "go2nn_robust_apply", "go2sim_step", "go2nn_eval_accumulate", "go2nn_robust_accumulate"] + ADDON_STEP,
+                      ["go2nn_eval_reduce", "go2nn_robust_reduce"] + ADDON_REDUCES),
+    "sensors": ("go2_flat", dict(ADDONS, sensors=[["nominal", {}], ["delay_1", {"delay": 1}]]),
+                ["go2sim_step", "go2nn_sensor_begin", "go2nn_sensor_apply", "go2nn_eval_clear"] + ADDON_BEGINS,
+                ["go2nn_mirror_rows", "go2sim_step", "go2nn_sensor_apply", "go2nn_eval_accumulate"] + ADDON_STEP,
+                ["go2nn_eval_reduce"] + ADDON_REDUCES),
+    "maneuvers": ("go2_flat", dict(ADDONS, maneuvers=[["start_1.0", [[0.0, 0.0, 0.0, 0.0], [0.04, 1.0, 0.0, 0.0]]], ["turn_flip", [[0.0, 0.0, 0.0, 1.0], [0.06, 0.0, 0.0, -1.0]]]],
+                                   maneuver_window_s=0.1, maneuver_hold_s=0.04),
+                  ["go2sim_step", "go2nn_eval_clear", "go2nn_maneuver_begin"] + ADDON_BEGINS,
+                  ["go2nn_mirror_rows", "go2nn_maneuver_apply", "go2sim_step", "go2nn_maneuver_accumulate", "go2nn_eval_accumulate"] + ADDON_STEP,
+                  ["go2nn_eval_reduce", "go2nn_maneuver_reduce"] + ADDON_REDUCES),
+    "ladder": ("go2", dict(ADDONS, ladder=True, ladder_levels=[0, 4], ladder_distance=0.1),
+               ["go2sim_step", "go2nn_eval_clear", "go2nn_ladder_begin"] + ADDON_BEGINS,
+               ["go2nn_mirror_rows", "go2sim_step", "go2nn_eval_accumulate", "go2nn_ladder_accumulate"] + ADDON_STEP,
+               ["go2nn_eval_reduce", "go2nn_ladder_reduce"] + ADDON_REDUCES),
+}
+
+
+@pytest.mark.parametrize("mode", list(LAUNCH_ORDER))
+def test_step_launch_order_of_every_mode(emu, mode):
+    """what an evaluation calls, by name and in order: the begins before the first step, the same sequence in every step (warm-up and counted; go2nn_eval_clear once between
+    them), the reduces after the last — for the plain evaluation with every add-on off and on, and for each extra axis next to every add-on"""
+    from go2_rl_gym_amd.utils.evaluator import PolicyEvaluator
+    task, over, before, step, after = LAUNCH_ORDER[mode]
+    if mode == "ladder":
+        from test_ladder_host import SCENARIOS
+        over = dict(over, ladder_scenarios=SCENARIOS)
+    log, ends = [], []
+    env_cfg, _ = task_registry.get_cfgs(task)
+    ev = PolicyEvaluator(env_cfg, dict(EVAL, num_envs=38, seconds=0.2, warmup_s=0.1, **over), task_class=task_registry.get_task_class(task), device="cpu",
+                         lib=Recording(load_oracle(), log), nn_lib=Recording(emu, log), step_callback=lambda ev, k, counted: ends.append((len(log), counted)))
+    del log[:]          # (what building the evaluator called: the specs' checks)
+    ev.evaluate(small_actor_critic())
+    W, S = ev.warmup_steps, ev.steps
+    assert (W, S) == (5, 10) and len(ends) == W + S and [c for _, c in ends] == [False] * W + [True] * S
+    assert log[:len(before)] == before
+    starts = [len(before)] + [e for e, _ in ends[:-1]]
+    slices = [log[a:b] for a, (b, _) in zip(starts, ends)]
+    assert slices[W][0] == "go2nn_eval_clear"          # the boundary: the warm-up's sums go, once
+    slices[W] = slices[W][1:]
+    assert slices[W] == step, (mode, slices[W])          # a counted step
+    assert all(s == step for s in slices), (mode, [s for s in slices if s != step][:1])
+    assert log[ends[-1][0]:] == after
+    assert not any(n.endswith("_begin") for s in slices for n in s) and not any(n.endswith("_reduce") for n in log[:ends[-1][0]])
     ev.close()
 
 

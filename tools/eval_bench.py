@@ -341,11 +341,11 @@ def main():
     dev_us, wall_us = timed(acc_fn, 200)
     out["accumulate_kernel"] = {"device_us_per_launch_back_to_back": dev_us, "host_us_per_call": wall_us}
     if a.robust:
-        rin = ev._robust_in()
+        robust, rin = next(t for t in ev.tables if t.name == "robust"), ev._robust_in()
 
         def pair():
-            ev._robust(ev.nn.go2nn_robust_apply, "go2nn_robust_apply", rin)
-            ev._robust(ev.nn.go2nn_robust_accumulate, "go2nn_robust_accumulate", rin)
+            ev._table_launch("apply", robust, rin)
+            ev._table_launch("accumulate", robust, rin)
         timed(pair, 20)
         dev_us, wall_us = timed(pair, 200)
         out["robust_apply_plus_accumulate"] = {"device_us_per_pair_back_to_back": dev_us, "host_us_per_pair": wall_us}
@@ -356,11 +356,11 @@ def main():
         dev_us, wall_us = timed(lad_fn, 200)
         out["ladder_accumulate_kernel"] = {"device_us_per_launch_back_to_back": dev_us, "host_us_per_call": wall_us}
     if a.maneuvers:
-        min_ = ev._maneuver_in()
+        maneuver, min_ = next(t for t in ev.tables if t.name == "maneuver"), ev._maneuver_in()
 
         def man_pair():
-            ev._maneuver(ev.nn.go2nn_maneuver_apply, "go2nn_maneuver_apply", min_)
-            ev._maneuver(ev.nn.go2nn_maneuver_accumulate, "go2nn_maneuver_accumulate", min_)
+            ev._table_launch("apply", maneuver, min_)
+            ev._table_launch("accumulate", maneuver, min_)
         timed(man_pair, 20)
         dev_us, wall_us = timed(man_pair, 200)
         out["maneuver_apply_plus_accumulate"] = {"device_us_per_pair_back_to_back": dev_us, "host_us_per_pair": wall_us}
