@@ -381,6 +381,9 @@ def bind(path):
     lib.go2nn_asym_reduce.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
     lib.go2nn_eval_bootstrap_check.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]          # (within ABI 7) the cells' member lists, in host memory
     lib.go2nn_eval_bootstrap.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p]
+    for fam in ("robust", "maneuver", "gait", "asym"):          # (within ABI 7) the same replicates of every scoring family's reduce table
+        getattr(lib, "go2nn_%s_bootstrap" % fam).argtypes = lib.go2nn_eval_bootstrap.argtypes
+    lib.go2nn_ladder_bootstrap.argtypes = lib.go2nn_eval_bootstrap.argtypes[:7] + [C.c_float, C.c_void_p, C.c_void_p]
     lib.go2nn_maneuver_check_specs.argtypes = [C.c_void_p, C.c_int32]
     lib.go2nn_maneuver_begin.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
     lib.go2nn_maneuver_apply.argtypes = [C.POINTER(Go2nnManeuverIn), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]

@@ -11,8 +11,9 @@
 //   eval_per_env(f, N)                       grid = ceil(N / 256), lane e calls f(e): eval_per_env_kernel<EvalAccumulate>, <LadderAccumulate>, ... in a kernel trace
 //   eval_table_begin(table, rows, N, start)  grid = ceil(rows N / 256), one float per lane: row 0 (a family's STEP row) = start, every other row = 0
 //   eval_reduce(term, group, N, G, cols)     grid = (G, cols), workgroup (g, c) writes out[g cols + c] = eval_group_sum of the Term at column c (eval_group_max for MAX_COL)
-//   eval_bootstrap<COLS>(term, cell_start, cell_envs, G, B, seed)   grid = (G, ceil(B / 256)), lane b writes replicate b of cell g: the Term's COLS columns summed over the
-//                                            cell's members redrawn with replacement (go2nn_bootstrap.h instantiates it for EvalTerm; any family's Term fits)
+//   eval_bootstrap<COLS, CHUNK, MAX_COL>(term, cell_start, cell_envs, G, B, seed)   grid = (G, ceil(B / 256), COLS / CHUNK), lane (g, b, z) writes window z of replicate
+//                                            b of cell g: the Term's columns summed (MAX_COL: the max) over the cell's members redrawn with replacement
+//                                            (go2nn_bootstrap.h instantiates it for every family's Term)
 // eval_field_fault is the one statement of what a Go2nnEvalField must satisfy; each family words its own messages around it.
 #ifndef GO2NN_EVAL_H
 #define GO2NN_EVAL_H
@@ -212,17 +213,42 @@ template <int MAX_COL = -1, class Term> static int eval_reduce(Term term, const 
 }
 
 // out[(b G + g) COLS + c] for every replicate b < B, cell g < G and column c < COLS: the sum of the Term at column c over n = cell_start[g + 1] - cell_start[g] members of the
-// cell drawn WITH replacement (a stratified bootstrap: every cell keeps its size), in fp64 in the order of the draws.  Draw k of (b, g) is member (x n) >> 32 of the cell's list
+// cell drawn WITH replacement (a stratified bootstrap: every cell keeps its size), in fp64 in the order of the draws; at c == MAX_COL (eval_reduce's: -1 = no such column) the
+// largest of the drawn members' terms instead (0 for an empty cell: the terms are >= 0).  Draw k of (b, g) is member (x n) >> 32 of the cell's list
 // cell_envs[cell_start[g] ...], x = word (k & 3) of philox4x32_10(b, g, k >> 2, 0, seed, EVAL_TAG_BOOTSTRAP): integers only, so the host loops, the lanes and a restatement in
-// Python integers pick the same members, and a replicate depends on (b, g, seed) but not on B.  grid = (G, ceil(B / 256)), lane b walks its cell's draws — one Philox block per
-// four, the words picked by the unrolled loop's constant index, never by a dynamic one (that array would live in scratch) — and keeps the COLS sums in registers, which is why
-// COLS is a template argument and not one of the call; no LDS, no atomics.  n is uniform over a workgroup; the member loads are gathers from a table that fits the caches.
+// Python integers pick the same members, and a replicate depends on (b, g, seed) but not on B, COLS or the Term: replicate (b, g) of EVERY family's table redraws the same robots.
+// grid = (G, ceil(B / 256), COLS / CHUNK), lane (g, b, z) walks its cell's draws — one Philox block per four, the words picked by the unrolled loop's constant index, never
+// by a dynamic one (that array would live in scratch) — and keeps the sums of ITS column window [z CHUNK, z CHUNK + CHUNK) in registers, which is why COLS and CHUNK are template
+// arguments and not ones of the call; every z-slice recomputes the same draws.  No LDS, no atomics.  n is uniform over a workgroup; the member loads are gathers from a table
+// that fits the caches.  CHUNK == COLS (EvalTerm's twelve columns) is one window with constant column indices: the code and the bits of the launch before it had a window.
+//
+// THE WINDOW'S WIDTH.  Read from the gfx950 code object's notes (build.py kernel_resources; scratch 0 and LDS 0 in every row) and timed on an MI355X: device events around
+// 200 back-to-back launches, 1024 robots, B = 1000, at 6 / 42 / 294 cells (profiles/bootstrap_all_bench.json):
+//   Term, COLS      CHUNK  windows  VGPRs  SGPRs   us per launch at 6 / 42 / 294 cells
+//   EvalTerm 12        12        1     64     41   131 /  22 /  17     (64 / 41 before the launch had a window: the same code)
+//   RobustTerm 7        7        1     32     38    70 /  13 /  13
+//   ManeuverTerm 9      9        1     36     38    94 /  16 /  16
+//   LadderTerm 6        6        1     40     46    68 /  12 /  10
+//   GaitTerm 55        55        1    130     45   934 / 143 /  94
+//   GaitTerm 55        28        2     74    106   561 /  92 /  87
+//   GaitTerm 55        19        3     56     91   401 /  67 /  77
+//   GaitTerm 55        11        5     56     69   132 /  74 /  68     kept: a lane's serial walk is what a launch at few cells waits for, and five windows cut it to a fifth
+//   AsymTerm 25        25        1    108     38   180 /  35 /  33     kept
+//   AsymTerm 25        13        2     81    106   573 /  89 /  48
+//   AsymTerm 25         9        3     73    106   380 /  63 /  44
+//   AsymTerm 25         5        5     57    106   176 /  46 /  42
+// (The widths 28, 19, 13 and 9 do not divide their column counts; they were timed with a guarded, narrower last window, a path the launch no longer has: CHUNK divides COLS.)
+// A window makes the column a run-time value: GaitTerm only turns it into a row index, AsymTerm branches on it into two fp64 divisions per imbalance column, which every
+// lane of a windowed launch then pays for on every column — so the 25 columns stay in one window (108 VGPRs, still 4 waves per SIMD) and the 55 are split.
 #define EVAL_TAG_BOOTSTRAP 7u          // the key's second word; 1 .. 6 are the sensor kernels' (go2nn_sensor.h, go2nn_sensor_rand.h)
-template <int COLS, class Term> EVAL_FN void eval_bootstrap_replicate(Term term, const int32_t* cell_start, const int32_t* cell_envs, int G, int g, int b, uint32_t seed, double* out) {
+template <int COLS, int CHUNK, int MAX_COL, class Term>
+EVAL_FN void eval_bootstrap_replicate(Term term, const int32_t* cell_start, const int32_t* cell_envs, int G, int g, int b, int z, uint32_t seed, double* out) {
+  static_assert(CHUNK >= 1 && COLS % CHUNK == 0, "the windows are equally wide: CHUNK divides COLS");
   const int s0 = cell_start[g], n = cell_start[g + 1] - s0;
-  double sum[COLS];
+  const int c0 = CHUNK == COLS ? 0 : z * CHUNK;          // (one window: the column indices below are constants)
+  double sum[CHUNK];
 #pragma unroll
-  for (int c = 0; c < COLS; ++c) sum[c] = 0.0;
+  for (int j = 0; j < CHUNK; ++j) sum[j] = 0.0;
   for (int k0 = 0; k0 < n; k0 += 4) {
     uint32_t w[4];
     philox4x32_10((uint32_t)b, (uint32_t)g, (uint32_t)(k0 >> 2), 0u, seed, EVAL_TAG_BOOTSTRAP, w);
@@ -231,31 +257,37 @@ template <int COLS, class Term> EVAL_FN void eval_bootstrap_replicate(Term term,
       if (k0 + q < n) {
         const int e = cell_envs[s0 + (int)(((uint64_t)w[q] * (uint64_t)(uint32_t)n) >> 32)];
 #pragma unroll
-        for (int c = 0; c < COLS; ++c) {
-          term.c = c;
-          sum[c] += term(e);
+        for (int j = 0; j < CHUNK; ++j) {
+          term.c = c0 + j;
+          const double v = term(e);
+          if (MAX_COL >= 0 && term.c == MAX_COL) sum[j] = fmax(sum[j], v);
+          else sum[j] += v;
         }
       }
     }
   }
   double* row = out + ((long long)b * G + g) * COLS;
 #pragma unroll
-  for (int c = 0; c < COLS; ++c) row[c] = sum[c];
+  for (int j = 0; j < CHUNK; ++j) row[c0 + j] = sum[j];
 }
 #ifndef GO2_EMU
-template <int COLS, class Term> __global__ void __launch_bounds__(EVAL_THREADS) eval_bootstrap_kernel(const Term term, const int32_t* cell_start, const int32_t* cell_envs, int G, int B, uint32_t seed, double* out) {
+template <int COLS, int CHUNK, int MAX_COL, class Term>
+__global__ void __launch_bounds__(EVAL_THREADS) eval_bootstrap_kernel(const Term term, const int32_t* cell_start, const int32_t* cell_envs, int G, int B, uint32_t seed, double* out) {
   const int b = blockIdx.y * EVAL_THREADS + threadIdx.x;
-  if (b < B) eval_bootstrap_replicate<COLS>(term, cell_start, cell_envs, G, (int)blockIdx.x, b, seed, out);
+  if (b < B) eval_bootstrap_replicate<COLS, CHUNK, MAX_COL>(term, cell_start, cell_envs, G, (int)blockIdx.x, b, (int)blockIdx.z, seed, out);
 }
 #endif
-template <int COLS, class Term> static int eval_bootstrap(const Term& term, const int32_t* cell_start, const int32_t* cell_envs, int G, int B, uint32_t seed, double* out, void* stream) {
+template <int COLS, int CHUNK = COLS, int MAX_COL = -1, class Term>
+static int eval_bootstrap(const Term& term, const int32_t* cell_start, const int32_t* cell_envs, int G, int B, uint32_t seed, double* out, void* stream) {
+  constexpr int Z = COLS / CHUNK;
 #ifdef GO2_EMU
   (void)stream;
   for (int b = 0; b < B; ++b)
-    for (int g = 0; g < G; ++g) eval_bootstrap_replicate<COLS>(term, cell_start, cell_envs, G, g, b, seed, out);
+    for (int g = 0; g < G; ++g)
+      for (int z = 0; z < Z; ++z) eval_bootstrap_replicate<COLS, CHUNK, MAX_COL>(term, cell_start, cell_envs, G, g, b, z, seed, out);
 #else
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(eval_bootstrap_kernel<COLS, Term>), dim3((unsigned)G, (unsigned)((B + EVAL_THREADS - 1) / EVAL_THREADS)), dim3(EVAL_THREADS), 0, (hipStream_t)stream,
-                     term, cell_start, cell_envs, G, B, seed, out);
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(eval_bootstrap_kernel<COLS, CHUNK, MAX_COL, Term>), dim3((unsigned)G, (unsigned)((B + EVAL_THREADS - 1) / EVAL_THREADS), (unsigned)Z), dim3(EVAL_THREADS), 0,
+                     (hipStream_t)stream, term, cell_start, cell_envs, G, B, seed, out);
   HIPCHK(hipGetLastError());
 #endif
   return 0;

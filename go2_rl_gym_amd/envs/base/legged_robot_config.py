@@ -316,6 +316,7 @@ class LeggedRobotCfgPPO(BaseConfig):
         bootstrap_seed = 2718   # the Philox seed of the redraws: the same seed, the same robots in replicate b of every evaluation
         confidence = 0.95       # the intervals' level: the (1 - confidence) / 2 and (1 + confidence) / 2 quantiles of the replicates
         bootstrap_max_bytes = 256 << 20  # the [B, cells, 12] fp64 table of replicates is refused above this
+        bootstrap_all = False   # (--ci_all) with bootstrap > 0: one more launch per active scoring family (go2nn_<family>_bootstrap) redraws the SAME robots on the family's table, and the modes' own figures, the gait and the asymmetry sections get their intervals too; bootstrap_max_bytes then caps the sum of all tables; ignored with bootstrap = 0
 
 
 class LeggedRobotCfgCTS(BaseConfig):
@@ -411,6 +412,7 @@ class LeggedRobotCfgCTS(BaseConfig):
         bootstrap_seed = 2718   # the Philox seed of the redraws: the same seed, the same robots in replicate b of every evaluation
         confidence = 0.95       # the intervals' level: the (1 - confidence) / 2 and (1 + confidence) / 2 quantiles of the replicates
         bootstrap_max_bytes = 256 << 20  # the [B, cells, 12] fp64 table of replicates is refused above this
+        bootstrap_all = False   # (--ci_all) with bootstrap > 0: one more launch per active scoring family (go2nn_<family>_bootstrap) redraws the SAME robots on the family's table, and the modes' own figures, the gait and the asymmetry sections get their intervals too; bootstrap_max_bytes then caps the sum of all tables; ignored with bootstrap = 0
 
 
 class LeggedRobotCfgMoECTS(LeggedRobotCfgCTS):

@@ -14,7 +14,7 @@ switch_falls, settle_time_s, window_lin_vel_err, window_ang_vel_err (lower is be
 the scenarios; the overall figures are then means over the conditions' robots, so --all_checkpoints --sensors --metric lin_vel_err names the checkpoint that tracks best
 across all of them.
 --gait also scores how the robots walk (utils/evaluator.py GAIT_KEYS), next to any of the modes above; --metric then also takes the pooled gait figures: slip_speed and
-touchdowns_per_s count as lower is better, trot_share and swing_clearance as higher is better, so --all_checkpoints --gait --metric slip_speed names the checkpoint whose
+touchdowns_per_s count as lower is better, trot_share and swing_clearance as higher is better (a per-foot figure, slip_speed/FL, ranks as its pooled one), so --all_checkpoints --gait --metric slip_speed names the checkpoint whose
 feet drag least.
 --asymmetry also scores left-right asymmetry (utils/evaluator.py ASYM_KEYS), next to any of the modes above; --metric then also takes equivariance_rmse (and /hip, /thigh,
 /calf), equivariance_rel, equivariance_max and imbalance/action, /torque, /power, /contact — all lower is better —, so --all_checkpoints --asymmetry --metric
@@ -26,7 +26,12 @@ and writes those of N fallen robots per cell (default 2) to eval_results/falls_<
 the modes above; --metric must then be one of CI_KEYS.  After the best checkpoint is named as without it, every checkpoint is compared with the best one ON THE SAME
 RESAMPLINGS — an evaluation is deterministic per robot index, so the difference of the two metrics per resampling is a paired comparison —: the JSON line gains
 "comparison" (per checkpoint its value and interval, the difference to the best and that difference's interval) and "tied_with_best", the checkpoints whose paired interval
-contains 0; the same goes to eval_results/comparison_<metric>.yaml in the run's directory."""
+contains 0; the same goes to eval_results/comparison_<metric>.yaml in the run's directory (a "/" in the metric's name written as "_").
+--ci_all (with --ci [B]; alone it means --ci 1000) also resamples the modes' own figures and the gait and asymmetry sections, on the same draws; --metric may then be any
+figure that has replicates (res["bootstrap"]["metrics"]: push_falls, settle_time_s, mean_level_cleared, slip_speed, equivariance_rmse, imbalance/torque, ...), so
+--all_checkpoints --asymmetry --ci --ci_all --metric equivariance_rmse says whether two checkpoints' equivariance errors can be told apart.  Refused before anything runs:
+left_share/* (no better direction), equivariance_max (a bootstrap of a maximum is not one), the integer counts pushes, switches and n_envs, and a figure whose flag is
+not on (push_falls without --robust)."""
 import json
 import math
 import os
@@ -35,11 +40,22 @@ from pathlib import Path
 
 from go2_rl_gym_amd.envs import *  # noqa: F401,F403
 from go2_rl_gym_amd.utils import get_args
-from go2_rl_gym_amd.utils.evaluator import CI_KEYS, PolicyEvaluator, compare, format_table, interval, replicate_metrics, results_dict
+from go2_rl_gym_amd.utils.evaluator import (ASYM_KEYS, CI_KEYS, DIAGONAL_PAIRS, GAIT_FOOT_KEYS, GAIT_KEYS, MANEUVER_KEYS, ROBUST_KEYS, PolicyEvaluator, compare, format_table, interval,
+                                            replicate_metrics, results_dict)
 from go2_rl_gym_amd.utils.helpers import _checkpoint_number, get_load_path
 from go2_rl_gym_amd.utils.task_registry import ROOT_DIR, task_registry
 
 HIGHER_IS_BETTER = ("survival", "speed_along_cmd", "recovered", "mean_level_cleared", "cleared", "settled", "trot_share", "swing_clearance")
+FEET = tuple(leg for pair in DIAGONAL_PAIRS for leg in pair)          # the feet the gait scorer names its per-foot keys after ("<key>/<foot>")
+
+
+def higher_is_better(metric):
+    """a per-foot gait figure ("swing_clearance/FL") has the direction of its pooled figure"""
+    return metric in HIGHER_IS_BETTER or (is_foot_metric(metric) and metric.split("/", 1)[0] in HIGHER_IS_BETTER)
+
+
+def is_foot_metric(metric):
+    return "/" in metric and metric.split("/", 1)[0] in GAIT_FOOT_KEYS and metric.split("/", 1)[1] in FEET
 
 
 def _own_flags(argv):
@@ -65,18 +81,42 @@ def check_metric(metric):
                          % (metric, metric.split("/", 1)[1]))
 
 
+def check_ci_metric(metric, args):
+    """--ci [--ci_all] --metric: refused before anything runs unless the metric will have replicates — with a message that says why"""
+    if metric in CI_KEYS:
+        return
+    if not getattr(args, "ci_all", False):
+        raise ValueError("--ci --metric %s: the bootstrap resamples the figures %s; the modes' own figures, the gait and the asymmetry sections have no replicates "
+                         "without --ci_all" % (metric, ", ".join(CI_KEYS)))
+    if metric in ("pushes", "switches", "n_envs"):
+        raise ValueError("--ci_all --metric %s: an integer count of the design, the same in every resampling of a cell's robots up to which robots were drawn; it gets no "
+                         "interval and ranks nothing" % metric)
+    if metric == "equivariance_max":
+        raise ValueError("--ci_all --metric equivariance_max: a maximum over the robots has no bootstrap interval (a resampling can only lose the largest value); rank by "
+                         "equivariance_rmse")
+    flags = [f for f, keys in (("robust", ROBUST_KEYS), ("maneuvers", MANEUVER_KEYS), ("ladder", ("cleared", "mean_level_cleared")), ("gait", GAIT_KEYS), ("asymmetry", ASYM_KEYS))
+             if metric in keys or (f == "gait" and is_foot_metric(metric))]
+    if not flags:
+        raise ValueError("--ci_all --metric %s: not a figure the evaluator resamples (utils/evaluator.py CI_KEYS, ROBUST_KEYS, MANEUVER_KEYS, cleared, mean_level_cleared, "
+                         "GAIT_KEYS and <GAIT_FOOT_KEYS>/<%s>, ASYM_KEYS)" % (metric, "|".join(FEET)))
+    if not any(getattr(args, f, False) for f in flags):
+        raise ValueError("--ci_all --metric %s: the figure is scored under %s, which is not on" % (metric, " or ".join("--" + f for f in flags)))
+
+
 def metric_value(row, metric):
-    """a checkpoint row's overall `metric`: the scores' own, or with --asymmetry one of the asymmetry figures (kept in their own section: they leave `overall` alone)"""
-    if metric in row["overall"]:
-        return row["overall"][metric]
-    return row["asymmetry"]["overall"][metric] if "asymmetry" in row else row["overall"][metric]
+    """a checkpoint row's overall `metric`: the scores' own; with --gait a per-foot gait figure (the pooled ones are in `overall`, the per-foot ones in the gait section's);
+    with --asymmetry one of the asymmetry figures (kept in their own section: they leave `overall` alone)"""
+    for section in ("gait", "asymmetry"):
+        if metric not in row["overall"] and metric in row.get(section, {}).get("overall", {}):
+            return row[section]["overall"][metric]
+    return row["overall"][metric]
 
 
 def best_checkpoint(rows, metric):
     """the row with the best overall `metric`.  A figure that does not exist (NaN: settle_time_s without a settled switch, recovery_time_s without a recovered push) ranks
     last, whatever the order of the rows"""
     check_metric(metric)
-    higher = metric in HIGHER_IS_BETTER
+    higher = higher_is_better(metric)
     worst = float("-inf") if higher else float("inf")
     value = lambda r: metric_value(r, metric)
     rank = lambda r: worst if isinstance(value(r), float) and math.isnan(value(r)) else value(r)
@@ -110,9 +150,8 @@ def evaluate(argv=None, log_root="default", env_kwargs=None, evaluator_kwargs=No
     own, rest = _own_flags(list(sys.argv[1:] if argv is None else argv))
     check_metric(own["metric"])
     args = get_args(rest)
-    if args.ci is not None and own["metric"] not in CI_KEYS:          # refused before anything runs: the comparison needs the metric's replicates
-        raise ValueError("--ci --metric %s: the bootstrap resamples the figures %s; the modes' own figures, the gait and the asymmetry sections have no replicates"
-                         % (own["metric"], ", ".join(CI_KEYS)))
+    if args.ci is not None:          # refused before anything runs: the comparison needs the metric's replicates
+        check_ci_metric(own["metric"], args)
     env_cfg, train_cfg = task_registry.get_cfgs(name=args.task)
     env_cfg.env.num_envs = min(env_cfg.env.num_envs, 64)          # the runner's own env only carries the model's shapes here; the evaluator brings its own simulator
     env_cfg.env.test = True
@@ -137,6 +176,8 @@ def evaluate(argv=None, log_root="default", env_kwargs=None, evaluator_kwargs=No
         rows.append({"checkpoint": p.name, "overall": res["overall"], "groups": res["groups"]})
         if res.get("bootstrap") is not None and own["metric"] in CI_KEYS:          # the [B] replicates of the overall metric: what the paired comparison below reads
             reps[p.name] = replicate_metrics(res["bootstrap"]["overall"])[own["metric"]]
+        elif res.get("bootstrap") is not None and "metrics" in res["bootstrap"]:          # (--ci_all: a family's figure; check_ci_metric let only those through)
+            reps[p.name] = res["bootstrap"]["metrics"][own["metric"]]
         if res.get("perturbations") is not None:
             rows[-1]["perturbations"] = res["perturbations"]
         if res.get("maneuvers") is not None:
@@ -170,7 +211,7 @@ def evaluate(argv=None, log_root="default", env_kwargs=None, evaluator_kwargs=No
         import yaml
         out["comparison"], out["tied_with_best"] = comparison(rows, reps, best, metric, ev.confidence)
         print(format_comparison(out["comparison"]))
-        path = os.path.join(str(paths[0].parent), "eval_results", "comparison_%s.yaml" % metric)
+        path = os.path.join(str(paths[0].parent), "eval_results", "comparison_%s.yaml" % metric.replace("/", "_"))
         os.makedirs(os.path.dirname(path), exist_ok=True)
         with open(path, "w") as f:
             yaml.safe_dump({"best": best["checkpoint"], "comparison": out["comparison"], "tied_with_best": out["tied_with_best"]}, f)

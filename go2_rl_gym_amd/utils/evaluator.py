@@ -94,7 +94,13 @@ row per replicate)}.  A partition's replicate rows are the sums of its cells' (_
 dict _row() makes — "overall", "groups", "cells", "perturbations", "sensors", "maneuvers", the ladder's per-level leaves — gains "ci": {metric: [lo, hi]} for CI_KEYS, the
 (1 - confidence) / 2 and (1 + confidence) / 2 quantiles ([nan, nan] where every replicate is NaN).  The cells are strata: every replicate keeps the design's robots per
 cell.  An evaluation is deterministic per robot index, so the same replicates of two checkpoints' evaluations are PAIRED: compare() below.  The modes' own figures
-(push_falls, settle_time_s, cleared, ...) and the gait and asymmetry sections get NO interval.  An add-on like `gait`: it reads only the accumulators and the cell
+(push_falls, settle_time_s, cleared, ...) and the gait and asymmetry sections get NO interval unless `evaluation.bootstrap_all` (--ci_all) is on: then one more launch per
+active scoring family (go2nn_<family>_bootstrap, after the family's reduce, outside any captured graph) redraws the SAME robots — the draws depend on (b, g, k, seed) only —
+on the family's table, res["bootstrap"] gains "tables": {family: [B, cells, cols]} and "metrics": {figure: float64 [B]} (the overall replicates of every figure that has an
+interval, the asymmetry's among them), and every leaf that reports a family's figures gains them in its "ci" — the leaves of res["gait"] and res["asymmetry"] too, the gait's
+with the per-foot keys; res["ladder_summary"][t] gains "ci" for level_cleared and mean_level_cleared from the replicate `cleared` curves.  The replicate figures are the row
+functions' vectorised twins (robust_replicates, ... below: the same IEEE operations on every replicate row and leaf at once); integer counts (pushes, switches, n_envs) and
+equivariance_max (a bootstrap of a maximum is not one) get no interval; `bootstrap_max_bytes` then caps the sum of all tables.  An add-on like `gait`: it reads only the accumulators and the cell
 assignment and works next to every mode; the table is refused above `bootstrap_max_bytes`; with bootstrap = 0 nothing is loaded, allocated or launched.
 
 Isolated: nothing of the training env, the model, the optimizer or torch's generators is written; policy state the evaluation needs (the CTS observation history, the
@@ -148,6 +154,9 @@ DIAGONAL_PAIRS = (("FL", "RR"), ("FR", "RL"))
 ASYM_LOADS = ("action", "torque", "power", "contact")          # in the order of ASYM_PAIRS (act_sq, torque_sq, power, contact)
 ASYM_EQ_KEYS = ("equivariance_rmse", "equivariance_rmse/hip", "equivariance_rmse/thigh", "equivariance_rmse/calf", "equivariance_rel", "equivariance_max")
 ASYM_KEYS = ASYM_EQ_KEYS + ("sym_steps_share",) + tuple("left_share/" + x for x in ASYM_LOADS) + tuple("imbalance/" + x for x in ASYM_LOADS)
+# with `bootstrap_all`: what the printed table's interval block shows of each family
+BOOTSTRAP_HEADLINES = (("robust", ("push_falls", "recovered", "recovery_time_s")), ("maneuver", ("switch_falls", "settled", "settle_time_s")),
+                       ("ladder", ("cleared", "mean_level_cleared")), ("gait", ("slip_speed", "trot_share", "swing_clearance")), ("asym", ("equivariance_rmse", "imbalance/torque")))
 MAX_CHUNK = 50
 # The accumulate kernel runs AFTER the env step, when the simulator has already rolled its action history (last_actions = this step's actions): the previous step's
 # actions — the kernel's `last_actions` input — are then in the simulator's last_last_actions buffer.
@@ -208,6 +217,89 @@ def intervals(rows, confidence):
         return {m: interval(reps[m], confidence) for m in CI_KEYS}
     q = np.quantile(mat, [(1.0 - confidence) / 2.0, (1.0 + confidence) / 2.0], axis=0)
     return {m: [float(q[0, i]), float(q[1, i])] for i, m in enumerate(CI_KEYS)}
+
+
+# ---- `evaluation.bootstrap_all`: the row functions' twins.  rows: float64 [..., cols], a family's reduce row per replicate (and per leaf) -> {key: float64 [...]}: the
+# arithmetic of PolicyEvaluator._<family>_row on every row at once — the same IEEE operations in the same order, so replicate b's figure is the row function of replicate
+# row b bit for bit —, NaN where the row function reports NaN.  Integer counts (pushes, switches, n_envs) and equivariance_max (a bootstrap of a maximum is not one) get none.
+def _per(x, d):
+    """x / d where d > 0, NaN elsewhere: the row functions' `x / n if n > 0 else nan`"""
+    x, d = np.broadcast_arrays(np.asarray(x, np.float64), np.asarray(d, np.float64))
+    return np.divide(x, d, out=np.full(x.shape, np.nan), where=d > 0)
+
+
+def robust_replicates(rows, dt):
+    r = np.asarray(rows, np.float64)
+    pushes, rec = r[..., 0], r[..., 2]
+    return {"push_falls": _per(r[..., 1], pushes), "recovered": _per(r[..., 2], pushes), "recovery_time_s": _per(r[..., 3], rec) * dt,
+            "peak_lin_vel_err": _per(r[..., 4], pushes), "peak_tilt": _per(r[..., 5], pushes)}
+
+
+def maneuver_replicates(rows, dt):
+    r = np.asarray(rows, np.float64)
+    v = {k: r[..., i] for i, k in enumerate(MANEUVER_OUT)}
+    sw, settled, steps = v["switches"], v["settled"], v["win_steps"]
+    return {"switch_falls": _per(v["switch_falls"], sw), "settled": _per(settled, sw), "settle_time_s": _per(v["settle_steps"], settled) * dt,
+            "window_lin_vel_err": _per(v["win_lin_err"], steps), "window_ang_vel_err": _per(v["win_ang_err"], steps), "peak_tilt": _per(v["peak_tilt_sum"], sw)}
+
+
+def ladder_replicates(rows, dt):
+    r = np.asarray(rows, np.float64)
+    v = {k: r[..., i] for i, k in enumerate(LADDER_OUT)}
+    return {"cleared": _per(v["cleared"], v["n"]), "fell": _per(v["fell"], v["n"]), "timed_out": _per(v["timed_out"], v["n"]),
+            "time_to_clear_s": _per(v["clear_steps"], v["cleared"]) * dt, "progress": _per(v["progress"], v["n"])}
+
+
+def gait_replicates(rows, dt, foot_names):
+    r = np.asarray(rows, np.float64)
+    K, first = len(GAIT_OUT_FOOT), gait_out_col(0, GAIT_OUT_FOOT[0])
+    feet = [r[..., first + f * K:first + (f + 1) * K] for f in range(4)]
+    d = {}
+    for name, row in [("", ((feet[0] + feet[1]) + feet[2]) + feet[3])] + [("/" + n, feet[f]) for f, n in enumerate(foot_names)]:          # (feet.sum(0): in the feet's order)
+        v = {k: row[..., i] for i, k in enumerate(GAIT_OUT_FOOT)}
+        d["duty_factor" + name] = _per(v["contact"], v["used"])
+        d["stride_frequency" + name] = _per(v["strides"], v["stride_steps"] * dt)
+        d["stance_time" + name] = _per(v["stance_steps"] * dt, v["stances"])
+        d["swing_time" + name] = _per(v["swing_steps"] * dt, v["swings"])
+        d["slip_speed" + name] = _per(v["slip_sum"], v["contact"])
+        d["swing_height" + name] = _per(v["height_sum"], v["swings"])
+        d["swing_clearance" + name] = _per(v["clearance_sum"], v["swings"])
+        d["touchdowns_per_s" + name] = _per(v["touchdowns"], v["used"] * dt)
+    frames, support = feet[0][..., 0], r[..., GO2NN_GAIT_OUT_SUPPORT0:GO2NN_GAIT_OUT_SUPPORT0 + 5]
+    d["trot_share"], d["flight_share"] = _per(r[..., GO2NN_GAIT_OUT_DIAGONAL], frames), _per(support[..., 0], frames)
+    weighted = np.zeros(frames.shape)          # np.dot(arange(5), support): whole numbers far below 2^53, exact in any order
+    for k in range(5):
+        weighted = weighted + float(k) * support[..., k]
+    d["mean_feet_in_contact"] = _per(weighted, frames)
+    return d
+
+
+def asym_replicates(rows):
+    r = np.asarray(rows, np.float64)
+    v = {k: r[..., i] for i, k in enumerate(ASYM_OUT)}
+    steps = v["eq_steps"]
+    d = {"equivariance_rmse": np.sqrt(_per(v["eq_sq"], 12.0 * steps))}
+    for kind in ("hip", "thigh", "calf"):
+        d["equivariance_rmse/" + kind] = np.sqrt(_per(v["eq_sq_" + kind], 4.0 * steps))
+    d["equivariance_rel"] = np.sqrt(_per(v["eq_sq"], v["act_sq"]))
+    d["sym_steps_share"] = _per(v["sym_steps"], steps)
+    for x, p in zip(ASYM_LOADS, ASYM_PAIRS):
+        d["left_share/" + x] = _per(v[p + "_l"], v[p + "_l"] + v[p + "_r"])
+    for x, p in zip(ASYM_LOADS, ASYM_PAIRS):
+        d["imbalance/" + x] = _per(v[p + "_imb"], v[p + "_imb_n"])
+    return d
+
+
+def interval_columns(mat, confidence):
+    """mat: float64 [B, M], M figures' replicates -> (lo [M], hi [M]): interval() of every column — the columns without a NaN in one quantile call, the others one by one"""
+    mat = np.asarray(mat, np.float64)
+    lo, hi = np.full(mat.shape[1], np.nan), np.full(mat.shape[1], np.nan)
+    clean = ~np.isnan(mat).any(0)
+    if clean.any() and mat.shape[0] > 0:
+        lo[clean], hi[clean] = np.quantile(mat[:, clean], [(1.0 - confidence) / 2.0, (1.0 + confidence) / 2.0], axis=0)
+    for j in np.nonzero(~clean)[0]:
+        lo[j], hi[j] = interval(mat[:, j], confidence)
+    return lo, hi
 
 
 def compare(reps_a, reps_b, confidence=0.95):
@@ -886,6 +978,14 @@ class PolicyEvaluator:
             raise ValueError("evaluation.confidence: an interval level inside (0, 1), got %r" % (_get(self.ev, "confidence"),))
         self.bootstrap_seed = int(_get(self.ev, "bootstrap_seed", 2718)) & 0xFFFFFFFF
         need, cap = B * self.num_cells * cols * 8, int(_get(self.ev, "bootstrap_max_bytes", 256 << 20))
+        self.bootstrap_all = bool(_get(self.ev, "bootstrap_all", False))
+        if self.bootstrap_all:          # the cap holds the SUM of all tables; the refusal names each table's share, before anything is allocated
+            share = [("eval", cols)] + [(t.name, int(t.out.shape[1])) for t in self.tables]
+            total = sum(B * self.num_cells * c * 8 for _, c in share)
+            if total > cap or any(B * self.num_cells * c >= 2 ** 31 for _, c in share):
+                raise ValueError("evaluation.bootstrap_all: %d replicates x %d cells x 8 bytes x (%s) = %d bytes, more than evaluation.bootstrap_max_bytes = %d (or a table "
+                                 "of 2^31 values); lower evaluation.bootstrap" % (B, self.num_cells, " + ".join("%s: %d columns = %d bytes" % (n, c, B * self.num_cells * c * 8)
+                                                                                                               for n, c in share), total, cap))
         if need > cap or B * self.num_cells * cols >= 2 ** 31:
             raise ValueError("evaluation.bootstrap: %d replicates x %d cells x %d columns x 8 bytes = %d bytes, more than evaluation.bootstrap_max_bytes = %d (or 2^31 values); "
                              "lower evaluation.bootstrap" % (B, self.num_cells, cols, need, cap))
@@ -896,6 +996,8 @@ class PolicyEvaluator:
                     "go2nn_eval_bootstrap_check")
         self.cell_start, self.cell_envs = torch.from_numpy(self.cell_start_host).to(self.device), torch.from_numpy(self.cell_envs_host).to(self.device)
         self.boot_out = torch.zeros(B, self.num_cells, cols, dtype=torch.float64, device=self.device)
+        if self.bootstrap_all:          # one more [B, cells, cols] table per active scoring family, in the families' reduce order
+            self.boot_outs = {t.name: torch.zeros(B, self.num_cells, int(t.out.shape[1]), dtype=torch.float64, device=self.device) for t in self.tables}
 
     def _keep_fallen(self, fell):
         """of the fallen robots, per cell of the finest partition the mode reports, the `blackbox` lowest env indices"""
@@ -1071,6 +1173,9 @@ class PolicyEvaluator:
         With `evaluation.bootstrap` also "bootstrap": {"replicates", "seed", "confidence", "table" (go2nn_eval_bootstrap's raw output, float64 [B, cells, 12]), "overall"
         (float64 [B, 12]: the overall row of every replicate; replicate_metrics() turns it into the figures' replicates)}, and every leaf dict with RESULT_KEYS gains
         "ci": {metric: [lo, hi]} for CI_KEYS.
+        With `evaluation.bootstrap_all` too "bootstrap" gains "tables": {family: go2nn_<family>_bootstrap's raw output, float64 [B, cells, cols]} and "metrics": {figure:
+        float64 [B]}, the "ci" of every leaf that reports a family's figures gains them, every leaf of "gait" and "asymmetry" gains a "ci", and every entry of
+        "ladder_summary" gains "ci": {"level_cleared", "mean_level_cleared"}.
         use_graph: None = eager, or with `evaluation.replay` eager the first time and a captured chunk afterwards (on the GPU); True / False force it."""
         with torch.inference_mode():
             if self.evaluations > 0:
@@ -1119,11 +1224,18 @@ class PolicyEvaluator:
                 self._check(self.nn.go2nn_eval_bootstrap(C.c_void_p(self.acc.data_ptr()), C.c_void_p(self.cell_start.data_ptr()), C.c_void_p(self.cell_envs.data_ptr()),
                                                          self.num_envs, self.num_cells, self.bootstrap, self.bootstrap_seed, C.c_void_p(self.boot_out.data_ptr()), self._stream()),
                             "go2nn_eval_bootstrap")
-            host = {}
+            host, bhost = {}, {}
+            boot_all = self.bootstrap > 0 and self.bootstrap_all
             for t, _ in pairs:
                 self._check(getattr(self.nn, "go2nn_%s_reduce" % t.name)(C.c_void_p(t.table.data_ptr()), C.c_void_p(self.group.data_ptr()), self.num_envs, self.num_cells,
                                                                          *t.reduce_args, C.c_void_p(t.out.data_ptr()), self._stream()), "go2nn_%s_reduce" % t.name)
+                if boot_all:          # the family's reduce rows of the SAME redrawn robots (outside any capture, as go2nn_eval_bootstrap above)
+                    self._check(getattr(self.nn, "go2nn_%s_bootstrap" % t.name)(C.c_void_p(t.table.data_ptr()), C.c_void_p(self.cell_start.data_ptr()), C.c_void_p(self.cell_envs.data_ptr()),
+                                                                                self.num_envs, self.num_cells, self.bootstrap, self.bootstrap_seed, *t.reduce_args,
+                                                                                C.c_void_p(self.boot_outs[t.name].data_ptr()), self._stream()), "go2nn_%s_bootstrap" % t.name)
                 host[t.name] = t.out.cpu().numpy().copy()
+                if boot_all:
+                    bhost[t.name] = self.boot_outs[t.name].cpu().numpy().copy()
             if run.asym is not None:
                 self.asym_last = None
             table = self.out.cpu().numpy().copy()          # the device -> host copy (and synchronisation) of an evaluation
@@ -1139,6 +1251,8 @@ class PolicyEvaluator:
             self._gait_results(res, host["gait"])
         if "asym" in host:
             self._asym_results(res, host["asym"])
+        if btable is not None and self.bootstrap_all:
+            self._bootstrap_all_results(res, btable, bhost)
         if trace is not None:
             self._label(trace, trace["env_ids"])
             res["trace"] = trace
@@ -1309,6 +1423,95 @@ class PolicyEvaluator:
                 res["maneuvers"][n]["ci"] = ci(t3[:, :, mi].sum(1))
         res["bootstrap"] = {"replicates": B, "seed": self.bootstrap_seed, "confidence": conf, "table": bcells, "overall": overall}
 
+    def _addon_replicates(self, bcells, pool=np.sum):
+        """bcells [B, cells, cols]: an add-on's bootstrap table -> [(path into the add-on's tree, replicate rows [B, cols])] for every leaf _addon_tree makes: its pooling,
+        one axis further in"""
+        B, T, S, key, names = bcells.shape[0], self.T, self.S, self.axis_key, self.axis_names
+        table, view = self._cell_views(bcells, pool)
+        out = [(("overall",), pool(table, 1))]
+        out += [(("groups", t, s[0]), table[:, ti * S + si]) for ti, t in enumerate(self.terrain_names) for si, s in enumerate(self.scenarios)]
+        if key in ("perturbations", "sensors"):
+            out += [(("cells", t, s[0], n), view[:, ti * S + si, pi]) for ti, t in enumerate(self.terrain_names) for si, s in enumerate(self.scenarios) for pi, n in enumerate(names)]
+            out += [((key, n), pool(view[:, :, pi], 1)) for pi, n in enumerate(names)]
+        elif key == "ladder":
+            out += [(("ladder", t, lv, s[0]), view[:, ti, li, si]) for ti, t in enumerate(self.terrain_names) for li, lv in enumerate(names) for si, s in enumerate(self.scenarios)]
+        elif key == "maneuvers":
+            out += [(("maneuvers", n), pool(table.reshape(B, T, S, -1)[:, :, si], 1)) for si, n in enumerate(names)]
+        return out
+
+    def _mode_replicates(self, res, name, bcells):
+        """bcells [B, cells, cols]: the bootstrap table of a mode's own family -> [(path into res, replicate rows [B, cols])] for every leaf that reports the family's
+        figures: the pooling of _results / _ladder_results, one axis further in"""
+        B, T, S, names = bcells.shape[0], self.T, self.S, self.axis_names
+        out = [(("overall",), bcells.sum(1))]
+        if name == "robust":
+            r3 = self._cell_views(bcells)[1]
+            out += [(("cells", t, s[0], n), r3[:, ti * S + si, pi]) for ti, t in enumerate(self.terrain_names) for si, s in enumerate(self.scenarios) for pi, n in enumerate(names)]
+            out += [(("perturbations", n), r3[:, :, pi].sum(1)) for pi, n in enumerate(names)]
+        elif name == "maneuver":
+            out += [(("groups", t, n), bcells[:, ti * S + mi]) for ti, t in enumerate(self.terrain_names) for mi, n in enumerate(names)]
+            out += [(("maneuvers", n), bcells.reshape(B, T, S, -1)[:, :, mi].sum(1)) for mi, n in enumerate(names)]
+        elif name == "ladder":
+            l4 = self._cell_views(bcells)[1]
+            out += [(("ladder", t, lv, s[0]), l4[:, ti, li, si]) for ti, t in enumerate(self.terrain_names) for li, lv in enumerate(self.levels) for si, s in enumerate(self.scenarios)]
+        return out
+
+    def _ladder_summary_replicates(self, cleared):
+        """cleared: float64 [B, levels], a terrain's replicate `cleared` curve under the first ladder scenario -> (level_cleared [B], mean_level_cleared [B]) by
+        _ladder_results' loop rule: an empty cell (NaN) has cleared nothing; the highest level of the unbroken run of levels at or above the pass share (-1: none); the
+        curve's sum from the lowest level up"""
+        curve = np.where(np.isnan(cleared), 0.0, cleared)
+        run = np.logical_and.accumulate(~(curve < self.ladder_pass_share), axis=1).sum(1)
+        top = np.where(run > 0, np.asarray(self.levels, np.float64)[np.maximum(run, 1) - 1], -1.0)
+        mean = np.zeros(curve.shape[0])
+        for li in range(curve.shape[1]):
+            mean = mean + curve[:, li]
+        return top, mean
+
+    def _bootstrap_all_results(self, res, bcells, bhost):
+        """bhost: {family: its bootstrap table [B, cells, cols]} -> the families' figures in the "ci" of every leaf that reports them (the leaves of res["gait"] and
+        res["asymmetry"] gain a "ci"), the ladder summary's intervals, and res["bootstrap"]["tables"] / ["metrics"].  Per family ONE vectorised pass over (replicates x
+        leaves): the row function's twin on the stacked replicate rows, one quantile call over every figure of every leaf"""
+        conf, bs, dt = self.confidence, res["bootstrap"], self.dt
+        metrics = dict(replicate_metrics(bs["overall"]))
+        twins = {"robust": lambda r: robust_replicates(r, dt), "maneuver": lambda r: maneuver_replicates(r, dt), "ladder": lambda r: ladder_replicates(r, dt),
+                 "gait": lambda r: gait_replicates(r, dt, self.foot_names), "asym": asym_replicates}
+        for name, table in bhost.items():
+            if name in ("gait", "asym"):
+                root = res["gait" if name == "gait" else "asymmetry"]
+                leaves = self._addon_replicates(table, self._asym_pool if name == "asym" else np.sum)
+            else:
+                root, leaves = res, self._mode_replicates(res, name, table)
+            reps = twins[name](np.stack([rows for _, rows in leaves], 1))          # {key: [B, leaves]}
+            keys = list(reps)
+            lo, hi = interval_columns(np.concatenate([reps[k] for k in keys], 1), conf)
+            L = len(leaves)
+            for li, (path, _) in enumerate(leaves):
+                node = root
+                for step in path:
+                    node = node[step]
+                if name == "ladder" and path == ("overall",):          # the overall row reports `cleared` alone (and mean_level_cleared, below)
+                    node["ci"]["cleared"] = [float(lo[keys.index("cleared") * L + li]), float(hi[keys.index("cleared") * L + li])]
+                    continue
+                node.setdefault("ci", {}).update({k: [float(lo[ki * L + li]), float(hi[ki * L + li])] for ki, k in enumerate(keys)})
+            overall = {k: np.ascontiguousarray(v[:, 0]) for k, v in reps.items()}          # (leaf 0 is "overall")
+            if name == "ladder":          # per terrain the summary's two figures from the replicate curves, and the overall mean over the terrains
+                overall = {"cleared": overall["cleared"]}
+                first, per_t = self.scenarios[0][0], []
+                at = {path: li for li, (path, _) in enumerate(leaves)}
+                for t in self.terrain_names:
+                    curve = np.stack([reps["cleared"][:, at[("ladder", t, lv, first)]] for lv in self.levels], 1)
+                    top, mean = self._ladder_summary_replicates(curve)
+                    res["ladder_summary"][t]["ci"] = {"level_cleared": interval(top, conf), "mean_level_cleared": interval(mean, conf)}
+                    per_t.append(mean)
+                per_t = np.stack(per_t, 1)
+                overall["mean_level_cleared"] = np.asarray([float(np.mean(per_t[b])) for b in range(per_t.shape[0])])
+                res["overall"]["ci"]["mean_level_cleared"] = interval(overall["mean_level_cleared"], conf)
+            if name == "gait":          # res["overall"] reports the pooled gait figures
+                res["overall"]["ci"].update({k: root["overall"]["ci"][k] for k in GAIT_KEYS})
+            metrics.update(overall)
+        bs["tables"], bs["metrics"] = dict(bhost), metrics
+
     def _results(self, cells, rcells=None, lcells=None, mcells=None):
         """cells: the eval reduce table per (terrain, scenario, perturbation) cell; rcells: the robust one (None without perturbations: a cell is a group then);
         lcells: the ladder's (None without the ladder), cells being per (terrain, level, scenario) then;  mcells: the maneuvers' (None without maneuvers), per
@@ -1358,7 +1561,7 @@ class PolicyEvaluator:
 # ---------------------------------------------------------------------------------------------------------------------------------------------------------------
 def scalars(res):
     """[(tag, value)]: with gait 'Eval/gait/<key>' and 'Eval/gait/<terrain>/<scenario>/<key>'; with asymmetry 'Eval/asymmetry/<key>' and 'Eval/asymmetry/<terrain>/<scenario>/<key>'; 'Eval/<metric>' for the overall figures, 'Eval/<terrain>/<scenario>/<metric>' per group, with perturbations 'Eval/robust/<name>/<metric>', with
-    maneuvers 'Eval/maneuver/<name>/<metric>', with sensor conditions 'Eval/sensors/<name>/<metric>' and, with the ladder, 'Eval/ladder/<terrain>/{level_cleared,mean_level_cleared}' and 'Eval/ladder/mean_level_cleared'; with the black box 'Eval/falls/robots_fell'; with the bootstrap 'Eval/ci_low/<metric>' and 'Eval/ci_high/<metric>' (overall only)"""
+    maneuvers 'Eval/maneuver/<name>/<metric>', with sensor conditions 'Eval/sensors/<name>/<metric>' and, with the ladder, 'Eval/ladder/<terrain>/{level_cleared,mean_level_cleared}' and 'Eval/ladder/mean_level_cleared'; with the black box 'Eval/falls/robots_fell'; with the bootstrap 'Eval/ci_low/<metric>' and 'Eval/ci_high/<metric>' (overall only; with `bootstrap_all` also the families' overall figures and 'Eval/asymmetry/ci_low|high/<key>')"""
     out = [("Eval/" + k, res["overall"][k]) for k in RESULT_KEYS]
     for t, per in res["groups"].items():
         for s, d in per.items():
@@ -1374,7 +1577,7 @@ def scalars(res):
             out += [("Eval/ladder/%s/%s" % (t, k), d[k]) for k in LADDER_SUMMARY_KEYS]
         out.append(("Eval/ladder/mean_level_cleared", res["overall"]["mean_level_cleared"]))
     if res.get("gait") is not None:          # overall: pooled and per foot; per group: pooled
-        out += [("Eval/gait/" + k, v) for k, v in res["gait"]["overall"].items() if k != "n_envs"]
+        out += [("Eval/gait/" + k, v) for k, v in res["gait"]["overall"].items() if k not in ("n_envs", "ci")]
         for t, per in res["gait"]["groups"].items():
             for s, d in per.items():
                 out += [("Eval/gait/%s/%s/%s" % (t, s, k), d[k]) for k in GAIT_KEYS]
@@ -1388,6 +1591,12 @@ def scalars(res):
     if res.get("bootstrap") is not None:          # with the bootstrap: 'Eval/ci_low/<metric>' and 'Eval/ci_high/<metric>', the overall figures only
         for k in CI_KEYS:
             out += [("Eval/ci_low/" + k, res["overall"]["ci"][k][0]), ("Eval/ci_high/" + k, res["overall"]["ci"][k][1])]
+        if "tables" in res["bootstrap"]:          # with `bootstrap_all`: the families' overall figures, and the asymmetry section's
+            for k, (lo, hi) in res["overall"]["ci"].items():
+                if k not in CI_KEYS:
+                    out += [("Eval/ci_low/" + k, lo), ("Eval/ci_high/" + k, hi)]
+            for k, (lo, hi) in ((res.get("asymmetry") or {}).get("overall", {}).get("ci") or {}).items():
+                out += [("Eval/asymmetry/ci_low/" + k, lo), ("Eval/asymmetry/ci_high/" + k, hi)]
     return out
 
 
@@ -1478,6 +1687,12 @@ def format_table(res):
         head = "%g %% interval, %d replicates" % (100.0 * bs["confidence"], bs["replicates"])
         lines += ["", "%-36s " % head + " ".join("%34s" % c for c in cols)]
         lines.append("%-36s " % "all" + " ".join("%34s" % ("%.4f [%.4f, %.4f]" % ((res["overall"][c],) + tuple(res["overall"]["ci"][c]))) for c in cols))
+        if "tables" in bs:          # with `bootstrap_all`: the active families' headline figures
+            cells = [(c, res["overall"]) for fam, cs in BOOTSTRAP_HEADLINES for c in cs if fam in bs["tables"] and fam != "asym"]
+            cells += [(c, res["asymmetry"]["overall"]) for fam, cs in BOOTSTRAP_HEADLINES for c in cs if fam == "asym" and fam in bs["tables"]]
+            if cells:
+                lines += ["%-36s " % "" + " ".join("%34s" % c for c, _ in cells)]
+                lines.append("%-36s " % "all" + " ".join("%34s" % ("%.4g [%.4g, %.4g]" % ((d[c],) + tuple(d["ci"][c]))) for c, d in cells))
     return "\n".join(lines)
 
 

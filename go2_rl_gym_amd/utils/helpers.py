@@ -93,7 +93,7 @@ _RUNNER_OVERRIDES = ("max_iterations", "experiment_name", "run_name", "load_run"
 def update_cfg_from_args(env_cfg, cfg_train, args):
     """Command-line overrides onto the config objects (legged_gym/utils/helpers.py update_cfg_from_args): --num_envs onto the env config;
     --seed, --resume and the runner fields above onto the train config; the RoboGauge switches when the train config has that section (parsed and ignored: the service is
-    out of scope), --symmetry onto algorithm.symmetry, --normalize_obs onto runner.empirical_normalization, and next to them --evaluate / --eval_interval / --record / --robust / --ladder / --maneuvers / --sensors / --gait / --blackbox / --asymmetry / --ci onto the `evaluation` section."""
+    out of scope), --symmetry onto algorithm.symmetry, --normalize_obs onto runner.empirical_normalization, and next to them --evaluate / --eval_interval / --record / --robust / --ladder / --maneuvers / --sensors / --gait / --blackbox / --asymmetry / --ci / --ci_all onto the `evaluation` section."""
     if env_cfg is not None and args.num_envs is not None:
         env_cfg.env.num_envs = args.num_envs
     if cfg_train is None:
@@ -146,6 +146,8 @@ def update_cfg_from_args(env_cfg, cfg_train, args):
             ev.asymmetry = True
         if getattr(args, "ci", None) is not None:
             ev.bootstrap = args.ci
+        if getattr(args, "ci_all", False):
+            ev.bootstrap_all = True
     return env_cfg, cfg_train
 
 
@@ -186,6 +188,9 @@ def get_args(argv=None):
     p.add_argument("--ci", type=int, nargs="?", const=1000, help="give every evaluated figure a bootstrap confidence interval from B resamplings of the robots within their "
                    "cells (default 1000; works next to every mode above), and let evaluate.py --all_checkpoints compare every checkpoint with the best one on the same "
                    "resamplings: evaluation.bootstrap = B")
+    p.add_argument("--ci_all", action="store_true", default=False, help="with --ci [B] (given alone: --ci 1000) also give the modes' own figures (push_falls, settle_time_s, "
+                   "cleared, ...) and the gait and asymmetry sections their intervals, from the same resamplings, and let evaluate.py --metric rank by them: "
+                   "evaluation.bootstrap_all = True")
     p.add_argument("--symmetry", action="store_true", default=False, help="train every PPO mini-batch on its left-right mirror image too (feed-forward PPO only): "
                    "algorithm.symmetry = True")
     p.add_argument("--mirror_loss", type=float, default=None, metavar="COEF", help="add COEF x the mean squared gap between the policy's answer to an observation and the "
@@ -204,6 +209,8 @@ def get_args(argv=None):
     p.add_argument("--subscenes", type=int, default=0)
     p.add_argument("--slices", type=int, default=0)
     args = p.parse_args(argv)
+    if args.ci_all and args.ci is None:          # --ci_all alone: --ci with its default
+        args.ci = 1000
     dev = args.sim_device
     args.sim_device_type = dev.split(":")[0]
     args.compute_device_id = int(dev.split(":")[1]) if ":" in dev else 0

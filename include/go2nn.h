@@ -857,6 +857,23 @@ int go2nn_asym_reduce(const float* table, const int32_t* group, int32_t N, int32
 int go2nn_eval_bootstrap_check(const int32_t* host_cell_start, const int32_t* host_cell_envs, int32_t N, int32_t G);
 int go2nn_eval_bootstrap(const float* acc, const int32_t* cell_start, const int32_t* cell_envs, int32_t N, int32_t G, int32_t B, uint32_t seed, double* out, void* stream);
 
+/* ---- the same replicates of every scoring family's reduce table (`evaluation.bootstrap_all`; csrc/go2nn_bootstrap.h).
+ * ADDED WITHIN ABI 7: five new entry points, nothing existing changes, GO2NN_ABI_VERSION stays 7.
+ * THE RULE, ONCE: replicate (b, g) of every family draws the same members as go2nn_eval_bootstrap's — j(b, g, k) above depends on (b, g, k, seed) and the cell's size, not on
+ * the table — so a replicate's rows across the tables are ONE resampled population (a robot drawn twice brings its pushes, its switches and its strides twice).
+ * Each entry point is its family's reduce with the group's envs replaced by the draws: `table` is the family's per-robot table, term(e, c) the family's reduce term, cols its
+ * reduce width (robust GO2NN_ROBUST_ACC_NUM + 1, maneuver GO2NN_MANEUVER_ACC_NUM + 1, ladder GO2NN_LADDER_OUT_NUM, gait GO2NN_GAIT_OUT_NUM, asym GO2NN_ASYM_OUT_NUM):
+ *   out[(b G + g) cols + c] = sum over k = 0 .. n - 1 of term(cell_envs[cell_start[g] + j(b, g, k)], c)                     out: fp64 [B, G, cols] row-major
+ * in fp64 in increasing k; the asym table's EQ_MAX column is the MAX over the drawn members instead (as go2nn_asym_reduce's is the group's max).  An empty cell gives zeros.
+ * One lane per (replicate, cell, column window), no LDS, no atomics; the gait table is split into column windows whose lanes recompute the same draws.
+ * GO2NN_EINVAL, with nothing written: go2nn_eval_bootstrap's cases with the bound B G cols < 2^31; the ladder also for dist2_thr <= 0 (go2nn_ladder_reduce's argument). */
+int go2nn_robust_bootstrap(const float* table, const int32_t* cell_start, const int32_t* cell_envs, int32_t N, int32_t G, int32_t B, uint32_t seed, double* out, void* stream);
+int go2nn_maneuver_bootstrap(const float* table, const int32_t* cell_start, const int32_t* cell_envs, int32_t N, int32_t G, int32_t B, uint32_t seed, double* out, void* stream);
+int go2nn_ladder_bootstrap(const float* table, const int32_t* cell_start, const int32_t* cell_envs, int32_t N, int32_t G, int32_t B, uint32_t seed, float dist2_thr, double* out,
+                           void* stream);
+int go2nn_gait_bootstrap(const float* table, const int32_t* cell_start, const int32_t* cell_envs, int32_t N, int32_t G, int32_t B, uint32_t seed, double* out, void* stream);
+int go2nn_asym_bootstrap(const float* table, const int32_t* cell_start, const int32_t* cell_envs, int32_t N, int32_t G, int32_t B, uint32_t seed, double* out, void* stream);
+
 /* ---- empirical (running mean / std) normalisation of the observations of feed-forward PPO (go2_rl_gym_amd/rsl_rl/modules/normalizer.py, rsl_rl/algorithms/ppo.py,
  * `runner.empirical_normalization`; csrc/go2nn_obs_norm.h).
  * ADDED WITHIN ABI 7: three new entry points and one struct, nothing existing changes, GO2NN_ABI_VERSION stays 7.

@@ -1,6 +1,6 @@
 """What one policy evaluation costs (utils/evaluator.py), and what the metric kernel saves over torch expressions.
 
-    python tools/eval_bench.py [--task go2_flat] [--reps 3] [--robust] [--ladder] [--maneuvers] [--sensors] [--blackbox] [--asymmetry] [--ci] [--out profiles/eval_bench.json]
+    python tools/eval_bench.py [--task go2_flat] [--reps 3] [--robust] [--ladder] [--maneuvers] [--sensors] [--blackbox] [--asymmetry] [--ci] [--ci_all] [--out profiles/eval_bench.json]
 
 Measures, on cuda:0, with the task's default `evaluation` section (1024 robots, 1 s + 10 s):
   * wall time of evaluate() run eagerly and with the captured chunk of steps replayed (simulator re-creation, capture and the final host copy included: it is what
@@ -22,6 +22,8 @@ back-to-back call with no robot frozen, by the same method.
 --asymmetry: a measurement of its own, ADDED to profiles/asymmetry_bench.json under the task's name: evaluate() run eagerly with evaluation.asymmetry off and on,
 alternating, --reps runs each (at least five) in this one session — best, median, spread and every run —, and per back-to-back call on the evaluator's own buffers the
 three extra pieces of a step: the mirror launch, the policy's second forward and go2nn_asym_accumulate.
+--ci_all: a measurement of its own, written to profiles/bootstrap_all_bench.json: evaluate() with --robust --gait --asymmetry --ci run eagerly without and with
+evaluation.bootstrap_all, alternating, the difference split into launches, copies and the host's quantiles, and every family's launch alone at 6, 42 and 294 cells.
 --ci: a measurement of its own, written to profiles/bootstrap_bench.json: evaluate() run eagerly with evaluation.bootstrap off and at 1000 replicates, alternating, --reps
 runs each (at least five) in this one session — best, median, spread, every run and the difference of the medians —, and go2nn_eval_bootstrap alone per back-to-back call
 on the evaluation's own accumulators at the plain cells, at --robust's cells and at seven times as many (--robust on a terrain task), each next to the same resampling
@@ -34,6 +36,7 @@ import os
 import statistics
 import sys
 import time
+import types
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -296,6 +299,106 @@ def bootstrap_main(a):
         e.close()
 
 
+def bootstrap_all_main(a):
+    """--ci_all: what `evaluation.bootstrap_all` costs one evaluation with --robust --gait --asymmetry --ci, next to the same evaluation without it in the same session
+    (alternating runs), the difference split into launches, copies and the host's replicate figures and quantiles, and every bootstrap launch alone (the five families' and go2nn_eval_bootstrap) at 6, 42 and 294 cells
+    next to the same resampling in vectorised numpy -> profiles/bootstrap_all_bench.json"""
+    import numpy as np
+    from go2_rl_gym_amd import build
+    B = 1000
+    env_cfg, train_cfg = task_registry.get_cfgs(a.task)
+    ev_cfg = dict(class_to_dict(train_cfg.evaluation), perturbations=[[n, dict(f)] for n, f in DEFAULT_PERTURBATIONS], gait=True, asymmetry=True, bootstrap=B)
+    make = lambda **over: PolicyEvaluator(env_cfg, dict(ev_cfg, **over), task_class=task_registry.get_task_class(a.task), device="cuda:0")
+    evs = {"ci": make(), "ci_all": make(bootstrap_all=True)}
+    from go2_rl_gym_amd.rsl_rl.modules import ActorCritic
+    torch.manual_seed(0)
+    ac = ActorCritic(45, 263, 12, **{k: v for k, v in class_to_dict(train_cfg.policy).items() if k in ("actor_hidden_dims", "critic_hidden_dims", "activation", "init_noise_std")}).to("cuda:0")
+    res = {k: ev.evaluate(ac, use_graph=False) for k, ev in evs.items()}
+    assert res["ci"]["bootstrap"]["table"].tobytes() == res["ci_all"]["bootstrap"]["table"].tobytes() and "tables" not in res["ci"]["bootstrap"]
+    ev = evs["ci_all"]
+    N, st, p = ev.num_envs, ev._stream(), lambda t: C.c_void_p(t.data_ptr())
+    entry = {"task": a.task, "device": torch.cuda.get_device_name(0), "num_envs": N, "steps": ev.warmup_steps + ev.steps, "cells": ev.num_cells, "replicates": B,
+             "families": {t.name: int(t.out.shape[1]) for t in ev.tables}, "table_bytes": {n: int(t.numel() * 8) for n, t in ev.boot_outs.items()}}
+    match = {"eval": 12, "robust": 7, "maneuver": 9, "ladder": 6, "gait": 55, "asym": 25}
+    entry["registers"] = {f: {k: r[k] for k in ("kernel", "vgpr_count", "sgpr_count", "scratch_bytes_per_lane", "lds_bytes_per_workgroup")}
+                          for f, r in ((f, build.kernel_resources(build.NN_OUT, match="eval_bootstrap_kernelILi%dELi" % c)) for f, c in match.items()) if r}
+    # the split: the families' launches on the evaluation's own tables (device events), the copies of their tables, the host's pass over them
+    launch = lambda t, s_d, e_d, G, out: getattr(ev.nn, "go2nn_%s_bootstrap" % t.name)(p(t.table), p(s_d), p(e_d), N, G, B, ev.bootstrap_seed, *t.reduce_args, p(out), st)
+    split = {"launch_us": {}, "copy_ms": {}}
+    for t in ev.tables:
+        fn = lambda: launch(t, ev.cell_start, ev.cell_envs, ev.num_cells, ev.boot_outs[t.name])
+        assert fn() == 0
+        timed(fn, 20)
+        split["launch_us"][t.name] = timed(fn, 200)[0]
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        ev.boot_outs[t.name].cpu().numpy().copy()
+        split["copy_ms"][t.name] = (time.perf_counter() - t0) * 1e3
+    host = []
+    for _ in range(3):
+        r = ev.evaluate(ac, use_graph=False)
+        tables = r["bootstrap"].pop("tables")
+        r["bootstrap"].pop("metrics")
+        t0 = time.perf_counter()
+        ev._bootstrap_all_results(r, r["bootstrap"]["table"], tables)
+        host.append((time.perf_counter() - t0) * 1e3)
+    split["host_replicates_and_quantiles_ms"] = {"best": min(host), "all": host}
+    split["launches_ms_total"], split["copies_ms_total"] = sum(split["launch_us"].values()) / 1e3, sum(split["copy_ms"].values())
+    entry["split_of_one_evaluation"] = split
+    # every family's launch alone at 6, 42 and 294 cells of these robots, next to the same resampling in vectorised numpy (random indices, a gather and a sum per cell)
+    entry["launch"] = {}
+    maneuver = make(perturbations=None, maneuvers=[[n, [list(seg) for seg in segs]] for n, segs in DEFAULT_MANEUVERS], gait=False, asymmetry=False, bootstrap_all=True)
+    maneuver.evaluate(ac, use_graph=False)
+    # the two launches this evaluation does not make: go2nn_eval_bootstrap on its own accumulators, and the ladder's (a terrain-task mode) on a table of these robots with
+    # random states and distances — the launch's work does not depend on the values
+    from go2_rl_gym_amd._nn import GO2NN_EVAL_NUM, GO2NN_LADDER_NUM, GO2NN_LADDER_OUT_NUM, LADDER_ROWS, LADDER_STATES
+    ltable = torch.rand(GO2NN_LADDER_NUM, N, device="cuda:0")
+    ltable[LADDER_ROWS.index("state")] = torch.randint(0, len(LADDER_STATES), (N,), device="cuda:0").float()
+    alone = types.SimpleNamespace
+    extra = [alone(name="eval", table=ev.acc, out=torch.zeros(1, GO2NN_EVAL_NUM + 2), reduce_args=()),
+             alone(name="ladder", table=ltable, out=torch.zeros(1, GO2NN_LADDER_OUT_NUM), reduce_args=(0.25,))]
+    for e, t in [(ev, t) for t in ev.tables] + [(maneuver, t) for t in maneuver.tables] + [(ev, t) for t in extra]:
+        terms = np.ascontiguousarray(np.resize(t.table.cpu().numpy().astype(np.float64), (int(t.out.shape[1]), N)).T)          # [N, cols]: the yardstick's gather width
+        for G in (6, 42, 294):
+            cell = (np.arange(N) % G).astype(np.int32)
+            start, envs = np.concatenate([[0], np.cumsum(np.bincount(cell, minlength=G))]).astype(np.int32), np.argsort(cell, kind="stable").astype(np.int32)
+            s_d, e_d = torch.from_numpy(start).to("cuda:0"), torch.from_numpy(envs).to("cuda:0")
+            out = torch.zeros(B, G, int(t.out.shape[1]), dtype=torch.float64, device="cuda:0")
+            fn = lambda: launch(t, s_d, e_d, G, out)
+            assert fn() == 0
+            timed(fn, 20)
+            dev_us, wall_us = timed(fn, 200)
+            host = []
+            for _ in range(3):
+                rng, t0 = np.random.default_rng(1), time.perf_counter()
+                ref = np.zeros((B, G, terms.shape[1]))
+                for g in range(G):
+                    mem = envs[start[g]:start[g + 1]]
+                    ref[:, g] = terms[mem[rng.integers(0, len(mem), (B, len(mem)))]].sum(1)
+                host.append((time.perf_counter() - t0) * 1e3)
+            entry["launch"]["%s/%d" % (t.name, G)] = {"device_us_per_call_back_to_back": dev_us, "host_us_per_call": wall_us, "numpy_on_host_ms": min(host)}
+    maneuver.close()
+    if not a.kernel_only:
+        walls = {k: [] for k in evs}
+        for _ in range(max(a.reps, 5)):          # alternating, in this one session
+            for k, e in evs.items():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                e.evaluate(ac, use_graph=False)
+                walls[k].append((time.perf_counter() - t0) * 1e3)
+        entry["evaluate_wall_ms_eager"] = {k: {"best": min(w), "median": statistics.median(w), "spread": max(w) - min(w), "all": w} for k, w in walls.items()}
+        entry["evaluate_wall_ms_eager"]["ci_all_minus_ci_median"] = statistics.median(walls["ci_all"]) - statistics.median(walls["ci"])
+        if os.path.exists(a.out):          # sections of the file this tool does not measure (merged by hand; their "about" says from what) stay
+            with open(a.out) as f:
+                entry.update({k: v for k, v in json.load(f).items() if k in ("chunk_widths", "bench_py_env_steps_per_s")})
+        os.makedirs(os.path.dirname(a.out), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(entry, f, indent=1)
+    print(json.dumps(entry))
+    for e in evs.values():
+        e.close()
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--task", default="go2_flat")
@@ -308,9 +411,12 @@ def main():
     p.add_argument("--blackbox", action="store_true")
     p.add_argument("--asymmetry", action="store_true")
     p.add_argument("--ci", action="store_true")
+    p.add_argument("--ci_all", action="store_true")
     p.add_argument("--out", default=None)
     a = p.parse_args()
-    a.out = a.out or os.path.join(ROOT, "profiles", "bootstrap_bench.json" if a.ci else "asymmetry_bench.json" if a.asymmetry else "blackbox_bench.json" if a.blackbox else "eval_bench.json")
+    a.out = a.out or os.path.join(ROOT, "profiles", "bootstrap_all_bench.json" if a.ci_all else "bootstrap_bench.json" if a.ci else "asymmetry_bench.json" if a.asymmetry else "blackbox_bench.json" if a.blackbox else "eval_bench.json")
+    if a.ci_all:
+        return bootstrap_all_main(a)
     if a.ci:
         return bootstrap_main(a)
     if a.asymmetry:
