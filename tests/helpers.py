@@ -459,6 +459,10 @@ def check_relative_to_conditioning(err, cond, floors, factor=3.0):
 BASE_B, THIGH_B, CALF_B, HIP_B, FOOT_B = 0, [4, 8, 12, 16], [5, 9, 13, 17], [3, 7, 11, 15], [6, 10, 14, 18]
 
 
+# the URDF joint stops (rad), in DOF order (hip, thigh, calf of FL, FR, RL, RR): the rear thighs reach further back
+JOINT_LO = np.array([-1.0472, -1.5708, -2.7227, -1.0472, -1.5708, -2.7227, -1.0472, -0.5236, -2.7227, -1.0472, -0.5236, -2.7227])
+JOINT_HI = np.array([1.0472, 3.4907, -0.83776, 1.0472, 3.4907, -0.83776, 1.0472, 4.5379, -0.83776, 1.0472, 4.5379, -0.83776])
+
 LYING_KW = dict(turn_over=1, turn_over_proportions=np.array([0.0, 0.0, 1.0], np.float32), push_robots=0, seed=3, kp=[0.0] * 12, kd=[0.5] * 12, randomize_action_delay=0)
 
 
@@ -469,7 +473,7 @@ def lying_robot_batch(sim, rng):
     the thigh and the calf of one leg in contact; up to 14 of the 19 bodies).  The simultaneous contact set the reference reads from PhysX:
     termination on the base force (legged_robot.py:170-173), _reward_collision over 8 thigh / calf bodies (:1277-1279), feet (:1252)."""
     N = sim.N
-    lo = np.array([-1.0472, -1.5708, -2.7227] * 2 + [-1.0472, -0.5236, -2.7227] * 2); hi = np.array([1.0472, 3.4907, -0.83776] * 2 + [1.0472, 4.5379, -0.83776] * 2)
+    lo, hi = JOINT_LO, JOINT_HI
     sim.dof_state[:, :, 0] = rng.uniform(lo + 0.06, hi - 0.06, (N, 12)); sim.dof_state[:, :, 1] = 0
     r, p, y = rng.uniform(-0.3, 0.3, N), rng.uniform(-0.3, 0.3, N), rng.uniform(-3, 3, N)
     cr, sr, cp, sp, cy, sy = np.cos(r / 2), np.sin(r / 2), np.cos(p / 2), np.sin(p / 2), np.cos(y / 2), np.sin(y / 2)

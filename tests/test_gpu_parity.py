@@ -62,7 +62,9 @@ def test_one_step_parity_vs_oracle(hip):
     """Each step starts from the oracle's state: 4 substeps (PD, dynamics, contact PGS) + post-physics on the GPU vs the independent CPU
     derivation.  ONE fp32 bound per tensor for every env of every step (helpers.PLANE_BOUND, round 4: root 3e-4, dof 5e-3, torque 3e-3, obs 3e-4,
     reward 2e-5) and a 10x tighter one for 99 % of them — the size of the fp32 oracle's own error against the fp64 oracle on the same
-    inputs (profiles/r2_parity_probe.txt)."""
+    inputs (profiles/r2_parity_probe.txt).
+    This is go2sim_default_cfg only (4 substeps, 8 sweeps, no armature, vertical gravity; hardly an env-step at a joint stop, none at the twist clamp): the other
+    settings and those rows are in tests/test_gpu_step_configs.py (cases and gates: tests/step_config_cases.py)."""
     from helpers import PLANE_BOUND, StepErrors, check_plane_errors, ill_conditioned_envs
     N = 64
     so = HostSim(load_oracle(), num_envs=N)

@@ -182,10 +182,8 @@ def test_joint_stops_hold_against_saturated_motors(which):
     """Robot floating in zero gravity, one leg per env driven with saturated torque into its upper (envs 0-3) or lower (4-7) URDF stops, arriving
     at the velocity limit (30.1 / 20.07 rad/s): the limit rows of the velocity-level solve stop every joint — transient overshoot below
     one substep's travel at that speed (0.15 rad), then at rest within 0.015 rad of the stop while the motor keeps pushing."""
-    from helpers import load_emu
+    from helpers import JOINT_HI as hi, JOINT_LO as lo, load_emu
     lib = load_oracle() if which == "oracle" else load_emu()
-    lo = np.array([-1.0472, -1.5708, -2.7227, -1.0472, -1.5708, -2.7227, -1.0472, -0.5236, -2.7227, -1.0472, -0.5236, -2.7227])
-    hi = np.array([1.0472, 3.4907, -0.83776, 1.0472, 3.4907, -0.83776, 1.0472, 4.5379, -0.83776, 1.0472, 4.5379, -0.83776])
     s = HostSim(lib, num_envs=8, gravity=[0, 0, 0], push_robots=0, randomize_action_delay=0, randomize_motor_strength=0, randomize_pd_gains=0,
                 randomize_motor_zero_offset=0)
     s.reset_all()
