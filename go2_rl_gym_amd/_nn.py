@@ -220,6 +220,19 @@ class Go2nnMirrorLoss(C.Structure):          # (within ABI 7) perm and sign None
                 ("B", C.c_int32), ("A", C.c_int32), ("K", C.c_int32), ("coef", C.c_float)]
 
 
+# the update's diagnostics: the columns of a table row in the order of the enum GO2NN_DIAG_* of include/go2nn.h (where the definitions are)
+DIAG_COLS = ("rows", "ratio_clipped", "ratio_sum", "logratio_sum", "k3_sum", "kl_sum", "kl_max", "adv_sum", "adv_sq", "adv_pos", "verr_sum", "verr_sq", "verr_abs_max",
+             "ret_sum", "ret_sq", "value_clipped", "ratio_max", "ratio_min")
+GO2NN_DIAG_NUM = len(DIAG_COLS)
+DIAG_MAX_COLS, DIAG_MIN_COLS = ("kl_max", "verr_abs_max", "ratio_max"), ("ratio_min",)          # every other column is a sum
+GO2NN_GRAD_SQNORM_MAX = 48
+
+
+class Go2nnPpoDiag(C.Structure):          # (within ABI 7) the inputs of Go2nnPpoHeads, read only
+    _fields_ = [(k, C.c_void_p) for k in ("y_a", "y_c", "w_mu", "b_mu", "w_v", "b_v", "std", "actions", "old_mu", "old_sigma", "old_logp", "adv", "old_values", "returns",
+                                          "partials", "table", "cursor")] + [(k, C.c_int32) for k in ("B", "A", "K", "surrogate_split", "slots")] + [("clip", C.c_float)]
+
+
 def mirror_loss_table_tensors(lib, table, device):
     """The action table of the mirror loss — an involution with sign[perm[j]] == sign[j] —, checked on the host (go2nn_mirror_loss_check_table) and uploaded
     -> (int16 tensor [A], float32 tensor [A]) on `device`"""
@@ -405,6 +418,10 @@ def bind(path):
     lib.go2nn_mirror_loss_cols.argtypes = [C.c_int32] * 2
     lib.go2nn_mirror_loss_check_table.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
     lib.go2nn_mirror_loss.argtypes = [C.POINTER(Go2nnMirrorLoss), C.c_void_p]
+    lib.go2nn_ppo_diag_rows.argtypes = [C.c_int32] * 3          # (within ABI 7) the update's diagnostics
+    lib.go2nn_ppo_diag.argtypes = [C.POINTER(Go2nnPpoDiag), C.c_void_p]
+    lib.go2nn_grad_sqnorm_rows.argtypes = [C.c_void_p, C.c_int32]
+    lib.go2nn_grad_sqnorm.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
     lib.go2nn_obs_norm_partial_rows.argtypes = [C.c_int32]          # (within ABI 7) empirical observation normalisation
     lib.go2nn_obs_norm_apply.argtypes = [C.POINTER(Go2nnObsNormJob), C.c_int32, C.c_int32, C.c_void_p]
     lib.go2nn_obs_norm_update.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]

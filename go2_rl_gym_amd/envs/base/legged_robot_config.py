@@ -254,6 +254,7 @@ class LeggedRobotCfgPPO(BaseConfig):
         max_grad_norm = 1.0
         symmetry = False          # train every mini-batch on its left-right mirror image too (utils/symmetry.py; feed-forward PPO only; --symmetry)
         mirror_loss_coef = 0.0    # > 0 (--mirror_loss COEF, needs symmetry): add COEF x mean((pi(o) - M_a pi(M_o o))^2) over the mini-batch to the PPO loss; feed-forward PPO only
+        diagnostics = False       # True (--diagnostics): per mini-batch step clip fraction, KL, explained variance, ratio / advantage statistics and the gradient norm in front of the clip, computed on the device inside the update and logged as Diag/* (rsl_rl/algorithms/_diag.py); read-only, the weights are bit for bit those of the key-off run; feed-forward PPO and the CTS family (not MCP-CTS)
 
     class runner:
         policy_class_name = "ActorCritic"
@@ -350,6 +351,7 @@ class LeggedRobotCfgCTS(BaseConfig):
         desired_kl = 0.01
         max_grad_norm = 1.0
         teacher_env_ratio = 0.75
+        diagnostics = False       # True (--diagnostics): the update's diagnostics as in LeggedRobotCfgPPO.algorithm, per segment (teacher rows, student rows, all) and per optimizer; MCP-CTS (a state-dependent std) refuses
 
     class runner:
         policy_class_name = "ActorCriticCTS"

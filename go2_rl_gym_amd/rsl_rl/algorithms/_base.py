@@ -52,6 +52,7 @@ class _RolloutHeads:
     _pk = None                  # the fused policy kernel of the rollout: None = not looked for yet, False = not applicable, else the kernel (_policy_kernel() of the subclass decides)
     _pk_packed = False          # the policy kernel's packed weights are those of the current parameters (they change in update() and when a checkpoint is loaded)
     _pk_recorded = False        # the rollout last RUN THROUGH PYTHON (eager, or while being captured) packed at its first step: what a replay of that capture does too
+    _diag = None                # the update's diagnostics (_diag.py:UpdateDiagnostics) when `algorithm.diagnostics` is on; None: nothing is loaded, allocated or launched
 
     # ------------------------------------------------------------------ construction
     def _init_modes(self, device, lib, learning_rate, use_graphs, fused_loss, fused_rollout):
@@ -73,6 +74,50 @@ class _RolloutHeads:
                                            # (+6 % whole-job, measured; GO2_FUSED_MLP=0 restores plain autograd)
         self._clip_adams = {}              # optimizer -> its FusedClipAdam (_clip_adam)
         return on_gpu
+
+    # ------------------------------------------------------------------ the update's diagnostics (_diag.py; off: every hook below is one `is None` test)
+    def _init_diagnostics(self, diagnostics, segments, optimizers):
+        """segments: the names of a mini-batch's row segments; optimizers: [(optimizer, prefix of its grad_* keys)]"""
+        if not diagnostics:
+            return
+        from ._diag import UpdateDiagnostics
+        self._diag = UpdateDiagnostics(self.device, self.num_learning_epochs, self.num_mini_batches, segments, [name for _, name in optimizers], self.clip_param,
+                                       self.max_grad_norm)
+        self._diag_opt = {id(o): j for j, (o, _) in enumerate(optimizers)}
+
+    def _diag_lib(self):
+        """the policy-side library of the diagnostics' kernels: the one the tests handed in, else the device library on a GPU (missing there is an error); None on the
+        CPU with none handed in, where the torch statement of the same sums runs"""
+        lib = getattr(self, "nn_lib", None)
+        if lib is None and str(self.device).startswith("cuda"):
+            from ... import _nn
+            lib = _nn.load_nn()
+        return lib
+
+    def _diag_torch(self, mu, sigma, value, act_b, tv_b, adv_b, ret_b, old_lp_b, old_mu_b, old_sig_b, split=0):
+        """a formulation that holds mu and value as tensors states the diagnostics' columns in torch (the argument order of the loss functions)"""
+        if self._diag is not None:
+            self._diag.record_torch(mu, sigma, value, act_b, old_mu_b, old_sig_b, old_lp_b, adv_b, tv_b, ret_b, split)
+
+    def _diag_finish(self):
+        """behind the update's own read-back: the tables come to the host with one more copy"""
+        if self._diag is not None:
+            self._diag.read()
+
+    @property
+    def diagnostics(self):
+        """the derived figures of the last update (PPO: one dict; the CTS family: per segment "teacher", "student", and pooled "all"); None with the key off"""
+        return None if self._diag is None else self._diag.result
+
+    @property
+    def diagnostics_table(self):
+        """numpy [steps, segments, GO2NN_DIAG_NUM] of the last update; None with the key off"""
+        return None if self._diag is None else self._diag.host_table
+
+    @property
+    def diagnostics_grad_sq(self):
+        """numpy [steps, optimizers]: the squared gradient norm in front of the clip; None with the key off"""
+        return None if self._diag is None else self._diag.host_grad_sq
 
     def _make_adam(self, params, lr=None):
         """Adam over params (or param groups).  lr None: the policy's rate — in graph mode the device tensor the captured steps read and write; any other rate is
@@ -152,7 +197,9 @@ class _RolloutHeads:
             kl_mean = allreduce_mean_bucket([p.grad for p in params if p.grad is not None], _world(), kl_mean if adaptive else None)
         if adaptive:
             self._decide_lr_host(kl_mean, optimizer)
-        nn.utils.clip_grad_norm_(params, self.max_grad_norm)
+        total_norm = nn.utils.clip_grad_norm_(params, self.max_grad_norm)
+        if self._diag is not None:
+            self._diag.grad_from_norm(self._diag_opt[id(optimizer)], total_norm)
         optimizer.step()
 
     # ------------------------------------------------------------------ graph mode
@@ -160,6 +207,8 @@ class _RolloutHeads:
         """The tail of a graph-mode mini-batch step: [adaptive-KL learning rate from kl_mean, decided on the device;] gradient clipping; Adam — as the library's
         clip + Adam call (_graph.py:FusedClipAdam) where that serves, else as torch launches."""
         adaptive = kl_mean is not None and self._adaptive()
+        if self._diag is not None:          # the squared norm the clip is about to see (go2sim_adam_clip_step keeps its own to itself)
+            self._diag.grad_sqnorm(self._diag_opt[id(optimizer)], params, self._diag_lib(), self._stream(self._lr_t))
         fa = self._clip_adams.get(optimizer)
         if fa is None:
             fa = self._clip_adams[optimizer] = FusedClipAdam(self.lib, optimizer, params, self.max_grad_norm)

@@ -24,7 +24,7 @@ class CTS(_RolloutHeads):
     def __init__(self, model, num_envs, history_length, num_learning_epochs=1, num_mini_batches=1, clip_param=0.2, gamma=0.998, lam=0.95,
                  value_loss_coef=1.0, entropy_coef=0.0, learning_rate=1e-3, student_encoder_learning_rate=1e-3, max_grad_norm=1.0,
                  use_clipped_value_loss=True, schedule="fixed", desired_kl=0.01, teacher_env_ratio=0.75, device="cpu", lib=None,
-                 use_graphs=None, fused_loss=None, fused_rollout=None, symmetry=False, mirror_loss_coef=0.0):
+                 use_graphs=None, fused_loss=None, fused_rollout=None, symmetry=False, mirror_loss_coef=0.0, diagnostics=False):
         if symmetry is not None and symmetry is not False:
             raise NotImplementedError("symmetry augmentation (algorithm.symmetry) is implemented for feed-forward PPO only: the CTS family's mirrored observation history "
                                       "is a different piece of work")
@@ -60,6 +60,11 @@ class CTS(_RolloutHeads):
         self._steps = None
         self._step_reps = None
         self._plan = False                  # the no-autograd mini-batch (modules/fused_cts.py): decided at the first graph-mode update (None: not applicable)
+        # the update's diagnostics (_diag.py): two row segments, two optimizers; off, nothing is loaded, allocated or launched
+        if diagnostics and getattr(model, "state_dependent_std", False):
+            raise NotImplementedError("algorithm.diagnostics with a state-dependent std (MCP-CTS) is not implemented: the figures' log-probability and KL are those of "
+                                      "go2nn_ppo_heads, one std per action dimension")
+        self._init_diagnostics(diagnostics, ("teacher", "student"), [(self.optimizer1, ""), (self.optimizer2, "student_encoder_")])
         self._sync_replicas(self.model)
 
     # the runner reaches the networks through either name
@@ -187,11 +192,13 @@ class CTS(_RolloutHeads):
             mu_b, (val_b, aux) = self._pair(lambda: m.policy_mean(latent, obs_b), lambda: m.value(latent, obs_b, priv_b), enabled=self._capture and not m.heads_share_parameters)
             self.surrogate_split = n_t
             loss, stats = _FusedPPOLoss.apply(mu_b, m.std, val_b, self, act_b, tv_b, adv_b, ret_b, old_lp_b, old_mu_b, old_sig_b)
+            self._diag_torch(mu_b, m.std, val_b, act_b, tv_b, adv_b, ret_b, old_lp_b, old_mu_b, old_sig_b, split=n_t)
             return self._policy_extra(loss, aux), stats[1], stats[0], stats[3], stats[2]
         m.update_distribution(torch.cat([latent, obs_b], dim=1))
         lp_b = m.get_actions_log_prob(act_b)
         val_b, aux = m.value(latent, obs_b, priv_b)
         loss, value_loss, surrogate_loss, ent, kl_mean = self.ppo_terms(lp_b, val_b, m.action_mean, m.action_std, m.entropy, tv_b, adv_b, ret_b, old_lp_b, old_mu_b, old_sig_b, n_t)
+        self._diag_torch(m.action_mean, m.action_std, val_b, act_b, tv_b, adv_b, ret_b, old_lp_b, old_mu_b, old_sig_b, split=n_t)
         return self._policy_extra(loss, aux), value_loss, surrogate_loss, ent, kl_mean
 
     _NUM_POLICY_LOGS = 0
@@ -276,7 +283,7 @@ class CTS(_RolloutHeads):
             self.optimizer1.zero_grad(set_to_none=True)
             stats = fused_cts.cts_policy_grads(self._plan, self.model, P["ain"][s], P["cin"][s], P["cobs"][i * mb:i * mb + n_t],
                                                tuple(P[k][s] for k in ("act", "val", "adv", "ret", "logp", "mu", "sig")), n_t, self.clip_param, self.value_loss_coef,
-                                               self.entropy_coef, self.use_clipped_value_loss, acc=self._acc_own)          # (the running sums: added by the pass's go2nn_sum_rows launch)
+                                               self.entropy_coef, self.use_clipped_value_loss, acc=self._acc_own, diag=self._diag)          # (the running sums: added by the pass's go2nn_sum_rows launch)
             kl_mean = stats[2]
         else:
             loss, value_loss, surrogate_loss, ent, kl_mean = self._policy_losses(*(self._perm[k][i * mb:(i + 1) * mb] for k in self._KEYS), self._teacher_rows())
@@ -451,6 +458,9 @@ class CTS(_RolloutHeads):
 
     def update(self):
         self.parameters_changed()          # the optimizer steps below change the parameters: the next rollout re-packs
+        if self._diag is not None:
+            self._diag.begin()          # the slot cursors: zeroed once per update, in front of its first step
         out = self._update_graphs() if self.use_graphs else self._update_eager()
+        self._diag_finish()
         self.storage.clear()
         return out

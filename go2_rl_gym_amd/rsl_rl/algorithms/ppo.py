@@ -37,7 +37,7 @@ from ._graph import CapturedStep, GradBucket, all_captured
 class PPO(_RolloutHeads):
     def __init__(self, actor_critic, num_learning_epochs=1, num_mini_batches=1, clip_param=0.2, gamma=0.998, lam=0.95, value_loss_coef=1.0,
                  entropy_coef=0.0, learning_rate=1e-3, max_grad_norm=1.0, use_clipped_value_loss=True, schedule="fixed", desired_kl=0.01,
-                 device="cpu", lib=None, use_graphs=None, fused_loss=None, fused_rollout=None, symmetry=False, mirror_loss_coef=0.0):
+                 device="cpu", lib=None, use_graphs=None, fused_loss=None, fused_rollout=None, symmetry=False, mirror_loss_coef=0.0, diagnostics=False):
         mirror_loss_coef = 0.0 if mirror_loss_coef is None else float(mirror_loss_coef)
         if not (math.isfinite(mirror_loss_coef) and mirror_loss_coef >= 0.0):
             raise ValueError("PPO(mirror_loss_coef=...) takes a finite weight >= 0, got %r" % (mirror_loss_coef,))
@@ -79,6 +79,11 @@ class PPO(_RolloutHeads):
         # nothing is loaded, allocated or launched.
         self._on_state, self._on_merged = None, False
         self._obs_norm()
+        # the update's diagnostics (_diag.py): off, nothing is loaded, allocated or launched; on, they read what the update reads and write tables of their own
+        if diagnostics and self._rnn:
+            raise NotImplementedError("algorithm.diagnostics with a recurrent policy is not implemented: its heads run in modules/fused_rnn.py, on the memories' outputs "
+                                      "of whole episode segments")
+        self._init_diagnostics(diagnostics, ("all",), [(self.optimizer, "")])
         self._sync_replicas(self.actor_critic)
 
     def rebind_lr(self):
@@ -185,6 +190,7 @@ class PPO(_RolloutHeads):
         if self.fused_loss:
             mu_b, val_b = ac.actor(obs_b), self._value(cobs_b)          # under autograd: one node per network (modules/fused.py:_FusedMLP)
             loss, stats = _FusedPPOLoss.apply(mu_b, ac.std, val_b, self, act_b, tv_b, adv_b, ret_b, old_lp_b, old_mu_b, old_sig_b)
+            self._diag_torch(mu_b, ac.std, val_b, act_b, tv_b, adv_b, ret_b, old_lp_b, old_mu_b, old_sig_b)
             if self.mirror_loss_coef > 0.0:
                 loss = loss + self._mirror_term(mu_b)
             return loss, stats[1], stats[0], stats[2]
@@ -192,6 +198,7 @@ class PPO(_RolloutHeads):
         lp_b = ac.get_actions_log_prob(act_b)
         val_b = self._value(cobs_b)
         loss, value_loss, surrogate_loss, _, kl_mean = self.ppo_terms(lp_b, val_b, ac.action_mean, ac.action_std, ac.entropy, tv_b, adv_b, ret_b, old_lp_b, old_mu_b, old_sig_b)
+        self._diag_torch(ac.action_mean, ac.action_std, val_b, act_b, tv_b, adv_b, ret_b, old_lp_b, old_mu_b, old_sig_b)
         if self.mirror_loss_coef > 0.0:
             loss = loss + self._mirror_term(ac.action_mean)
         return loss, value_loss, surrogate_loss, kl_mean
@@ -334,13 +341,14 @@ class PPO(_RolloutHeads):
             self.optimizer.zero_grad(set_to_none=True)
             mirror = self._mirror_kernel_args() if self.mirror_loss_coef > 0.0 else None          # (go2nn_mirror_loss behind go2nn_ppo_heads; its weighted loss is added to acc[2])
             stats = fused.ppo_pair_grads(ac, batch[0], batch[1], batch[2], batch[3], batch[4], batch[5], batch[6], batch[7], batch[8], self.clip_param, self.value_loss_coef,
-                                         self.entropy_coef, self.use_clipped_value_loss, acc=self._acc, mirror=mirror)          # (the running loss sums: added by the pass's go2nn_sum_rows launch)
+                                         self.entropy_coef, self.use_clipped_value_loss, acc=self._acc, mirror=mirror, diag=self._diag)          # (the running loss sums: added by the pass's go2nn_sum_rows launch)
             kl_mean = stats[2]
         elif self.fused_loss:
             # the loss kernel already holds d loss / d (mu, std, value): seed the backward pass of the two networks with them directly
             # (loss.backward() through the autograd.Function costs a clone and three multiplications by the unit upstream gradient)
             mu_b, val_b = ac.actor(batch[0]), self._value(batch[1])
             stats, gmu, gstd, gval = _FusedPPOLoss.kernel(self, mu_b, ac.std, val_b, *batch[2:])
+            self._diag_torch(mu_b, ac.std, val_b, *batch[2:])
             self.optimizer.zero_grad(set_to_none=True)
             if self.mirror_loss_coef > 0.0:       # the mirror term's gradient joins the kernel's; acc = [surrogate, value loss, L_mirror]
                 gmu = gmu + self._mirror_grad(mu_b)
@@ -451,6 +459,8 @@ class PPO(_RolloutHeads):
     def update(self):
         self.parameters_changed()          # the optimizer steps below change the parameters: the next rollout re-packs
         self._on_merged = False
+        if self._diag is not None:
+            self._diag.begin()          # the slot cursors: zeroed once per update, in front of its first step
         if self._rnn and self.use_graphs and self._rnn_memory() is not None:
             out = self._rnn_update_graphs()
         elif self.use_graphs and not self._rnn:
@@ -458,6 +468,7 @@ class PPO(_RolloutHeads):
         else:
             out = self._update_eager()
         self._obs_norm_finish()
+        self._diag_finish()
         self.storage.clear()
         return out
 

@@ -539,13 +539,15 @@ def ppo_pair_applicable(ac, xa, xc):
     return pl is not None and ac.std.dim() == 1 and ac.std.shape[0] == pl[0][-1].out_features and ac.std.requires_grad
 
 
-def pair_grads(k, la, lc, xa, xc, std, batch, clip, vcoef, ecoef, use_clipped_value_loss, surrogate_split=0, acc=None, imgs=None, need_gz0=True, mirror=None):
+def pair_grads(k, la, lc, xa, xc, std, batch, clip, vcoef, ecoef, use_clipped_value_loss, surrogate_split=0, acc=None, imgs=None, need_gz0=True, mirror=None, diag=None):
     """Forward of two MLPs with grouped hidden layers, go2nn_ppo_heads, backward of the hidden layers; the reductions are queued on `k` (the caller finishes).
     batch: actions, old values, advantages, returns, old log-probs, old mu, old sigma.  imgs: (actor images, critic images) of the hidden layers when the caller split
     them together with other networks' weights.  Sets .grad of every parameter of both networks and of std.
     mirror: (coef, perm int16 [A], sign fp32 [A]) — the rows are [B / 2 originals | B / 2 mirror images] and the mirror loss (go2nn_mirror_loss, one launch behind
     go2nn_ppo_heads) adds its gradient to the actor's gz; k.mirror_sums = (the heads' dW_mu | gb_a | db_mu, the mirror loss's): the caller adds the second to the
     first after k.finish() (ppo_pair_grads); acc[2] receives the weighted loss.
+    diag: the update's diagnostics (algorithms/_diag.py:UpdateDiagnostics: the table, the partial rows and the slot cursor) — ONE go2nn_ppo_diag call right behind the
+    heads' (and the mirror loss's), reading the heads' inputs; None: nothing of it runs.
     -> (sums [surrogate, value loss, KL, entropy | ...] — valid after k.finish() —, the gradients at the first layers' pre-activations)"""
     from ..._nn import Go2nnMirrorLoss, Go2nnPpoHeads
     actions, old_values, adv, returns, old_logp, old_mu, old_sigma = batch
@@ -595,21 +597,23 @@ def pair_grads(k, la, lc, xa, xc, std, batch, clip, vcoef, ecoef, use_clipped_va
         macc = acc[2:] if acc is not None and acc.numel() == 3 else None
         k.sums.append((mpart, mtot, mrows, mcols, macc, 1 if macc is not None else 0))
         k.mirror_sums = (tot[4 + A:4 + A + (A + 1) * K + A], mtot[4:])
+    if diag is not None:
+        diag.record_kernel(_NN, h, k.stream)
     gz1 = k.chain_backward([{"lins": la[:H], "acts": acts[0], "gz": gz[0], "gb": gb_a, "imgs": ia}, {"lins": lc[:H], "acts": acts[1], "gz": gz[1], "gb": gb_c, "imgs": ic}], need_gz0=need_gz0)
     return tot, gz1
 
 
-def ppo_pair_grads(ac, xa, xc, actions, old_values, adv, returns, old_logp, old_mu, old_sigma, clip, vcoef, ecoef, use_clipped_value_loss, acc=None, mirror=None):
+def ppo_pair_grads(ac, xa, xc, actions, old_values, adv, returns, old_logp, old_mu, old_sigma, clip, vcoef, ecoef, use_clipped_value_loss, acc=None, mirror=None, diag=None):
     """One PPO mini-batch gradient (ppo.py:131-170 + loss.backward()) of a plain ActorCritic as explicit launches; every parameter's .grad is set (replaced, as after
     zero_grad(set_to_none=True)).  acc: optional float32[>= 2] device tensor — the mini-batch's surrogate and value loss are ADDED to acc[0:2] by the pass's
     go2nn_sum_rows launch (the update's running sums).  mirror: (coef, perm, sign) device tensors of the action table — the rows are an augmented mini-batch and the
-    mirror loss is part of the objective (pair_grads); acc is then float32[3] and acc[2] receives the weighted mirror loss.
+    mirror loss is part of the objective (pair_grads); acc is then float32[3] and acc[2] receives the weighted mirror loss.  diag: the update's diagnostics (pair_grads).
     -> stats [surrogate, value loss, KL, entropy] (means, device tensor)"""
     la, lc = pair_lins(ac.actor, ac.critic)
     k = _Launch(xa.device)
     with torch.no_grad():
         tot, _ = pair_grads(k, la, lc, xa, xc, ac.std, (actions, old_values, adv, returns, old_logp, old_mu, old_sigma), clip, vcoef, ecoef, use_clipped_value_loss, 0, acc, need_gz0=False,
-                            mirror=mirror)
+                            mirror=mirror, diag=diag)
         k.finish()
         if mirror is not None:
             head, extra = k.mirror_sums

@@ -127,12 +127,13 @@ def _plain_input_grad(k, gz0, lin0, img0):
     return gz0.mm(lin0.weight)
 
 
-def cts_policy_grads(plan, model, ain, cin, priv_t, batch, n_t, clip, vcoef, ecoef, use_clipped_value_loss, acc=None):
+def cts_policy_grads(plan, model, ain, cin, priv_t, batch, n_t, clip, vcoef, ecoef, use_clipped_value_loss, acc=None, diag=None):
     """One CTS policy mini-batch gradient (cts.py:180-250 + loss.backward()).
     ain [B, L + obs], cin [B, L + priv]: the actor's / critic's input matrices, rows [0, n_t) teacher samples, the rest student samples; columns [L, ...) hold obs /
     privileged obs, the STUDENT rows' first L columns the (constant) student latents; the teacher rows' first L columns are written here.  priv_t [n_t, priv]: the
     teacher rows' privileged observations (the teacher encoder's input).  batch: actions, old values, advantages, returns, old log-probs, old mu, old sigma.
     acc: optional float32[>= 4] — [surrogate, value loss, KL, entropy] of the mini-batch are ADDED to it by the pass's go2nn_sum_rows launch.
+    diag: the update's diagnostics (algorithms/_diag.py) or None — handed on to pair_grads.
     -> stats [surrogate, value loss, KL, entropy] (device tensor; valid after the launches)"""
     k = _Launch(ain.device)
     nn_ = k.nn
@@ -149,7 +150,7 @@ def cts_policy_grads(plan, model, ain, cin, priv_t, batch, n_t, clip, vcoef, eco
         inv = k.new(n_t)
         latent_concat(k, eacts[-1], ain, cin, inv)
         # actor + critic: grouped hidden layers, heads + PPO loss with the split surrogate, backward down to the first layers' pre-activations
-        tot, gz1 = fused.pair_grads(k, la, lc, ain, cin, model.std, batch, clip, vcoef, ecoef, use_clipped_value_loss, surrogate_split=n_t, acc=acc, imgs=(ia, ic))
+        tot, gz1 = fused.pair_grads(k, la, lc, ain, cin, model.std, batch, clip, vcoef, ecoef, use_clipped_value_loss, surrogate_split=n_t, acc=acc, imgs=(ia, ic), diag=diag)
         # into the teacher encoder: d loss / d [latent | obs] of the actor on the teacher rows (the critic sees latent.detach()), through the normaliser
         g_in = _plain_input_grad(k, gz1[0][:n_t], la[0], ia[0])
         r = nn_.go2nn_l2norm_backward_rows(n_t)

@@ -360,6 +360,11 @@ class OnPolicyRunner:
         if mirror is not None:
             w.add_scalar("Loss/mirror", mirror, locs["it"])
         w.add_scalar("Loss/learning_rate", self.alg.learning_rate, locs["it"])
+        diag = getattr(self.alg, "diagnostics", None)          # (algorithm.diagnostics: the update's figures, Diag/<key>, for the CTS family Diag/<segment>/<key>)
+        if diag:
+            from ..algorithms._diag import log_items, report_lines
+            for tag, v in log_items(diag):
+                w.add_scalar("Diag/" + tag, v, locs["it"])
         if hasattr(ac, "std"):        # not for the MCP actor, whose std is an output of the network (on_policy_runner_cts.py:239-240)
             w.add_scalar("Policy/mean_noise_std", mean_std.item(), locs["it"])
         w.add_scalar("Perf/total_fps", fps, locs["it"])
@@ -379,6 +384,8 @@ class OnPolicyRunner:
             s += f"""{label:>{pad}} {v:.4f}\n"""
         if mirror is not None:
             s += f"""{'Mirror loss:':>{pad}} {mirror:.6f}\n"""
+        if diag:
+            s += report_lines(diag, pad)
         s += f"""{'Mean action noise std:':>{pad}} {mean_std.item():.2f}\n"""
         for _, label, rb, lb in groups:
             s += (f"""{'Mean %sreward:' % label:>{pad}} {statistics.mean(rb):.2f}\n"""

@@ -93,7 +93,7 @@ _RUNNER_OVERRIDES = ("max_iterations", "experiment_name", "run_name", "load_run"
 def update_cfg_from_args(env_cfg, cfg_train, args):
     """Command-line overrides onto the config objects (legged_gym/utils/helpers.py update_cfg_from_args): --num_envs onto the env config;
     --seed, --resume and the runner fields above onto the train config; the RoboGauge switches when the train config has that section (parsed and ignored: the service is
-    out of scope), --symmetry onto algorithm.symmetry, --normalize_obs onto runner.empirical_normalization, and next to them --evaluate / --eval_interval / --record / --robust / --ladder / --maneuvers / --sensors / --gait / --blackbox / --asymmetry / --ci / --ci_all onto the `evaluation` section."""
+    out of scope), --symmetry onto algorithm.symmetry, --diagnostics onto algorithm.diagnostics, --normalize_obs onto runner.empirical_normalization, and next to them --evaluate / --eval_interval / --record / --robust / --ladder / --maneuvers / --sensors / --gait / --blackbox / --asymmetry / --ci / --ci_all onto the `evaluation` section."""
     if env_cfg is not None and args.num_envs is not None:
         env_cfg.env.num_envs = args.num_envs
     if cfg_train is None:
@@ -114,6 +114,8 @@ def update_cfg_from_args(env_cfg, cfg_train, args):
                 setattr(gauge, field, given)
     if getattr(args, "symmetry", False):
         cfg_train.algorithm.symmetry = True          # (a CTS task's algorithm then refuses at construction: feed-forward PPO only)
+    if getattr(args, "diagnostics", False):
+        cfg_train.algorithm.diagnostics = True          # (a recurrent policy or MCP-CTS then refuses at construction)
     if getattr(args, "mirror_loss", None) is not None:          # the mirror loss is a term on the augmented mini-batches: the flag switches augmentation on too
         cfg_train.algorithm.mirror_loss_coef = args.mirror_loss
         cfg_train.algorithm.symmetry = True
@@ -193,6 +195,9 @@ def get_args(argv=None):
                    "evaluation.bootstrap_all = True")
     p.add_argument("--symmetry", action="store_true", default=False, help="train every PPO mini-batch on its left-right mirror image too (feed-forward PPO only): "
                    "algorithm.symmetry = True")
+    p.add_argument("--diagnostics", action="store_true", default=False, help="log the update's diagnostics as Diag/*: clip fraction, approximate and analytic KL, explained "
+                   "variance, ratio and advantage statistics, gradient norm and clipped share, with their first- and last-epoch values; computed on the device inside the "
+                   "update, training is bit for bit unchanged (feed-forward PPO and the CTS family): algorithm.diagnostics = True")
     p.add_argument("--mirror_loss", type=float, default=None, metavar="COEF", help="add COEF x the mean squared gap between the policy's answer to an observation and the "
                    "mirrored answer to its mirror image to the PPO loss (feed-forward PPO only; switches --symmetry on): algorithm.mirror_loss_coef = COEF")
     p.add_argument("--normalize_obs", action="store_true", default=False, help="normalise both observation streams by their running mean and standard deviation "

@@ -778,6 +778,66 @@ int32_t go2nn_mirror_loss_cols(int32_t A, int32_t K);
 int go2nn_mirror_loss_check_table(const int16_t* host_perm, const float* host_sign, int32_t A);
 int go2nn_mirror_loss(const Go2nnMirrorLoss* a, void* stream);
 
+/* ---- the update's diagnostics: what a PPO user reads to find out why a run stalls — clip fraction, KL, explained variance, gradient norm — computed on the device
+ * inside the captured update (go2_rl_gym_amd/rsl_rl/algorithms/_diag.py, `algorithm.diagnostics`; csrc/go2nn_diag.h).  READ-ONLY: nothing training reads is written.
+ * ADDED WITHIN ABI 7: four new entry points, one struct and one enum, nothing existing changes, GO2NN_ABI_VERSION stays 7.
+ * Per mini-batch step and per SEGMENT of its rows (surrogate_split = 0: one segment, all rows; n > 0: rows [0, n) and rows [n, B), the CTS teacher / student rows) one
+ * row of GO2NN_DIAG_NUM fp64 columns.  For row i, with mu = y_a W_mu^T + b_mu and v = y_c w_v + b_v (the fp32 dot products of go2nn_ppo_heads), all in fp32:
+ *   lp  = sum_j [-(a_j - mu_j)^2 / (2 std_j^2) - log std_j - log sqrt(2 pi)]        the log-probability of the stored action
+ *   lr  = lp - old_logp,   rho = exp(lr)
+ *   kl  = sum_j [log(std_j / old_sigma_j + 1e-5) + (old_sigma_j^2 + (old_mu_j - mu_j)^2) / (2 std_j^2) - 1 / 2]      (go2nn_ppo_heads' expression for its mean KL)
+ *   err = returns - v
+ * and every column is the fp64 sum (or extremum) of the rows' fp32 terms: */
+enum {
+  GO2NN_DIAG_ROWS = 0,        /* rows of the segment */
+  GO2NN_DIAG_RATIO_CLIPPED,   /* rows with |rho - 1| > clip */
+  GO2NN_DIAG_RATIO_SUM,       /* sum rho */
+  GO2NN_DIAG_LOGRATIO_SUM,    /* sum lr */
+  GO2NN_DIAG_K3_SUM,          /* sum (rho - 1) - lr */
+  GO2NN_DIAG_KL_SUM,          /* sum kl */
+  GO2NN_DIAG_KL_MAX,          /* max kl */
+  GO2NN_DIAG_ADV_SUM,         /* sum adv (the advantages as the mini-batch holds them) */
+  GO2NN_DIAG_ADV_SQ,          /* sum adv^2 */
+  GO2NN_DIAG_ADV_POS,         /* rows with adv > 0 */
+  GO2NN_DIAG_VERR_SUM,        /* sum err */
+  GO2NN_DIAG_VERR_SQ,         /* sum err^2 */
+  GO2NN_DIAG_VERR_ABS_MAX,    /* max |err| */
+  GO2NN_DIAG_RET_SUM,         /* sum returns */
+  GO2NN_DIAG_RET_SQ,          /* sum returns^2 */
+  GO2NN_DIAG_VALUE_CLIPPED,   /* rows with |v - old_values| > clip */
+  GO2NN_DIAG_RATIO_MAX,       /* max rho */
+  GO2NN_DIAG_RATIO_MIN,       /* min rho */
+  GO2NN_DIAG_NUM
+};
+/* go2nn_ppo_diag: two plain launches (capturable) on the stream of go2nn_ppo_heads, behind it.  The pass streams y_a, y_c [B, K] and the per-row inputs of
+ * go2nn_ppo_heads once (GO2NN_DIAG_PASS_ROWS rows per workgroup, loads dense along K) and leaves per-workgroup partial rows in `partials`:
+ * go2nn_ppo_diag_rows(B, A, K) x segments x GO2NN_DIAG_NUM doubles, segments = surrogate_split > 0 ? 2 : 1.  The finish, one block, combines them in increasing row
+ * order, writes table[*cursor] ([slots][segments][GO2NN_DIAG_NUM]) and advances the device-side cursor by one; a cursor outside [0, slots) writes nothing and stays.
+ * The caller zeroes the cursor once per update.  No atomics, fixed order: two launches give the same bits.
+ * GO2NN_EINVAL, with nothing written, for a null struct or pointer, B < 1, A outside [1, 16], K not a multiple of 4 in [4, 256], surrogate_split outside [0, B),
+ * slots < 1. */
+#define GO2NN_DIAG_PASS_ROWS 48
+typedef struct Go2nnPpoDiag {
+  const float *y_a, *y_c, *w_mu, *b_mu, *w_v, *b_v, *std, *actions, *old_mu, *old_sigma, *old_logp, *adv, *old_values, *returns;      /* as Go2nnPpoHeads */
+  double* partials;            /* go2nn_ppo_diag_rows x segments x GO2NN_DIAG_NUM */
+  double* table;               /* [slots][segments][GO2NN_DIAG_NUM] */
+  int32_t* cursor;             /* one int32 in the buffers' memory space */
+  int32_t B, A, K, surrogate_split, slots;
+  float clip;
+} Go2nnPpoDiag;
+int32_t go2nn_ppo_diag_rows(int32_t B, int32_t A, int32_t K);
+int go2nn_ppo_diag(const Go2nnPpoDiag* a, void* stream);
+/* go2nn_grad_sqnorm: out[*cursor] = sum over `count` tensors (1 .. GO2NN_GRAD_SQNORM_MAX, the limit of go2sim_adam_clip_step) of the squares of their numel[i]
+ * floats — the squared L2 norm that clip_grad_norm_ sees, BEFORE clipping — with the squares and every sum in fp64, then the cursor advances by one; a cursor outside
+ * [0, slots) writes nothing and stays.  `grads` and `numel` are HOST arrays (of device pointers / of sizes): they travel by value in the kernel arguments.  Two plain
+ * launches (capturable), a two-stage fixed-order reduction: `partials` holds go2nn_grad_sqnorm_rows(numel, count) doubles (one per GO2NN_GRAD_SQNORM_CHUNK floats of
+ * every tensor).  GO2NN_EINVAL, with nothing written, for a null pointer, count outside [1, GO2NN_GRAD_SQNORM_MAX], a numel < 1 (or above
+ * INT32_MAX - GO2NN_GRAD_SQNORM_CHUNK: the kernel's element index is an int), slots < 1. */
+#define GO2NN_GRAD_SQNORM_MAX 48
+#define GO2NN_GRAD_SQNORM_CHUNK 4096
+int32_t go2nn_grad_sqnorm_rows(const int32_t* host_numel, int32_t count);
+int go2nn_grad_sqnorm(const float* const* host_grads, const int32_t* host_numel, int32_t count, double* partials, double* out, int32_t* cursor, int32_t slots, void* stream);
+
 /* ---- the evaluator's left-right asymmetry scores: how far is the policy from equivariant on the states it visits, and does the robot load its left and right legs
  * equally (go2_rl_gym_amd/utils/evaluator.py, `evaluation.asymmetry`; the tables: go2_rl_gym_amd/utils/symmetry.py; csrc/go2nn_asym.h).
  * ADDED WITHIN ABI 7: three new entry points, nothing existing changes, GO2NN_ABI_VERSION stays 7.
