@@ -310,6 +310,46 @@ def obs_norm_update(lib, table, state, n, eps, mean32, inv32, stream=None):
         raise RuntimeError("go2nn_obs_norm_update failed: %s" % lib.go2nn_last_error().decode())
 
 
+GO2NN_VALUE_NORM_ROWS = 1024          # include/go2nn.h: elements per block of go2nn_value_norm_apply = per row of its partial table
+
+
+def value_norm_apply(lib, values, returns, stat32, partials=None, stream=None):
+    """values, returns: fp32 views of n contiguous floats each, normalised in place by stat32 = mean32 | std32 | inv32; partials fp64 [partial_rows(n), 2] or None
+    (go2nn_value_norm_apply)"""
+    n = int(values.numel())
+    for t in (values, returns, stat32):
+        assert t.is_contiguous() and t.dtype == torch.float32 and t.device == values.device, "contiguous fp32 tensors on one device"
+    assert returns.numel() == n and stat32.numel() == 3
+    if partials is not None:
+        assert partials.is_contiguous() and partials.dtype == torch.float64 and partials.device == values.device and partials.numel() == -(-n // GO2NN_VALUE_NORM_ROWS) * 2, \
+            "partials: fp64 [partial_rows(n), 2]"
+    if lib.go2nn_value_norm_apply(values.data_ptr(), returns.data_ptr(), n, stat32.data_ptr(), partials.data_ptr() if partials is not None else None, stream) != 0:
+        raise RuntimeError("go2nn_value_norm_apply failed: %s" % lib.go2nn_last_error().decode())
+
+
+def value_norm_update(lib, partials, state, n, eps, stat32, w_last=None, b_last=None, stream=None):
+    """partials fp64 [rows, 2] merged into state fp64 [3] = count | mean | M2, stat32 rewritten; w_last [1, K] / b_last [1] (the critic's last layer): output preservation
+    (go2nn_value_norm_update)"""
+    assert partials.is_contiguous() and partials.dtype == state.dtype == torch.float64 and state.numel() == 3 and stat32.numel() == 3 and stat32.dtype == torch.float32
+    K = 0
+    if w_last is not None:
+        assert w_last.is_contiguous() and b_last.is_contiguous() and w_last.dtype == b_last.dtype == torch.float32 and b_last.numel() == 1 and w_last.shape[0] == 1
+        K = int(w_last.numel())
+    if lib.go2nn_value_norm_update(partials.data_ptr(), int(partials.numel() // 2), state.data_ptr(), float(n), float(eps), stat32.data_ptr(),
+                                   w_last.data_ptr() if w_last is not None else None, b_last.data_ptr() if w_last is not None else None, K, stream) != 0:
+        raise RuntimeError("go2nn_value_norm_update failed: %s" % lib.go2nn_last_error().decode())
+
+
+def value_head_fold(lib, w, b, stat32, w_out, b_out, stream=None):
+    """(w [1, K], b [1]) of a critic's last layer -> (w std32, b std32 + mean32) in the scratch pair (go2nn_value_head_fold)"""
+    K = int(w.numel())
+    for t in (w, b, stat32, w_out, b_out):
+        assert t.is_contiguous() and t.dtype == torch.float32 and t.device == w.device
+    assert b.numel() == 1 and w_out.numel() == K and b_out.numel() == 1 and stat32.numel() == 3
+    if lib.go2nn_value_head_fold(w.data_ptr(), b.data_ptr(), K, stat32.data_ptr(), w_out.data_ptr(), b_out.data_ptr(), stream) != 0:
+        raise RuntimeError("go2nn_value_head_fold failed: %s" % lib.go2nn_last_error().decode())
+
+
 def trace_env_ids(env_ids, num_envs):
     """the tracked robots of go2nn_trace_record as the kernel needs them -> int32 numpy [K], strictly increasing, each in [0, num_envs).  The kernel cannot report a bad
     index (it would read outside the buffers), so anything else raises here."""
@@ -425,6 +465,10 @@ def bind(path):
     lib.go2nn_obs_norm_partial_rows.argtypes = [C.c_int32]          # (within ABI 7) empirical observation normalisation
     lib.go2nn_obs_norm_apply.argtypes = [C.POINTER(Go2nnObsNormJob), C.c_int32, C.c_int32, C.c_void_p]
     lib.go2nn_obs_norm_update.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.go2nn_value_norm_partial_rows.argtypes = [C.c_int32]          # (within ABI 7) value normalisation
+    lib.go2nn_value_norm_apply.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.go2nn_value_norm_update.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+    lib.go2nn_value_head_fold.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     if lib.go2nn_abi_version() != GO2NN_ABI_VERSION:
         raise RuntimeError("%s: ABI version %d, expected %d" % (path, lib.go2nn_abi_version(), GO2NN_ABI_VERSION))
     return lib
@@ -466,8 +510,10 @@ class PackedMlp:
     """One MLP's parameters as the kernels read them: the Go2nnMlp descriptor (pointers to the LIVE parameter tensors) and the packed operand
     buffer, refreshed by pack() — one small launch — whenever the parameters have changed (once per rollout: they only change in update())."""
 
-    def __init__(self, lib, seq, linears=None):
-        """seq: an nn.Sequential of Linear / ELU; or linears: the Linear modules of such a stack (wherever they live: nested containers, a normaliser behind them)"""
+    def __init__(self, lib, seq, linears=None, fold=None):
+        """seq: an nn.Sequential of Linear / ELU; or linears: the Linear modules of such a stack (wherever they live: nested containers, a normaliser behind them).
+        fold: the fp32 [3] stat32 of a ValueNormalization (modules/normalizer.py) — the scalar last layer is read from a scratch pair (W std32, b std32 + mean32) that
+        pack() refills from the live parameters and stat32 with ONE go2nn_value_head_fold launch in front of go2nn_pack: the kernels answer in raw units"""
         layers = mlp_layers(seq) if linears is None else [(m.weight, m.bias) for m in linears]
         if layers is not None and (len(layers) > GO2NN_MAX_LAYERS or max([layers[0][0].shape[1]] + [w.shape[0] for w, _ in layers]) > GO2NN_MAX_WIDTH):
             layers = None
@@ -481,6 +527,14 @@ class PackedMlp:
             assert w.is_contiguous() and b.is_contiguous()
             self.desc.dims[l + 1] = w.shape[0]
             self.desc.weight[l], self.desc.bias[l] = w.data_ptr(), b.data_ptr()
+        self._live = [(w.data_ptr(), b.data_ptr()) for w, b in layers]
+        self.fold = None
+        if fold is not None:
+            w, b = layers[-1]
+            if w.shape[0] != 1 or fold.numel() != 3 or fold.dtype != torch.float32 or fold.device != w.device:
+                raise ValueError("a folded last layer: a scalar output and an fp32 [3] stat32 on the parameters' device")
+            self.fold = (fold, torch.zeros_like(w), torch.zeros_like(b))
+            self.desc.weight[len(layers) - 1], self.desc.bias[len(layers) - 1] = self.fold[1].data_ptr(), self.fold[2].data_ptr()
         n = lib.go2nn_packed_floats(C.byref(self.desc))
         if n <= 0:
             raise ValueError(lib.go2nn_last_error().decode())
@@ -493,11 +547,14 @@ class PackedMlp:
         return C.c_void_p(torch.cuda.current_stream(d).cuda_stream) if d.type == "cuda" else None
 
     def still_valid(self):
-        return all(self.desc.weight[l] == w.data_ptr() and self.desc.bias[l] == b.data_ptr() for l, (w, b) in enumerate(self.layers))
+        return all(self._live[l] == (w.data_ptr(), b.data_ptr()) for l, (w, b) in enumerate(self.layers))          # (the LIVE parameters, also of a folded last layer)
 
     def pack(self):
         if not self.still_valid():
             raise RuntimeError("the MLP's parameter tensors were re-allocated after the policy kernel was built (rebuild PolicyKernel)")
+        if self.fold is not None:
+            w, b = self.layers[-1]
+            value_head_fold(self.lib, w.detach(), b.detach(), self.fold[0], self.fold[1], self.fold[2], self._stream())
         rc = self.lib.go2nn_pack(C.byref(self.desc), C.c_void_p(self.packed.data_ptr()), self._stream())
         if rc != 0:
             raise RuntimeError("go2nn_pack failed: %s" % self.lib.go2nn_last_error().decode())
@@ -514,9 +571,10 @@ class PackedMlp:
 class PolicyKernel:
     """PPO.act (rsl_rl/algorithms/ppo.py:90-102) for an ActorCritic of two Linear/ELU MLPs and a state-independent std, as one launch."""
 
-    def __init__(self, lib, actor_critic):
+    def __init__(self, lib, actor_critic, value_fold=None):
+        """value_fold: stat32 of the value normaliser — the critic's packed weights answer in raw units (PackedMlp(fold=...))"""
         self.lib, self.ac = lib, actor_critic
-        self.actor, self.critic = PackedMlp(lib, actor_critic.actor), PackedMlp(lib, actor_critic.critic)
+        self.actor, self.critic = PackedMlp(lib, actor_critic.actor), PackedMlp(lib, actor_critic.critic, fold=value_fold)
         if self.actor.out_dim > 32 or self.critic.out_dim != 1:
             raise ValueError("head: up to 32 actions and a scalar value")
 
@@ -551,11 +609,11 @@ class PolicyKernelCTS:
     the sampling head (go2nn_policy_act_latent).  plan: modules/fused_cts.py:CtsPlan (which Linear modules make up the four networks); a model whose student encoder
     is not a plain MLP (the MoE variants) leaves the student rows of the latent to the caller."""
 
-    def __init__(self, lib, model, plan, teacher_idx, student_idx):
+    def __init__(self, lib, model, plan, teacher_idx, student_idx, value_fold=None):
         self.lib, self.model, self.L = lib, model, plan.L
         self.enc_t = PackedMlp(lib, None, linears=plan.teacher)
         self.enc_s = PackedMlp(lib, None, linears=plan.student) if plan.student is not None else None
-        self.actor, self.critic = PackedMlp(lib, None, linears=plan.actor), PackedMlp(lib, None, linears=plan.critic)
+        self.actor, self.critic = PackedMlp(lib, None, linears=plan.actor), PackedMlp(lib, None, linears=plan.critic, fold=value_fold)          # (value_fold: as PolicyKernel)
         if self.actor.out_dim > 32 or self.critic.out_dim != 1:
             raise ValueError("head: up to 32 actions and a scalar value")
         self.ti, self.si = teacher_idx.to(torch.int32).contiguous(), student_idx.to(torch.int32).contiguous()

@@ -255,6 +255,10 @@ class LeggedRobotCfgPPO(BaseConfig):
         symmetry = False          # train every mini-batch on its left-right mirror image too (utils/symmetry.py; feed-forward PPO only; --symmetry)
         mirror_loss_coef = 0.0    # > 0 (--mirror_loss COEF, needs symmetry): add COEF x mean((pi(o) - M_a pi(M_o o))^2) over the mini-batch to the PPO loss; feed-forward PPO only
         diagnostics = False       # True (--diagnostics): per mini-batch step clip fraction, KL, explained variance, ratio / advantage statistics and the gradient norm in front of the clip, computed on the device inside the update and logged as Diag/* (rsl_rl/algorithms/_diag.py); read-only, the weights are bit for bit those of the key-off run; feed-forward PPO and the CTS family (not MCP-CTS)
+        normalize_value = False            # True (--normalize_value): the critic predicts returns normalised by their running mean / std, so the value clip and the value loss are in units of the returns' std (rsl_rl/modules/normalizer.py:ValueNormalization; README: value normalisation); feed-forward PPO and the CTS family, one rank
+        normalize_value_eps = 1e-2         # v^ = (v - mean) / (std + eps)
+        normalize_value_until = None       # no rollout is merged once this many returns have been seen; None: never stops
+        normalize_value_preserve = False   # True: when the statistics move, the critic's last layer is rewritten so that every raw value stays what it was (PopArt's step; Adam's moments are not rescaled); which default learns better has not been measured
 
     class runner:
         policy_class_name = "ActorCritic"
@@ -352,6 +356,10 @@ class LeggedRobotCfgCTS(BaseConfig):
         max_grad_norm = 1.0
         teacher_env_ratio = 0.75
         diagnostics = False       # True (--diagnostics): the update's diagnostics as in LeggedRobotCfgPPO.algorithm, per segment (teacher rows, student rows, all) and per optimizer; MCP-CTS (a state-dependent std) refuses
+        normalize_value = False            # True (--normalize_value): value normalisation as in LeggedRobotCfgPPO.algorithm, for every CTS-family class
+        normalize_value_eps = 1e-2
+        normalize_value_until = None
+        normalize_value_preserve = False   # (AC-MoE and Dual-MoE, whose critics mix several value heads, refuse it)
 
     class runner:
         policy_class_name = "ActorCriticCTS"

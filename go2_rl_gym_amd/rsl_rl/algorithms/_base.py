@@ -52,6 +52,10 @@ class _RolloutHeads:
     _pk = None                  # the fused policy kernel of the rollout: None = not looked for yet, False = not applicable, else the kernel (_policy_kernel() of the subclass decides)
     _pk_packed = False          # the policy kernel's packed weights are those of the current parameters (they change in update() and when a checkpoint is loaded)
     _pk_recorded = False        # the rollout last RUN THROUGH PYTHON (eager, or while being captured) packed at its first step: what a replay of that capture does too
+    _vn = None                  # value normalisation (modules/normalizer.py:ValueNormalization) when `algorithm.normalize_value` is on; None: nothing is loaded, allocated or launched
+    _vn_state = None            # its formulation and buffers, made at the first compute_returns (_vn_setup)
+    _vn_merged = True           # this update has merged its rollout's moments (update() clears it: a replayed compute_returns graph never passes through Python)
+    return_stats = None         # (mean, std) of the raw returns as the last update left them: Train/return_mean, Train/return_std
     _diag = None                # the update's diagnostics (_diag.py:UpdateDiagnostics) when `algorithm.diagnostics` is on; None: nothing is loaded, allocated or launched
 
     # ------------------------------------------------------------------ construction
@@ -118,6 +122,132 @@ class _RolloutHeads:
     def diagnostics_grad_sq(self):
         """numpy [steps, optimizers]: the squared gradient norm in front of the clip; None with the key off"""
         return None if self._diag is None else self._diag.host_grad_sq
+
+    # ------------------------------------------------------------------ value normalisation (`algorithm.normalize_value`; off: every hook below is one `is None` test)
+    # The critic's output is v^ = (v - mean) / std of the raw GAE returns' running statistics.  The ROLLOUT stores raw values v = v^ std32 + mean32 — the time-out
+    # bootstrap, GAE and the advantage normalisation run unchanged in raw units —: the fused policy kernels read a critic whose packed last layer is folded
+    # (_nn.py:PackedMlp(fold=...), one go2nn_value_head_fold launch in front of go2nn_pack, once per rollout), the torch formulations state v^ * std32 + mean32
+    # (_vn_raw).  BEHIND GAE one go2nn_value_norm_apply launch normalises `values` and `returns` in place and leaves the raw returns' moments: the update reads
+    # normalised rows and does not change.  The statistics are frozen inside an iteration; ONE go2nn_value_norm_update launch behind the last optimizer step merges the
+    # moments (and, with normalize_value_preserve, rewrites the critic's last layer so that every raw value stays what it was).  The eager mode, a rollout without the
+    # library (fused_rollout off) and GO2_FUSED_POLICY=0 state all of it in torch (modules/normalizer.py): the numerical yardstick.  Tests hand in the host build
+    # (nn_lib) to run the kernels on the CPU.
+    def _init_value_norm(self, net, normalize_value=False, eps=1e-2, until=None, preserve=False):
+        """switches value normalisation on when the key is set or the module already has the child `value_normalizer` (a loaded checkpoint brought it)"""
+        if not normalize_value and getattr(net, "value_normalizer", None) is None:
+            return
+        if getattr(net, "is_recurrent", False):
+            raise NotImplementedError("algorithm.normalize_value with a recurrent policy is not implemented: its heads live in modules/fused_rnn.py, where the value "
+                                      "never passes the sites that denormalise it")
+        if _world() > 1 or _collectives_on() or os.environ.get("GO2_FORCE_COLLECTIVES", "0") == "1":
+            raise NotImplementedError("algorithm.normalize_value trains on one rank only (the three fp64 moments of the returns would need an all-reduce)")
+        from ..modules.normalizer import attach_value_normalizer
+        had = getattr(net, "value_normalizer", None) is not None
+        vn = attach_value_normalizer(net, 1e-2 if eps is None else eps, until, preserve)
+        if had and normalize_value:          # (the child came with a checkpoint: the run's own cap and preservation switch hold, eps travels with the statistics)
+            vn.until, vn.preserve = (None if until is None else float(until)), bool(preserve)
+        self._vn, self._vn_state, self._vn_merged = vn, None, True
+        if vn.preserve:
+            self._vn_last_layer()          # (refuses here, not at the first merge)
+        # the policy kernel is rebuilt with (or without) the folded critic
+        self._pk, self._pk_packed, self._pk_recorded = None, False, False
+
+    def enable_value_norm(self, eps=1e-2, until=None, preserve=False):
+        """(runner.load) a checkpoint carries value_normalizer.*: the child is attached and this algorithm continues in normalised units, whatever its config said"""
+        if self._vn is None:
+            self._init_value_norm(self.actor_critic, True, eps, until, preserve)
+        return self._vn
+
+    def value_norm_changed(self):
+        """the statistics were loaded: the host's copy of count is re-read (the normaliser does that itself), nothing of an earlier rollout is merged into them"""
+        self._vn_merged = True
+
+    def _vn_last_layer(self):
+        """-> (weight [1, K], bias [1]) of the critic's last layer, for output preservation"""
+        critic = getattr(self.actor_critic, "critic", None)
+        lin = [m for m in critic.modules() if isinstance(m, nn.Linear)] if isinstance(critic, nn.Module) else []
+        if hasattr(self.actor_critic, "critic_experts") or not lin or lin[-1].out_features != 1 or lin[-1].bias is None:
+            raise NotImplementedError("algorithm.normalize_value_preserve needs a critic that ends in ONE scalar Linear layer (%s mixes several value heads)"
+                                      % type(self.actor_critic).__name__)
+        return lin[-1].weight, lin[-1].bias
+
+    def _vn_library(self):
+        """the library of the three launches, or None: the torch statement.  The kernels serve the graph mode on the library's rollout; a handed-in nn_lib (tests: the
+        host build) runs them in any mode"""
+        if self._vn is None or not self.fused_rollout:
+            return None
+        lib = getattr(self, "nn_lib", None)
+        if lib is None and self.use_graphs and str(self.device).startswith("cuda"):
+            from ... import _nn
+            lib = _nn.load_nn()          # (missing on a GPU is an error: no quiet torch fallback)
+        return lib
+
+    def _vn_fold(self):
+        """-> stat32 for the policy kernel's folded critic, or None (off / the torch formulation, which denormalises the kernel's rows itself)"""
+        return self._vn.stat32 if self._vn_library() is not None else None
+
+    def _vn_raw(self, v):
+        """the torch statement: a normalised value v^ (what the critic module answers) -> the raw value"""
+        return v if self._vn is None else self._vn.denormalize(v.detach())
+
+    def _vn_raw_kernel(self, v, pk):
+        """a value the policy kernel pk computed on its packed critic: raw already when that critic is folded"""
+        return v if (self._vn is None or pk.critic.fold is not None) else self._vn.denormalize(v)
+
+    def _vn_rows_raw(self, pk, s):
+        """the policy kernel wrote step s's values into the storage row: raw already when its critic is folded, else denormalised there (torch)"""
+        if self._vn is not None and pk.critic.fold is None:
+            row = self.storage.values[s]
+            row.copy_(self._vn.denormalize(row))
+
+    def _vn_setup(self):
+        st, vs = self.storage, self._vn_state
+        if vs is not None and vs["storage"] is st:
+            return vs
+        T, N = st.num_transitions_per_env, st.num_envs
+        for t in (st.values, st.returns):
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != T * N:
+                raise ValueError("value normalisation: contiguous fp32 [T, N, 1] values and returns")
+        lib = self._vn_library()
+        vs = self._vn_state = {"storage": st, "lib": lib, "n": T * N}
+        if lib is not None:
+            vs["partials"] = torch.zeros(int(lib.go2nn_value_norm_partial_rows(T * N)), 2, dtype=torch.float64, device=st.returns.device)
+        else:
+            vs["raw"] = torch.empty_like(st.returns)
+        return vs
+
+    def _vn_after_gae(self):
+        """behind storage.compute_returns (inside the captured compute_returns graph): values and returns become normalised rows, the raw returns' moments are kept"""
+        if self._vn is None:
+            return
+        vs, st, vn = self._vn_setup(), self.storage, self._vn
+        if vs["lib"] is not None:
+            from ... import _nn
+            _nn.value_norm_apply(vs["lib"], st.values.view(-1), st.returns.view(-1), vn.stat32, vs["partials"], self._stream(st.returns))
+        else:
+            vs["raw"].copy_(st.returns)
+            st.values.copy_(vn.normalize(st.values))
+            st.returns.copy_(vn.normalize(st.returns))
+
+    def _vn_finish(self):
+        """once per update(), behind its last optimizer step: the rollout and the update of this iteration both ran on the statistics the iteration began with.  The
+        `until` cap is the host's decision: count grows by T N per iteration, no device read"""
+        vn = self._vn
+        if vn is None or self._vn_merged:
+            return
+        self._vn_merged = True
+        vs = self._vn_setup()
+        if vn.accepts():
+            last = self._vn_last_layer() if vn.preserve else None
+            if vs["lib"] is not None:
+                from ... import _nn
+                _nn.value_norm_update(vs["lib"], vs["partials"], vn.state, vs["n"], vn.eps, vn.stat32, last[0] if last else None, last[1] if last else None,
+                                      self._stream(vn.state))
+                vn.note_merged(vs["n"])
+            else:
+                vn.merge(vs["raw"], last)
+        if not self.use_graphs:          # (the eager mode reads every loss with .item() already; graph mode: _read_back)
+            self.return_stats = tuple(vn.stat32[:2].tolist())
 
     def _make_adam(self, params, lr=None):
         """Adam over params (or param groups).  lr None: the policy's rate — in graph mode the device tensor the captured steps read and write; any other rate is
@@ -240,8 +370,11 @@ class _RolloutHeads:
 
     def _read_back(self, acc, n):
         """ONE device -> host read per update: -> the running sums `acc` over n mini-batch steps as means; the learning rate the device decided becomes learning_rate"""
-        out = torch.cat([acc / n, self._lr_t.reshape(1)]).tolist()
+        vn = self._vn          # (value normalisation: the returns' mean32 / std32 ride in the same read)
+        out = torch.cat([acc / n] + ([vn.stat32[:2].to(acc.dtype)] if vn is not None else []) + [self._lr_t.reshape(1)]).tolist()
         self.learning_rate = float(out.pop())
+        if vn is not None:
+            self.return_stats = (out.pop(-2), out.pop())
         return out
 
     # The update's permutation in graph mode: a keyed bijection computed on the device (include/go2sim_shuffle.h) under (seed, counter).  The seed follows
@@ -326,7 +459,7 @@ class _RolloutHeads:
     def _transition_to_rows(self, net, actions, values, s):
         """The eager formulation: `actions` just sampled from net's distribution and `values` become the transition and are copied into the storage rows.  -> actions"""
         st, t = self.storage, self.transition
-        t.actions, t.values = actions.detach(), values.detach()
+        t.actions, t.values = actions.detach(), self._vn_raw(values.detach())          # (value normalisation: the storage holds raw values during the rollout)
         t.actions_log_prob = net.get_actions_log_prob(t.actions).detach()
         t.action_mean, t.action_sigma = net.action_mean.detach(), net.action_std.detach()
         st.actions[s].copy_(t.actions)
@@ -341,7 +474,7 @@ class _RolloutHeads:
 
     def _act_head(self, mu, std, eps, value, s):
         st = self.storage
-        mu, eps, value = mu.detach().contiguous(), eps.contiguous(), value.detach().contiguous()
+        mu, eps, value = mu.detach().contiguous(), eps.contiguous(), self._vn_raw(value.detach()).contiguous()
         actions = torch.empty_like(mu)
         p = self._ptr
         self._call("go2sim_act_head", p(mu), p(std.detach()), p(eps), p(value), p(actions), p(st.actions[s]), p(st.mu[s]), p(st.sigma[s]),

@@ -24,7 +24,8 @@ class CTS(_RolloutHeads):
     def __init__(self, model, num_envs, history_length, num_learning_epochs=1, num_mini_batches=1, clip_param=0.2, gamma=0.998, lam=0.95,
                  value_loss_coef=1.0, entropy_coef=0.0, learning_rate=1e-3, student_encoder_learning_rate=1e-3, max_grad_norm=1.0,
                  use_clipped_value_loss=True, schedule="fixed", desired_kl=0.01, teacher_env_ratio=0.75, device="cpu", lib=None,
-                 use_graphs=None, fused_loss=None, fused_rollout=None, symmetry=False, mirror_loss_coef=0.0, diagnostics=False):
+                 use_graphs=None, fused_loss=None, fused_rollout=None, symmetry=False, mirror_loss_coef=0.0, diagnostics=False,
+                 normalize_value=False, normalize_value_eps=1e-2, normalize_value_until=None, normalize_value_preserve=False):
         if symmetry is not None and symmetry is not False:
             raise NotImplementedError("symmetry augmentation (algorithm.symmetry) is implemented for feed-forward PPO only: the CTS family's mirrored observation history "
                                       "is a different piece of work")
@@ -65,6 +66,8 @@ class CTS(_RolloutHeads):
             raise NotImplementedError("algorithm.diagnostics with a state-dependent std (MCP-CTS) is not implemented: the figures' log-probability and KL are those of "
                                       "go2nn_ppo_heads, one std per action dimension")
         self._init_diagnostics(diagnostics, ("teacher", "student"), [(self.optimizer1, ""), (self.optimizer2, "student_encoder_")])
+        # value normalisation (_base.py): every value of the family passes one of its sites (the policy kernel's folded critic, _act_head, _transition_to_rows)
+        self._init_value_norm(self.model, normalize_value, normalize_value_eps, normalize_value_until, normalize_value_preserve)
         self._sync_replicas(self.model)
 
     # the runner reaches the networks through either name
@@ -115,8 +118,10 @@ class CTS(_RolloutHeads):
         if pk is not None:
             # two launches (include/go2nn.h ABI 5): both encoders on their env subsets -> the env-ordered latent; actor + critic + sampling head on [latent | obs] / [latent | priv]
             latent = self._rollout_latent(pk, privileged_obs, history)
-            return self._transition_from_rows(pk.act(latent, obs, privileged_obs, self._rollout_noise(m, st, s), st.actions[s], st.mu[s], st.sigma[s],
-                                                     st.actions_log_prob[s].view(-1), st.values[s].view(-1)), s)
+            actions = pk.act(latent, obs, privileged_obs, self._rollout_noise(m, st, s), st.actions[s], st.mu[s], st.sigma[s], st.actions_log_prob[s].view(-1),
+                             st.values[s].view(-1))
+            self._vn_rows_raw(pk, s)
+            return self._transition_from_rows(actions, s)
         latent = self._latent_env_order(privileged_obs, history)
         if self.fused_rollout:
             mu, value = self._pair(lambda: m.policy_mean(latent, obs), lambda: m.evaluate_joint(privileged_obs, latent, obs), enabled=self._capture and not m.heads_share_parameters)
@@ -133,11 +138,12 @@ class CTS(_RolloutHeads):
     def compute_returns(self, last_privileged_obs, last_history, last_obs=None):
         pk = self._kernel()
         if pk is not None and self._pk_packed and all(x.is_contiguous() and x.dtype == torch.float32 for x in (last_privileged_obs, last_history)):
-            last_values = pk.value(self._rollout_latent(pk, last_privileged_obs, last_history), last_privileged_obs)      # on the weights packed for this rollout (unchanged since)
+            last_values = self._vn_raw_kernel(pk.value(self._rollout_latent(pk, last_privileged_obs, last_history), last_privileged_obs), pk)      # on the weights packed for this rollout (unchanged since)
         else:
             latent = self._latent_env_order(last_privileged_obs, last_history)
-            last_values = self.model.evaluate_joint(last_privileged_obs, latent, last_obs).detach()
+            last_values = self._vn_raw(self.model.evaluate_joint(last_privileged_obs, latent, last_obs).detach())
         self.storage.compute_returns(last_values, self.gamma, self.lam)
+        self._vn_after_gae()
 
     def _policy_kernel(self):
         """-> _nn.PolicyKernelCTS for this model, or None (GO2_FUSED_POLICY=0, or heads / encoders the kernel does not cover: modules/fused_cts.py:cts_plan).  On a
@@ -158,7 +164,7 @@ class CTS(_RolloutHeads):
                     fused._NN = saved
                 try:
                     if plan is not None:
-                        self._pk = _nn.PolicyKernelCTS(lib, self.model, plan, self.teacher_env_idxs, self.student_env_idxs)
+                        self._pk = _nn.PolicyKernelCTS(lib, self.model, plan, self.teacher_env_idxs, self.student_env_idxs, value_fold=self._vn_fold())
                         self._latent_buf = torch.zeros(self.storage.num_envs, plan.L, device=self.device)
                 except ValueError:          # (a width the kernel's LDS tiles do not hold)
                     self._pk = False
@@ -441,6 +447,7 @@ class CTS(_RolloutHeads):
             for _ in range(self._step_reps or self.num_learning_epochs):
                 for step in steps:
                     step()
+        self._vn_finish()          # (behind the last optimizer step, in front of the read-back's host synchronisation)
         n = self.num_learning_epochs * nmb
         acc = self._acc
         if self._plan is not None:      # the own steps' running sums, in the autograd formulation's slots
@@ -458,9 +465,11 @@ class CTS(_RolloutHeads):
 
     def update(self):
         self.parameters_changed()          # the optimizer steps below change the parameters: the next rollout re-packs
+        self._vn_merged = False
         if self._diag is not None:
             self._diag.begin()          # the slot cursors: zeroed once per update, in front of its first step
         out = self._update_graphs() if self.use_graphs else self._update_eager()
+        self._vn_finish()
         self._diag_finish()
         self.storage.clear()
         return out

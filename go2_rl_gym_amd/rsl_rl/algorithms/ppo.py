@@ -37,7 +37,8 @@ from ._graph import CapturedStep, GradBucket, all_captured
 class PPO(_RolloutHeads):
     def __init__(self, actor_critic, num_learning_epochs=1, num_mini_batches=1, clip_param=0.2, gamma=0.998, lam=0.95, value_loss_coef=1.0,
                  entropy_coef=0.0, learning_rate=1e-3, max_grad_norm=1.0, use_clipped_value_loss=True, schedule="fixed", desired_kl=0.01,
-                 device="cpu", lib=None, use_graphs=None, fused_loss=None, fused_rollout=None, symmetry=False, mirror_loss_coef=0.0, diagnostics=False):
+                 device="cpu", lib=None, use_graphs=None, fused_loss=None, fused_rollout=None, symmetry=False, mirror_loss_coef=0.0, diagnostics=False,
+                 normalize_value=False, normalize_value_eps=1e-2, normalize_value_until=None, normalize_value_preserve=False):
         mirror_loss_coef = 0.0 if mirror_loss_coef is None else float(mirror_loss_coef)
         if not (math.isfinite(mirror_loss_coef) and mirror_loss_coef >= 0.0):
             raise ValueError("PPO(mirror_loss_coef=...) takes a finite weight >= 0, got %r" % (mirror_loss_coef,))
@@ -84,6 +85,8 @@ class PPO(_RolloutHeads):
             raise NotImplementedError("algorithm.diagnostics with a recurrent policy is not implemented: its heads run in modules/fused_rnn.py, on the memories' outputs "
                                       "of whole episode segments")
         self._init_diagnostics(diagnostics, ("all",), [(self.optimizer, "")])
+        # value normalisation (_base.py): off, nothing is loaded, allocated or launched, and the state dict keeps its keys
+        self._init_value_norm(self.actor_critic, normalize_value, normalize_value_eps, normalize_value_until, normalize_value_preserve)
         self._sync_replicas(self.actor_critic)
 
     def rebind_lr(self):
@@ -138,8 +141,9 @@ class PPO(_RolloutHeads):
             pk = None
         self._ensure_packed(pk, s)
         if pk is not None:
-            return self._transition_from_rows(pk.act(x_a, x_c, self._rollout_noise(ac, st, s), st.actions[s], st.mu[s], st.sigma[s], st.actions_log_prob[s].view(-1),
-                                                     st.values[s].view(-1)), s)
+            actions = pk.act(x_a, x_c, self._rollout_noise(ac, st, s), st.actions[s], st.mu[s], st.sigma[s], st.actions_log_prob[s].view(-1), st.values[s].view(-1))
+            self._vn_rows_raw(pk, s)
+            return self._transition_from_rows(actions, s)
         mu, value = self._pair(lambda: ac.actor(x_a), lambda: self._value(x_c), enabled=self._capture)
         return self._act_head(mu, ac.std, self._rollout_noise(ac, st, s), value, s)
 
@@ -155,7 +159,7 @@ class PPO(_RolloutHeads):
             if lib is not None:
                 from ... import _nn
                 ok = _nn.PolicyKernel.supports(self.actor_critic) and self.storage is not None and (self.storage.privileged_observations is not None or self._rnn)
-            self._pk = _nn.PolicyKernel(lib, self.actor_critic) if ok else False
+            self._pk = _nn.PolicyKernel(lib, self.actor_critic, value_fold=self._vn_fold()) if ok else False
         return self._kernel()
 
     def process_env_step(self, rewards, dones, infos):
@@ -178,10 +182,11 @@ class PPO(_RolloutHeads):
                 x_c = self._obs_norm_last(on, x_c)
             pk = self._kernel()
             if pk is not None and self._pk_packed and x_c.is_contiguous() and x_c.dtype == torch.float32:
-                last_values = pk.critic.forward(x_c)          # the bootstrap value as ONE launch on the weights packed for this rollout (they have not changed since)
+                last_values = self._vn_raw_kernel(pk.critic.forward(x_c), pk)          # the bootstrap value as ONE launch on the weights packed for this rollout (they have not changed since)
             else:
-                last_values = self._value(x_c).detach()
+                last_values = self._vn_raw(self._value(x_c).detach())
         self.storage.compute_returns(last_values, self.gamma, self.lam)
+        self._vn_after_gae()
 
     # ------------------------------------------------------------------ update half (ppo.py:120-187)
     def _losses(self, obs_b, cobs_b, act_b, tv_b, adv_b, ret_b, old_lp_b, old_mu_b, old_sig_b):
@@ -443,6 +448,7 @@ class PPO(_RolloutHeads):
             for g in self._graph:
                 g()
         self._obs_norm_finish()          # (enqueued behind the last optimizer step and in front of the read-back's host synchronisation: no idle gap in front of it)
+        self._vn_finish()
         surrogate, value, *rest = self._read_back(self._acc, self.num_learning_epochs * nmb)
         if rest:
             self.mirror_loss = rest[0] / self.mirror_loss_coef
@@ -459,6 +465,7 @@ class PPO(_RolloutHeads):
     def update(self):
         self.parameters_changed()          # the optimizer steps below change the parameters: the next rollout re-packs
         self._on_merged = False
+        self._vn_merged = False
         if self._diag is not None:
             self._diag.begin()          # the slot cursors: zeroed once per update, in front of its first step
         if self._rnn and self.use_graphs and self._rnn_memory() is not None:
@@ -468,6 +475,7 @@ class PPO(_RolloutHeads):
         else:
             out = self._update_eager()
         self._obs_norm_finish()
+        self._vn_finish()
         self._diag_finish()
         self.storage.clear()
         return out

@@ -360,6 +360,10 @@ class OnPolicyRunner:
         if mirror is not None:
             w.add_scalar("Loss/mirror", mirror, locs["it"])
         w.add_scalar("Loss/learning_rate", self.alg.learning_rate, locs["it"])
+        ret = getattr(self.alg, "return_stats", None)          # (algorithm.normalize_value: the raw returns' running mean / std, read with the update's own read-back)
+        if ret is not None:
+            w.add_scalar("Train/return_mean", ret[0], locs["it"])
+            w.add_scalar("Train/return_std", ret[1], locs["it"])
         diag = getattr(self.alg, "diagnostics", None)          # (algorithm.diagnostics: the update's figures, Diag/<key>, for the CTS family Diag/<segment>/<key>)
         if diag:
             from ..algorithms._diag import log_items, report_lines
@@ -443,11 +447,28 @@ class OnPolicyRunner:
         getattr(self.alg, "set_shuffle_counter", lambda it: None)(d["iter"])          # graph mode's keyed permutation continues at the checkpoint's iteration
         return d["infos"]
 
+    def _load_value_norm(self, sd):
+        """A checkpoint that carries value_normalizer.* was trained in normalised units and continues in them: the child is attached and the algorithm switched on,
+        whatever this run's switch says.  One without them, loaded while the switch is on, starts from the initial statistics.  -> the keys load_state_dict may miss"""
+        ac, a = self.alg.actor_critic, self.alg_cfg
+        carries, has = any(k.startswith("value_normalizer.") for k in sd), getattr(ac, "value_normalizer", None) is not None
+        if carries and not has:
+            self.alg.enable_value_norm(a.get("normalize_value_eps", 1e-2), a.get("normalize_value_until"), a.get("normalize_value_preserve", False))
+        if carries or has:          # (a captured rollout holds the critic's packed weights as they were built, a captured compute_returns has or lacks the launch)
+            self._rollout_graph, self._returns_graph, self._eager_rollouts = None, None, 0
+            self.alg.value_norm_changed()
+        if has and not carries:
+            print("[go2_rl_gym_amd] the checkpoint carries no return statistics: value normalisation starts from its initial state (count 0, mean 0, var 1)")
+            ac.value_normalizer.set_state(0.0, 0.0, 1.0)
+            return tuple("value_normalizer." + k for k in ac.value_normalizer.state_dict())
+        return ()
+
     def _load_model(self, sd):
         """model_state_dict into the actor-critic.  A checkpoint that carries observation statistics brings them along whatever this run's switch says (the children are
         attached first: it carries what it needs to run); one without them, loaded while the switch is on, starts from the initial statistics; else as ever."""
         from ..modules.normalizer import normalizer_widths
         ac = self.alg.actor_critic
+        vn_missing = self._load_value_norm(sd)
         has, w = getattr(ac, "obs_normalizer", None) is not None, normalizer_widths(sd)
         if w is not None and not has:
             self._attach_normalizers(ac, shared=w[1] is None)
@@ -455,12 +476,17 @@ class OnPolicyRunner:
         if w is None and has:
             print("[go2_rl_gym_amd] the checkpoint carries no observation statistics: empirical normalisation starts from its initial state (count 0, mean 0, var 1)")
             res = ac.load_state_dict(sd, strict=False)
-            bad = [k for k in res.missing_keys if not k.startswith(("obs_normalizer.", "critic_obs_normalizer."))] + list(res.unexpected_keys)
+            bad = [k for k in res.missing_keys if not k.startswith(("obs_normalizer.", "critic_obs_normalizer.")) and k not in vn_missing] + list(res.unexpected_keys)
             if bad:
                 raise RuntimeError("Error(s) in loading state_dict for %s: missing or unexpected keys %s" % (type(ac).__name__, bad))
             for n in (ac.obs_normalizer, getattr(ac, "critic_obs_normalizer", None)):
                 if n is not None:
                     n.set_state(0.0, 0.0, 1.0)
+        elif vn_missing:
+            res = ac.load_state_dict(sd, strict=False)
+            bad = [k for k in res.missing_keys if k not in vn_missing] + list(res.unexpected_keys)
+            if bad:
+                raise RuntimeError("Error(s) in loading state_dict for %s: missing or unexpected keys %s" % (type(ac).__name__, bad))
         else:
             ac.load_state_dict(sd)
         if getattr(ac, "obs_normalizer", None) is not None:

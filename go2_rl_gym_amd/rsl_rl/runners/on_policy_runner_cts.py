@@ -114,7 +114,11 @@ class OnPolicyRunnerCTS(OnPolicyRunner):
 
     def load(self, path, load_optimizer=True):
         d = torch.load(path, map_location=self.device)
-        self.alg.model.load_state_dict(d["model_state_dict"])
+        sd = d["model_state_dict"]
+        vn_missing = self._load_value_norm(sd)          # (a checkpoint with value_normalizer.* switches value normalisation on: on_policy_runner.py)
+        res = self.alg.model.load_state_dict(sd, strict=not vn_missing)
+        if vn_missing and ([k for k in res.missing_keys if k not in vn_missing] or res.unexpected_keys):
+            raise RuntimeError("Error(s) in loading state_dict for %s: missing keys %s, unexpected keys %s" % (type(self.alg.model).__name__, res.missing_keys, res.unexpected_keys))
         self.alg.parameters_changed()          # (what the rollout's kernels hold packed is stale now)
         if load_optimizer:
             load_optimizer_state(self.alg.optimizer1, d["optimizer1_state_dict"])

@@ -93,7 +93,7 @@ _RUNNER_OVERRIDES = ("max_iterations", "experiment_name", "run_name", "load_run"
 def update_cfg_from_args(env_cfg, cfg_train, args):
     """Command-line overrides onto the config objects (legged_gym/utils/helpers.py update_cfg_from_args): --num_envs onto the env config;
     --seed, --resume and the runner fields above onto the train config; the RoboGauge switches when the train config has that section (parsed and ignored: the service is
-    out of scope), --symmetry onto algorithm.symmetry, --diagnostics onto algorithm.diagnostics, --normalize_obs onto runner.empirical_normalization, and next to them --evaluate / --eval_interval / --record / --robust / --ladder / --maneuvers / --sensors / --gait / --blackbox / --asymmetry / --ci / --ci_all onto the `evaluation` section."""
+    out of scope), --symmetry onto algorithm.symmetry, --diagnostics onto algorithm.diagnostics, --normalize_obs onto runner.empirical_normalization, --normalize_value onto algorithm.normalize_value, and next to them --evaluate / --eval_interval / --record / --robust / --ladder / --maneuvers / --sensors / --gait / --blackbox / --asymmetry / --ci / --ci_all onto the `evaluation` section."""
     if env_cfg is not None and args.num_envs is not None:
         env_cfg.env.num_envs = args.num_envs
     if cfg_train is None:
@@ -119,6 +119,8 @@ def update_cfg_from_args(env_cfg, cfg_train, args):
     if getattr(args, "mirror_loss", None) is not None:          # the mirror loss is a term on the augmented mini-batches: the flag switches augmentation on too
         cfg_train.algorithm.mirror_loss_coef = args.mirror_loss
         cfg_train.algorithm.symmetry = True
+    if getattr(args, "normalize_value", False):
+        cfg_train.algorithm.normalize_value = True          # (a recurrent policy or more than one rank then refuses at construction)
     if getattr(args, "normalize_obs", False):
         cfg_train.runner.empirical_normalization = True          # (a CTS or recurrent task, or --symmetry next to it, then refuses at construction: feed-forward PPO only)
     ev = getattr(cfg_train, "evaluation", None)
@@ -202,6 +204,8 @@ def get_args(argv=None):
                    "mirrored answer to its mirror image to the PPO loss (feed-forward PPO only; switches --symmetry on): algorithm.mirror_loss_coef = COEF")
     p.add_argument("--normalize_obs", action="store_true", default=False, help="normalise both observation streams by their running mean and standard deviation "
                    "(feed-forward PPO only; the statistics travel in the checkpoint): runner.empirical_normalization = True")
+    p.add_argument("--normalize_value", action="store_true", default=False, help="let the critic predict returns normalised by their running mean and standard deviation "
+                   "(feed-forward PPO and the CTS family, one rank; the statistics travel in the checkpoint): algorithm.normalize_value = True")
     p.add_argument("--record_steps", type=int, default=500, help="play.py --record: the last S steps of the rollout are kept")
     # flags contributed by isaacgym.gymutil.parse_arguments in the reference
     p.add_argument("--sim_device", type=str, default="cuda:0")

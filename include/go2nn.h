@@ -967,6 +967,30 @@ int32_t go2nn_obs_norm_partial_rows(int32_t N);          /* ceil(N / GO2NN_OBS_N
 int go2nn_obs_norm_apply(const Go2nnObsNormJob* jobs, int32_t n_jobs, int32_t N, void* stream);
 int go2nn_obs_norm_update(const double* table, int32_t steps, int32_t rows, int32_t D, double* state, double n, double eps, float* mean32, float* inv32, void* stream);
 
+/* ---- value normalisation: the critic predicts returns normalised by their running mean / std (go2_rl_gym_amd/rsl_rl/modules/normalizer.py:ValueNormalization,
+ * rsl_rl/algorithms/_base.py, `algorithm.normalize_value`; csrc/go2nn_value_norm.h).
+ * ADDED WITHIN ABI 7: four new entry points, nothing existing changes, GO2NN_ABI_VERSION stays 7.  All three launches are plain and capturable.
+ * stat32: fp32 [3] = mean32 | std32 | inv32 in the buffers' memory space, mean32 = (float) mean, std32 = (float) (sqrt(var) + eps), inv32 = (float) (1 / (sqrt(var) + eps)).
+ * go2nn_value_norm_apply: in place over the n floats of `values` and of `returns` (they must not overlap)
+ *   x <- (x - mean32) * inv32                 one fp32 subtraction, one fp32 product (no FMA can form), no clamp: the device, the host build, torch and numpy agree bit for bit
+ * A 256-lane block owns GO2NN_VALUE_NORM_ROWS consecutive elements; 16-byte accesses only where both pointers are 16-byte aligned.  partials == NULL: normalise only.
+ * Otherwise partials is fp64 [go2nn_value_norm_partial_rows(n), 2]: row b receives the sums of d and of d * d over elements [b * ROWS, (b + 1) * ROWS) of the RAW
+ * returns, d = (double) R - (double) mean32.  Fixed summation order, no atomics: two launches give the same bits.
+ * GO2NN_EINVAL, with nothing written, for a null values, returns or stat32, a pointer not aligned to a float, n < 1.
+ * go2nn_value_norm_update: one block.  state: fp64 [3] = count | mean | M2 (var = M2 / count; at count 0 M2 is not read: the initial var = 1 is forgotten at the first
+ * batch); n: the table's samples.  Reading the old stat32 first: S1, S2 = the rows' sums in increasing order; batch mean = mean32_old + S1 / n, batch M2 = S2 - S1^2 / n
+ * (floored at 0); Chan's pooled update into the state; stat32 rewritten.  w_last != NULL (output preservation): the critic's last layer, fp32 [K] and b_last fp32 [1], is
+ * rewritten W <- W sigma / sigma', b <- (sigma b + mu - mu') / sigma' with (mu, sigma) the old and (mu', sigma') the new mean32, std32: v * std32 + mean32 of every
+ * input stays what it was.  w_last == NULL: no preservation, b_last and K are not read.
+ * GO2NN_EINVAL, with nothing written, for a null partials, state or stat32, rows < 1, n or eps not finite and above 0, w_last given with b_last null or K < 1.
+ * go2nn_value_head_fold: w_out[k] = w[k] * std32 (k < K), b_out[0] = b[0] * std32 + mean32: the last layer of a critic whose packed operand buffer answers in raw units.
+ * GO2NN_EINVAL, with nothing written, for a null pointer or K < 1. */
+#define GO2NN_VALUE_NORM_ROWS 1024
+int32_t go2nn_value_norm_partial_rows(int32_t n);          /* ceil(n / GO2NN_VALUE_NORM_ROWS); 0 for n < 1 */
+int go2nn_value_norm_apply(float* values, float* returns, int32_t n, const float* stat32, double* partials, void* stream);
+int go2nn_value_norm_update(const double* partials, int32_t rows, double* state, double n, double eps, float* stat32, float* w_last, float* b_last, int32_t K, void* stream);
+int go2nn_value_head_fold(const float* w, const float* b, int32_t K, const float* stat32, float* w_out, float* b_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
