@@ -220,6 +220,11 @@ class Go2nnMirrorLoss(C.Structure):          # (within ABI 7) perm and sign None
                 ("B", C.c_int32), ("A", C.c_int32), ("K", C.c_int32), ("coef", C.c_float)]
 
 
+class Go2nnSmoothLoss(C.Structure):          # (within ABI 7) rows in block layout: r = b T n + t n + j
+    _fields_ = [("y_a", C.c_void_p), ("w_mu", C.c_void_p), ("b_mu", C.c_void_p), ("w", C.c_void_p), ("gz_a", C.c_void_p), ("partials", C.c_void_p),
+                ("blocks", C.c_int32), ("T", C.c_int32), ("n", C.c_int32), ("A", C.c_int32), ("K", C.c_int32), ("coef", C.c_float)]
+
+
 # the update's diagnostics: the columns of a table row in the order of the enum GO2NN_DIAG_* of include/go2nn.h (where the definitions are)
 DIAG_COLS = ("rows", "ratio_clipped", "ratio_sum", "logratio_sum", "k3_sum", "kl_sum", "kl_max", "adv_sum", "adv_sq", "adv_pos", "verr_sum", "verr_sq", "verr_abs_max",
              "ret_sum", "ret_sq", "value_clipped", "ratio_max", "ratio_min")
@@ -458,6 +463,11 @@ def bind(path):
     lib.go2nn_mirror_loss_cols.argtypes = [C.c_int32] * 2
     lib.go2nn_mirror_loss_check_table.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
     lib.go2nn_mirror_loss.argtypes = [C.POINTER(Go2nnMirrorLoss), C.c_void_p]
+    lib.go2nn_smooth_loss_rows.argtypes = [C.c_int32] * 5          # (within ABI 7) the temporal action-smoothness loss on env-block mini-batches
+    lib.go2nn_smooth_loss_cols.argtypes = [C.c_int32] * 2
+    lib.go2nn_smooth_loss_set_segments.argtypes = [C.c_int32]
+    lib.go2nn_smooth_loss.argtypes = [C.POINTER(Go2nnSmoothLoss), C.c_void_p]
+    lib.go2nn_smooth_indices.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
     lib.go2nn_ppo_diag_rows.argtypes = [C.c_int32] * 3          # (within ABI 7) the update's diagnostics
     lib.go2nn_ppo_diag.argtypes = [C.POINTER(Go2nnPpoDiag), C.c_void_p]
     lib.go2nn_grad_sqnorm_rows.argtypes = [C.c_void_p, C.c_int32]

@@ -253,6 +253,7 @@ class LeggedRobotCfgPPO(BaseConfig):
         desired_kl = 0.01
         max_grad_norm = 1.0
         symmetry = False          # train every mini-batch on its left-right mirror image too (utils/symmetry.py; feed-forward PPO only; --symmetry)
+        smooth_loss_coef = 0.0    # > 0 (--smooth_loss COEF): add COEF x mean((pi(o_t) - pi(o_t+1))^2) over successive steps of an episode to the PPO loss, on env-block mini-batches; feed-forward PPO only
         mirror_loss_coef = 0.0    # > 0 (--mirror_loss COEF, needs symmetry): add COEF x mean((pi(o) - M_a pi(M_o o))^2) over the mini-batch to the PPO loss; feed-forward PPO only
         diagnostics = False       # True (--diagnostics): per mini-batch step clip fraction, KL, explained variance, ratio / advantage statistics and the gradient norm in front of the clip, computed on the device inside the update and logged as Diag/* (rsl_rl/algorithms/_diag.py); read-only, the weights are bit for bit those of the key-off run; feed-forward PPO and the CTS family (not MCP-CTS)
         normalize_value = False            # True (--normalize_value): the critic predicts returns normalised by their running mean / std, so the value clip and the value loss are in units of the returns' std (rsl_rl/modules/normalizer.py:ValueNormalization; README: value normalisation); feed-forward PPO and the CTS family, one rank

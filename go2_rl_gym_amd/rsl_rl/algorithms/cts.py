@@ -25,13 +25,16 @@ class CTS(_RolloutHeads):
                  value_loss_coef=1.0, entropy_coef=0.0, learning_rate=1e-3, student_encoder_learning_rate=1e-3, max_grad_norm=1.0,
                  use_clipped_value_loss=True, schedule="fixed", desired_kl=0.01, teacher_env_ratio=0.75, device="cpu", lib=None,
                  use_graphs=None, fused_loss=None, fused_rollout=None, symmetry=False, mirror_loss_coef=0.0, diagnostics=False,
-                 normalize_value=False, normalize_value_eps=1e-2, normalize_value_until=None, normalize_value_preserve=False):
+                 normalize_value=False, normalize_value_eps=1e-2, normalize_value_until=None, normalize_value_preserve=False, smooth_loss_coef=0.0):
         if symmetry is not None and symmetry is not False:
             raise NotImplementedError("symmetry augmentation (algorithm.symmetry) is implemented for feed-forward PPO only: the CTS family's mirrored observation history "
                                       "is a different piece of work")
         if mirror_loss_coef is not None and mirror_loss_coef > 0:          # (the config reaches this class as **alg_cfg: 0.0 is accepted)
             raise NotImplementedError("the mirror loss (algorithm.mirror_loss_coef) is implemented for feed-forward PPO only: it is a term on the mini-batches that symmetry "
                                       "augmentation builds, which the CTS family does not have")
+        if smooth_loss_coef is not None and smooth_loss_coef > 0:
+            raise NotImplementedError("the smoothness loss (algorithm.smooth_loss_coef) is implemented for feed-forward PPO only: the CTS family's mini-batches are separate "
+                                      "draws of teacher and student samples, not blocks of whole environments")
         self.desired_kl, self.schedule, self.learning_rate = desired_kl, schedule, learning_rate
         self.history_length = history_length
         self.model = model

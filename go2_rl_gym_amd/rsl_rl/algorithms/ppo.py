@@ -38,10 +38,13 @@ class PPO(_RolloutHeads):
     def __init__(self, actor_critic, num_learning_epochs=1, num_mini_batches=1, clip_param=0.2, gamma=0.998, lam=0.95, value_loss_coef=1.0,
                  entropy_coef=0.0, learning_rate=1e-3, max_grad_norm=1.0, use_clipped_value_loss=True, schedule="fixed", desired_kl=0.01,
                  device="cpu", lib=None, use_graphs=None, fused_loss=None, fused_rollout=None, symmetry=False, mirror_loss_coef=0.0, diagnostics=False,
-                 normalize_value=False, normalize_value_eps=1e-2, normalize_value_until=None, normalize_value_preserve=False):
+                 normalize_value=False, normalize_value_eps=1e-2, normalize_value_until=None, normalize_value_preserve=False, smooth_loss_coef=0.0):
         mirror_loss_coef = 0.0 if mirror_loss_coef is None else float(mirror_loss_coef)
         if not (math.isfinite(mirror_loss_coef) and mirror_loss_coef >= 0.0):
             raise ValueError("PPO(mirror_loss_coef=...) takes a finite weight >= 0, got %r" % (mirror_loss_coef,))
+        smooth_loss_coef = 0.0 if smooth_loss_coef is None else float(smooth_loss_coef)
+        if not (math.isfinite(smooth_loss_coef) and smooth_loss_coef >= 0.0):
+            raise ValueError("PPO(smooth_loss_coef=...) takes a finite weight >= 0, got %r" % (smooth_loss_coef,))
         self.desired_kl, self.schedule, self.learning_rate = desired_kl, schedule, learning_rate
         self.actor_critic = actor_critic
         self.actor_critic.to(device)
@@ -76,6 +79,12 @@ class PPO(_RolloutHeads):
         if mirror_loss_coef > 0.0 and self._sym is None:
             raise ValueError("PPO(mirror_loss_coef > 0) is a term on the mirror-augmented mini-batches: it needs symmetry=mirror_tables(env_cfg) (algorithm.symmetry = True; "
                              "--mirror_loss sets both)")
+        # the temporal action-smoothness loss on env-block mini-batches (the `smoothness loss` section below): 0 = off, and then the mini-batches, every launch and the
+        # state dict are what they are without it.  smooth_loss: the last update's mean of L_smooth / coef over its mini-batch steps
+        self.smooth_loss_coef, self.smooth_loss, self._sl, self._sw, self._sw_all = smooth_loss_coef, 0.0, None, None, None
+        if smooth_loss_coef > 0.0 and self._rnn:
+            raise NotImplementedError("the smoothness loss with a recurrent policy is not implemented: its heads run in modules/fused_rnn.py, on the memories' outputs of "
+                                      "whole episode segments")
         # empirical observation normalisation: present iff the actor-critic has the children (the runner attaches them; a checkpoint that carries them too).  Absent:
         # nothing is loaded, allocated or launched.
         self._on_state, self._on_merged = None, False
@@ -100,6 +109,11 @@ class PPO(_RolloutHeads):
                 g["lr"] = self._lr_t
 
     def init_storage(self, num_envs, num_transitions_per_env, actor_obs_shape, critic_obs_shape, action_shape):
+        if self.smooth_loss_coef > 0.0:          # env-block mini-batches: whole environments, at least one pair of successive steps
+            if num_envs % self.num_mini_batches != 0:
+                raise ValueError("smooth_loss_coef > 0 takes mini-batches of whole environments: %d envs are not a multiple of %d mini-batches" % (num_envs, self.num_mini_batches))
+            if num_transitions_per_env < 2:
+                raise ValueError("smooth_loss_coef > 0 compares successive steps of a rollout: %d step per env holds no pair" % num_transitions_per_env)
         self.storage = RolloutStorage(num_envs, num_transitions_per_env, actor_obs_shape, critic_obs_shape, action_shape, self.device, lib=self.lib)
         if self._sym is not None:
             st = self.storage
@@ -198,6 +212,8 @@ class PPO(_RolloutHeads):
             self._diag_torch(mu_b, ac.std, val_b, act_b, tv_b, adv_b, ret_b, old_lp_b, old_mu_b, old_sig_b)
             if self.mirror_loss_coef > 0.0:
                 loss = loss + self._mirror_term(mu_b)
+            if self.smooth_loss_coef > 0.0:
+                loss = loss + self._smooth_term(mu_b)
             return loss, stats[1], stats[0], stats[2]
         ac.update_distribution(obs_b)     # the reference calls act() here and discards the sample (ppo.py:131)
         lp_b = ac.get_actions_log_prob(act_b)
@@ -206,23 +222,36 @@ class PPO(_RolloutHeads):
         self._diag_torch(ac.action_mean, ac.action_std, val_b, act_b, tv_b, adv_b, ret_b, old_lp_b, old_mu_b, old_sig_b)
         if self.mirror_loss_coef > 0.0:
             loss = loss + self._mirror_term(ac.action_mean)
+        if self.smooth_loss_coef > 0.0:
+            loss = loss + self._smooth_term(ac.action_mean)
         return loss, value_loss, surrogate_loss, kl_mean
 
     def _update_eager(self):
-        mean_value_loss, mean_surrogate_loss, mean_mirror = 0.0, 0.0, 0.0
-        batches = self._rnn_batches() if self._rnn else self.storage.mini_batch_generator(self.num_mini_batches, self.num_learning_epochs)
+        mean_value_loss, mean_surrogate_loss, mean_mirror, mean_smooth = 0.0, 0.0, 0.0, 0.0
+        if self._rnn:
+            batches = self._rnn_batches()
+        elif self.smooth_loss_coef > 0.0:          # all T steps of a slice of the permuted environments, time-major, and their pair weights
+            batches = self.storage.env_block_mini_batch_generator(self.num_mini_batches, self.num_learning_epochs)
+        else:
+            batches = self.storage.mini_batch_generator(self.num_mini_batches, self.num_learning_epochs)
         for batch in batches:
             if self._sym is not None:
                 batch = self._sym_batch(batch)
+            if self.smooth_loss_coef > 0.0:
+                self._sw = batch[11]
             loss, value_loss, surrogate_loss, kl_mean = self._rnn_losses(batch) if self._rnn else self._losses(*batch[:9])
             self._eager_step(loss, self.optimizer, self._params, kl_mean)
             mean_value_loss += value_loss.item()
             mean_surrogate_loss += surrogate_loss.item()
             if self.mirror_loss_coef > 0.0:
                 mean_mirror += self._ml.item()
+            if self.smooth_loss_coef > 0.0:
+                mean_smooth += self._sl.item()
         n = self.num_learning_epochs * self.num_mini_batches
         if self.mirror_loss_coef > 0.0:
             self.mirror_loss = mean_mirror / n
+        if self.smooth_loss_coef > 0.0:
+            self.smooth_loss = mean_smooth / n
         return mean_value_loss / n, mean_surrogate_loss / n
 
     # ---- symmetry augmentation ---------------------------------------------------------------------------------
@@ -319,6 +348,72 @@ class PPO(_RolloutHeads):
             self._ml_dev = _nn.mirror_loss_table_tensors(self._nn_library(), self._sym_table("act"), self.device)
         return (self.mirror_loss_coef,) + tuple(self._ml_dev)
 
+    # ---- smoothness loss ---------------------------------------------------------------------------------------
+    # The temporal half of CAPS on the policy's action mean (`smooth_loss_coef` > 0).  The update's mini-batches then are ENV BLOCKS — all T steps of a slice of the
+    # permuted environments, time-major: row t n + j (under symmetry augmentation followed by the mirror images' block) — instead of random rows, so rows (t, j) and
+    # (t + 1, j) are both ordinary PPO samples of the mini-batch and the actor's forward has already produced both answers: with w[t, j] = (dones[t, env j] == 0)
+    #     e[b, t, j, :] = w[t, j] (mu[b, t, j, :] - mu[b, t + 1, j, :])   (t < T - 1),        L_smooth = coef mean(e^2)   (masked pairs count as 0: a fixed denominator)
+    # costs no forward pass.  Both rows of a pair receive gradient, nothing is detached.  Eager mode: the torch expression below, the numerical
+    # yardstick.  Graph mode on the heads path: go2nn_smooth_loss (csrc/go2nn_smooth_loss.h), one launch behind go2nn_ppo_heads (and go2nn_mirror_loss); the mini-batch
+    # order and the weights come from go2nn_smooth_indices inside the captured permutation step.  KL, the learning rate, clipping, Adam and the rank average do not
+    # know about it.
+    def _smooth_shape(self, rows):
+        """-> (blocks, T, n) of a mini-batch of `rows` rows whose pair weights are self._sw [T n]"""
+        T = self.storage.num_transitions_per_env
+        n = self._sw.numel() // T
+        blocks = rows // (T * n)
+        if blocks * T * n != rows or blocks not in (1, 2):
+            raise ValueError("smoothness loss: %d rows are not 1 or 2 blocks of %d steps x %d envs" % (rows, T, n))
+        return blocks, T, n
+
+    def _smooth_error(self, mu_b):
+        blocks, T, n = self._smooth_shape(mu_b.shape[0])
+        m = mu_b.view(blocks, T, n, mu_b.shape[1])
+        return (m[:, :-1] - m[:, 1:]) * self._sw.view(1, T, n, 1)[:, :-1].to(mu_b.dtype)
+
+    def _smooth_term(self, mu_b):
+        """-> the weighted term of the loss (under autograd); self._sl = L_smooth / coef of this mini-batch"""
+        ms = self._smooth_error(mu_b).square().mean()          # (over blocks (T - 1) n A elements, masked pairs included)
+        self._sl = ms.detach()
+        return self.smooth_loss_coef * ms
+
+    def _smooth_grad(self, mu_b):
+        """-> d L_smooth / d mu [blocks T n, A] as a torch expression, for the branch that seeds autograd with the loss kernel's gradients; self._sl as _smooth_term"""
+        with torch.no_grad():
+            e = self._smooth_error(mu_b)
+            self._sl = e.square().mean()
+            ge = (2.0 * self.smooth_loss_coef / e.numel()) * e
+            g = torch.zeros((e.shape[0], e.shape[1] + 1) + tuple(e.shape[2:]), dtype=mu_b.dtype, device=mu_b.device)
+            g[:, :-1] += ge          # row t: + e[t]
+            g[:, 1:] -= ge           # row t + 1: - e[t]
+            return g.view_as(mu_b)
+
+    def _smooth_order(self, nmb):
+        """Graph mode, inside the captured permutation step: the env-block index list of the update into self._sidx (what go2sim_shuffle_gather / index_select take) and
+        the pair weights into self._sw_all [nmb, T n].  ONE go2nn_smooth_indices call (the keyed bijection over the environments; its second launch advances the counter,
+        so a replayed graph draws a new permutation every time); with torch.randperm patched (the tests' hook) or no policy-side library: the same lists with torch ops
+        from torch.randperm(N), as the eager generator builds them."""
+        st = self.storage
+        T, N = st.num_transitions_per_env, st.num_envs
+        n = N // nmb
+        lib = None if torch.randperm is not _RANDPERM else self._nn_library(required=None)
+        if lib is None:
+            idx, w = st.env_block_indices(nmb, torch.randperm(N, requires_grad=False, device=self.device))
+            self._sidx.copy_(idx.reshape(-1))
+            self._sw_all.copy_(w.reshape(nmb, T * n))
+            return self._sidx
+        if self._shuffle_key is None:
+            self._make_shuffle_key()
+        p = lambda t: t.data_ptr()
+        if lib.go2nn_smooth_indices(p(self._sidx), p(self._sw_all), p(st.dones), nmb, T, N, p(self._shuffle_key), self._stream(self._acc)) != 0:
+            raise RuntimeError("go2nn_smooth_indices: %s" % lib.go2nn_last_error().decode())
+        return self._sidx
+
+    def _smooth_kernel_args(self, i, rows):
+        """-> (coef, pair weights uint8 [T n] of mini-batch i, blocks, T, n) of go2nn_smooth_loss"""
+        self._sw = self._sw_all[i]
+        return (self.smooth_loss_coef, self._sw) + self._smooth_shape(rows)
+
     # ---- graph mode -------------------------------------------------------------------------------------------
     _KEYS = ("obs", "cobs", "act", "val", "adv", "ret", "logp", "mu", "sig")
 
@@ -345,8 +440,9 @@ class PPO(_RolloutHeads):
             from ..modules import fused
             self.optimizer.zero_grad(set_to_none=True)
             mirror = self._mirror_kernel_args() if self.mirror_loss_coef > 0.0 else None          # (go2nn_mirror_loss behind go2nn_ppo_heads; its weighted loss is added to acc[2])
+            smooth = self._smooth_kernel_args(i, batch[0].shape[0]) if self.smooth_loss_coef > 0.0 else None          # (go2nn_smooth_loss behind both; its weighted loss: the last slot of acc)
             stats = fused.ppo_pair_grads(ac, batch[0], batch[1], batch[2], batch[3], batch[4], batch[5], batch[6], batch[7], batch[8], self.clip_param, self.value_loss_coef,
-                                         self.entropy_coef, self.use_clipped_value_loss, acc=self._acc, mirror=mirror, diag=self._diag)          # (the running loss sums: added by the pass's go2nn_sum_rows launch)
+                                         self.entropy_coef, self.use_clipped_value_loss, acc=self._acc, mirror=mirror, diag=self._diag, smooth=smooth)          # (the running loss sums: added by the pass's go2nn_sum_rows launch)
             kl_mean = stats[2]
         elif self.fused_loss:
             # the loss kernel already holds d loss / d (mu, std, value): seed the backward pass of the two networks with them directly
@@ -355,7 +451,15 @@ class PPO(_RolloutHeads):
             stats, gmu, gstd, gval = _FusedPPOLoss.kernel(self, mu_b, ac.std, val_b, *batch[2:])
             self._diag_torch(mu_b, ac.std, val_b, *batch[2:])
             self.optimizer.zero_grad(set_to_none=True)
-            if self.mirror_loss_coef > 0.0:       # the mirror term's gradient joins the kernel's; acc = [surrogate, value loss, L_mirror]
+            if self.smooth_loss_coef > 0.0:       # the regularisers' gradients join the kernel's; acc = [surrogate, value loss(, L_mirror), L_smooth]
+                self._sw = self._sw_all[i]
+                extra = []
+                if self.mirror_loss_coef > 0.0:
+                    gmu = gmu + self._mirror_grad(mu_b)
+                    extra.append(self.mirror_loss_coef * self._ml.reshape(1))
+                gmu = gmu + self._smooth_grad(mu_b)
+                self._acc.add_(torch.cat([stats[:2]] + extra + [self.smooth_loss_coef * self._sl.reshape(1)]))
+            elif self.mirror_loss_coef > 0.0:       # the mirror term's gradient joins the kernel's; acc = [surrogate, value loss, L_mirror]
                 gmu = gmu + self._mirror_grad(mu_b)
                 self._acc.add_(torch.cat([stats[:2], self.mirror_loss_coef * self._ml.reshape(1)]))
             else:
@@ -369,10 +473,13 @@ class PPO(_RolloutHeads):
                 torch.autograd.backward([mu_b, ac.std, val_b], [gmu, gstd.view_as(ac.std), gval])
             kl_mean = stats[2]
         else:
+            if self.smooth_loss_coef > 0.0:
+                self._sw = self._sw_all[i]
             loss, value_loss, surrogate_loss, kl_mean = self._losses(*batch)
             self.optimizer.zero_grad(set_to_none=True)
             loss.backward()
-            self._acc.add_(torch.stack([surrogate_loss.detach(), value_loss.detach()] + ([self.mirror_loss_coef * self._ml] if self.mirror_loss_coef > 0.0 else [])))
+            self._acc.add_(torch.stack([surrogate_loss.detach(), value_loss.detach()] + ([self.mirror_loss_coef * self._ml] if self.mirror_loss_coef > 0.0 else [])
+                                       + ([self.smooth_loss_coef * self._sl] if self.smooth_loss_coef > 0.0 else [])))
         if split:
             if self._bucket is None:
                 self._bucket = GradBucket(self._params, 1 if self._adaptive() else 0)
@@ -405,7 +512,12 @@ class PPO(_RolloutHeads):
                           "mu": flat(st.mu), "sig": flat(st.sigma)}
             self._mb = mb
             self._perm = {k: torch.empty((nmb * mb,) + tuple(v.shape[1:]), device=self.device, dtype=v.dtype) for k, v in self._flat.items()}
-            self._acc = torch.zeros(3 if self.mirror_loss_coef > 0.0 else 2, device=self.device)          # [surrogate, value loss(, the weighted mirror loss)]
+            smooth = self.smooth_loss_coef > 0.0
+            # [surrogate, value loss(, the weighted mirror loss)(, the weighted smoothness loss)]
+            self._acc = torch.zeros(2 + (self.mirror_loss_coef > 0.0) + smooth, device=self.device)
+            if smooth:          # (init_storage has checked that the mini-batches are whole environments: nmb * mb = T N)
+                self._sidx = torch.empty(nmb * mb, dtype=torch.int64, device=self.device)
+                self._sw_all = torch.zeros(nmb, mb, dtype=torch.uint8, device=self.device)
             self._bucket = None
             mirror =self._sym_setup(nmb, mb) if self._sym is not None else None
             if _collectives_on():
@@ -428,12 +540,14 @@ class PPO(_RolloutHeads):
             def gather():
                 if not use_lib:
                     self._acc.zero_()
-                    indices = torch.randperm(rows, requires_grad=False, device=self.device)
+                    indices = self._smooth_order(nmb) if smooth else torch.randperm(rows, requires_grad=False, device=self.device)
                     for k in self._KEYS:
                         torch.index_select(self._flat[k], 0, indices, out=self._perm[k])
                     return
                 idx = None
-                if torch.randperm is not _RANDPERM:
+                if smooth:          # env blocks: the index list comes from go2nn_smooth_indices, in front of the gather in the same captured step
+                    idx = self._smooth_order(nmb)
+                elif torch.randperm is not _RANDPERM:
                     idx = torch.randperm(rows, requires_grad=False, device=self.device).to(torch.int64).contiguous()
                 p = self._ptr
                 self._call("go2sim_shuffle_gather", self._gather_jobs, len(keys), rows, p(idx), p(self._shuffle_key), p(self._acc), int(self._acc.numel()), self._stream(self._acc))
@@ -450,8 +564,10 @@ class PPO(_RolloutHeads):
         self._obs_norm_finish()          # (enqueued behind the last optimizer step and in front of the read-back's host synchronisation: no idle gap in front of it)
         self._vn_finish()
         surrogate, value, *rest = self._read_back(self._acc, self.num_learning_epochs * nmb)
-        if rest:
-            self.mirror_loss = rest[0] / self.mirror_loss_coef
+        if self.mirror_loss_coef > 0.0:
+            self.mirror_loss = rest.pop(0) / self.mirror_loss_coef
+        if self.smooth_loss_coef > 0.0:
+            self.smooth_loss = rest.pop(0) / self.smooth_loss_coef
         return value, surrogate
 
     def graphs_captured(self):

@@ -539,17 +539,20 @@ def ppo_pair_applicable(ac, xa, xc):
     return pl is not None and ac.std.dim() == 1 and ac.std.shape[0] == pl[0][-1].out_features and ac.std.requires_grad
 
 
-def pair_grads(k, la, lc, xa, xc, std, batch, clip, vcoef, ecoef, use_clipped_value_loss, surrogate_split=0, acc=None, imgs=None, need_gz0=True, mirror=None, diag=None):
+def pair_grads(k, la, lc, xa, xc, std, batch, clip, vcoef, ecoef, use_clipped_value_loss, surrogate_split=0, acc=None, imgs=None, need_gz0=True, mirror=None, diag=None, smooth=None):
     """Forward of two MLPs with grouped hidden layers, go2nn_ppo_heads, backward of the hidden layers; the reductions are queued on `k` (the caller finishes).
     batch: actions, old values, advantages, returns, old log-probs, old mu, old sigma.  imgs: (actor images, critic images) of the hidden layers when the caller split
     them together with other networks' weights.  Sets .grad of every parameter of both networks and of std.
     mirror: (coef, perm int16 [A], sign fp32 [A]) — the rows are [B / 2 originals | B / 2 mirror images] and the mirror loss (go2nn_mirror_loss, one launch behind
     go2nn_ppo_heads) adds its gradient to the actor's gz; k.mirror_sums = (the heads' dW_mu | gb_a | db_mu, the mirror loss's): the caller adds the second to the
     first after k.finish() (ppo_pair_grads); acc[2] receives the weighted loss.
+    smooth: (coef, w uint8 [T n], blocks, T, n) — the rows are env blocks, row b T n + t n + j, and the smoothness loss (go2nn_smooth_loss, one launch behind
+    go2nn_ppo_heads and go2nn_mirror_loss: a fixed order, both add into gz) adds its gradient to the actor's gz; k.smooth_sums as k.mirror_sums; the slot of acc
+    behind the mirror loss's (or behind the value loss) receives the weighted loss.
     diag: the update's diagnostics (algorithms/_diag.py:UpdateDiagnostics: the table, the partial rows and the slot cursor) — ONE go2nn_ppo_diag call right behind the
     heads' (and the mirror loss's), reading the heads' inputs; None: nothing of it runs.
     -> (sums [surrogate, value loss, KL, entropy | ...] — valid after k.finish() —, the gradients at the first layers' pre-activations)"""
-    from ..._nn import Go2nnMirrorLoss, Go2nnPpoHeads
+    from ..._nn import Go2nnMirrorLoss, Go2nnPpoHeads, Go2nnSmoothLoss
     actions, old_values, adv, returns, old_logp, old_mu, old_sigma = batch
     H, B = len(la) - 1, xa.shape[0]
     cont = lambda t: t.detach() if t.is_contiguous() else t.detach().contiguous()
@@ -574,7 +577,9 @@ def pair_grads(k, la, lc, xa, xc, std, batch, clip, vcoef, ecoef, use_clipped_va
                       p(keep[4]), p(keep[5]), p(keep[6]), p(gz[0]), p(gz[1]), p(part), B, A, K, int(bool(use_clipped_value_loss)), float(clip), float(vcoef), float(ecoef), int(surrogate_split))
     k.check(_NN.go2nn_ppo_heads(C.byref(h), k.stream), "go2nn_ppo_heads")
     k.keep = keep          # (alive until the launches have run)
-    k.sums.append((part, tot, rows, cols, acc, 4 if acc is not None and acc.numel() >= 4 else (2 if acc is not None else 0)))
+    nreg = (mirror is not None) + (smooth is not None)          # (the regularisers' slots of acc follow the heads' two)
+    hacc = acc[:2] if acc is not None and nreg and acc.numel() == 2 + nreg else acc
+    k.sums.append((part, tot, rows, cols, hacc, 4 if hacc is not None and hacc.numel() >= 4 else (2 if hacc is not None else 0)))
     o = 4 + A
     std.grad = tot[4:o].view_as(std)
     la[H].weight.grad, gb_a, la[H].bias.grad = tot[o:o + A * K].view(A, K), tot[o + A * K:o + (A + 1) * K], tot[o + (A + 1) * K:o + (A + 1) * K + A]
@@ -594,16 +599,31 @@ def pair_grads(k, la, lc, xa, xc, std, batch, clip, vcoef, ecoef, use_clipped_va
         ml = Go2nnMirrorLoss(p(acts[0][H]), p(la[H].weight), p(la[H].bias), p(perm), p(sign), p(gz[0]), p(mpart), B // 2, A, K, float(coef))
         k.check(_NN.go2nn_mirror_loss(C.byref(ml), k.stream), "go2nn_mirror_loss")
         k.keep = keep + [perm, sign]
-        macc = acc[2:] if acc is not None and acc.numel() == 3 else None
+        macc = acc[2:3] if acc is not None and acc.numel() == 2 + nreg else None
         k.sums.append((mpart, mtot, mrows, mcols, macc, 1 if macc is not None else 0))
         k.mirror_sums = (tot[4 + A:4 + A + (A + 1) * K + A], mtot[4:])
+    if smooth is not None:
+        # the smoothness loss behind it, the same way: gz[0] += its gradient; its [L, 0, 0, 0 | dW_mu | gb_a | db_mu] sums are one more job of the pass's sum launch
+        coef, w, blocks, T, n = smooth
+        if blocks * T * n != B or w.numel() != T * n or w.dtype != torch.uint8 or not w.is_contiguous():
+            raise ValueError("smoothness loss: %d rows are not %d block(s) of %d steps x %d envs, or the pair weights are not their uint8 [T n]" % (B, blocks, T, n))
+        srows, scols = _NN.go2nn_smooth_loss_rows(blocks, T, n, A, K), _NN.go2nn_smooth_loss_cols(A, K)
+        if srows <= 0 or scols <= 0:
+            raise RuntimeError("go2nn_smooth_loss: %s" % _NN.go2nn_last_error().decode())
+        spart, stot = k.new(srows * scols), k.new(scols)
+        sl = Go2nnSmoothLoss(p(acts[0][H]), p(la[H].weight), p(la[H].bias), p(w), p(gz[0]), p(spart), blocks, T, n, A, K, float(coef))
+        k.check(_NN.go2nn_smooth_loss(C.byref(sl), k.stream), "go2nn_smooth_loss")
+        k.keep = list(k.keep) + [w]
+        sacc = acc[1 + nreg:2 + nreg] if acc is not None and acc.numel() == 2 + nreg else None
+        k.sums.append((spart, stot, srows, scols, sacc, 1 if sacc is not None else 0))
+        k.smooth_sums = (tot[4 + A:4 + A + (A + 1) * K + A], stot[4:])
     if diag is not None:
         diag.record_kernel(_NN, h, k.stream)
     gz1 = k.chain_backward([{"lins": la[:H], "acts": acts[0], "gz": gz[0], "gb": gb_a, "imgs": ia}, {"lins": lc[:H], "acts": acts[1], "gz": gz[1], "gb": gb_c, "imgs": ic}], need_gz0=need_gz0)
     return tot, gz1
 
 
-def ppo_pair_grads(ac, xa, xc, actions, old_values, adv, returns, old_logp, old_mu, old_sigma, clip, vcoef, ecoef, use_clipped_value_loss, acc=None, mirror=None, diag=None):
+def ppo_pair_grads(ac, xa, xc, actions, old_values, adv, returns, old_logp, old_mu, old_sigma, clip, vcoef, ecoef, use_clipped_value_loss, acc=None, mirror=None, diag=None, smooth=None):
     """One PPO mini-batch gradient (ppo.py:131-170 + loss.backward()) of a plain ActorCritic as explicit launches; every parameter's .grad is set (replaced, as after
     zero_grad(set_to_none=True)).  acc: optional float32[>= 2] device tensor — the mini-batch's surrogate and value loss are ADDED to acc[0:2] by the pass's
     go2nn_sum_rows launch (the update's running sums).  mirror: (coef, perm, sign) device tensors of the action table — the rows are an augmented mini-batch and the
@@ -613,9 +633,12 @@ def ppo_pair_grads(ac, xa, xc, actions, old_values, adv, returns, old_logp, old_
     k = _Launch(xa.device)
     with torch.no_grad():
         tot, _ = pair_grads(k, la, lc, xa, xc, ac.std, (actions, old_values, adv, returns, old_logp, old_mu, old_sigma), clip, vcoef, ecoef, use_clipped_value_loss, 0, acc, need_gz0=False,
-                            mirror=mirror, diag=diag)
+                            mirror=mirror, diag=diag, smooth=smooth)
         k.finish()
         if mirror is not None:
             head, extra = k.mirror_sums
             head.add_(extra)          # dW_mu | gb_a | db_mu of the heads += the mirror loss's (the actor head's .grad and the last hidden layer's bias .grad are views of `head`)
+        if smooth is not None:
+            head, extra = k.smooth_sums
+            head.add_(extra)          # ... += the smoothness loss's
     return tot[:4]

@@ -359,6 +359,9 @@ class OnPolicyRunner:
         mirror = self.alg.mirror_loss if getattr(self.alg, "mirror_loss_coef", 0.0) > 0.0 else None          # (the mirror loss: L_mirror / coef = equivariance_rmse^2 of the update's rows)
         if mirror is not None:
             w.add_scalar("Loss/mirror", mirror, locs["it"])
+        smooth = self.alg.smooth_loss if getattr(self.alg, "smooth_loss_coef", 0.0) > 0.0 else None          # (the smoothness loss: L_smooth / coef, the mean squared step of the action mean)
+        if smooth is not None:
+            w.add_scalar("Loss/smooth", smooth, locs["it"])
         w.add_scalar("Loss/learning_rate", self.alg.learning_rate, locs["it"])
         ret = getattr(self.alg, "return_stats", None)          # (algorithm.normalize_value: the raw returns' running mean / std, read with the update's own read-back)
         if ret is not None:
@@ -388,6 +391,8 @@ class OnPolicyRunner:
             s += f"""{label:>{pad}} {v:.4f}\n"""
         if mirror is not None:
             s += f"""{'Mirror loss:':>{pad}} {mirror:.6f}\n"""
+        if smooth is not None:
+            s += f"""{'Smoothness loss:':>{pad}} {smooth:.6f}\n"""
         if diag:
             s += report_lines(diag, pad)
         s += f"""{'Mean action noise std:':>{pad}} {mean_std.item():.2f}\n"""

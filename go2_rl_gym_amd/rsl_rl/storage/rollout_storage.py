@@ -115,6 +115,34 @@ class RolloutStorage:
                 b = indices[i * mini_batch_size:(i + 1) * mini_batch_size]
                 yield obs[b], cobs[b], acts[b], vals[b], adv[b], rets[b], logp[b], mu[b], sig[b], (None, None), None
 
+    # ---- env-block mini-batches (the smoothness loss: algorithms/ppo.py) ---------------------------------------------------------------------------------
+    def env_block_indices(self, num_mini_batches, env_perm):
+        """-> (idx int64 [nmb, T, n], w uint8 [nmb, T, n]): mini-batch i holds all T steps of the envs env_perm[i n : (i + 1) n], time-major — idx[i, t, j] = t N +
+        env_perm[i n + j] is a row of the flattened [T N, .] rollout —, w[i, t, j] = (t < T - 1 and dones[t, that env] == 0): the pair (t, t + 1) is compared"""
+        T, N = self.num_transitions_per_env, self.num_envs
+        if N % num_mini_batches != 0:
+            raise ValueError("env-block mini-batches: %d envs are not a multiple of %d mini-batches" % (N, num_mini_batches))
+        n = N // num_mini_batches
+        envs = env_perm.to(torch.int64).view(num_mini_batches, 1, n)
+        idx = (torch.arange(T, device=envs.device, dtype=torch.int64).view(1, T, 1) * N + envs).contiguous()
+        w = (self.dones.view(-1)[idx] == 0).to(torch.uint8)
+        w[:, T - 1] = 0
+        return idx, w
+
+    def env_block_mini_batch_generator(self, num_mini_batches, num_epochs=8, env_perm=None):
+        """mini_batch_generator's tuple over env blocks (one env permutation per update, torch.randperm(N) unless given), followed by the pair weights w [T n] (uint8)"""
+        if env_perm is None:
+            env_perm = torch.randperm(self.num_envs, requires_grad=False, device=self.device)
+        idx, w = self.env_block_indices(num_mini_batches, env_perm)
+        flat = lambda t: t.flatten(0, 1)
+        obs = flat(self.observations)
+        cobs = flat(self.privileged_observations) if self.privileged_observations is not None else obs
+        rows = (obs, cobs, flat(self.actions), flat(self.values), flat(self.advantages), flat(self.returns), flat(self.actions_log_prob), flat(self.mu), flat(self.sigma))
+        for _ in range(num_epochs):
+            for i in range(num_mini_batches):
+                b = idx[i].reshape(-1)
+                yield tuple(t[b] for t in rows) + ((None, None), None, w[i].reshape(-1))
+
     # ---- recurrent policies ------------------------------------------------------------------------------------------------------------------------------
     def reccurent_mini_batch_generator(self, num_mini_batches, num_epochs=8):
         """The reference formulation of the recurrent update's mini-batches (GO2_FUSED_MLP=0, the CPU; the name is the reference's): contiguous env slices, every

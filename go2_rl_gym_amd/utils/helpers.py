@@ -116,6 +116,8 @@ def update_cfg_from_args(env_cfg, cfg_train, args):
         cfg_train.algorithm.symmetry = True          # (a CTS task's algorithm then refuses at construction: feed-forward PPO only)
     if getattr(args, "diagnostics", False):
         cfg_train.algorithm.diagnostics = True          # (a recurrent policy or MCP-CTS then refuses at construction)
+    if getattr(args, "smooth_loss", None) is not None:
+        cfg_train.algorithm.smooth_loss_coef = args.smooth_loss
     if getattr(args, "mirror_loss", None) is not None:          # the mirror loss is a term on the augmented mini-batches: the flag switches augmentation on too
         cfg_train.algorithm.mirror_loss_coef = args.mirror_loss
         cfg_train.algorithm.symmetry = True
@@ -200,6 +202,8 @@ def get_args(argv=None):
     p.add_argument("--diagnostics", action="store_true", default=False, help="log the update's diagnostics as Diag/*: clip fraction, approximate and analytic KL, explained "
                    "variance, ratio and advantage statistics, gradient norm and clipped share, with their first- and last-epoch values; computed on the device inside the "
                    "update, training is bit for bit unchanged (feed-forward PPO and the CTS family): algorithm.diagnostics = True")
+    p.add_argument("--smooth_loss", type=float, default=None, metavar="COEF", help="add COEF x the mean squared gap between the policy's action means at successive steps of an "
+                   "episode to the PPO loss; the update's mini-batches become blocks of whole environments (feed-forward PPO only): algorithm.smooth_loss_coef = COEF")
     p.add_argument("--mirror_loss", type=float, default=None, metavar="COEF", help="add COEF x the mean squared gap between the policy's answer to an observation and the "
                    "mirrored answer to its mirror image to the PPO loss (feed-forward PPO only; switches --symmetry on): algorithm.mirror_loss_coef = COEF")
     p.add_argument("--normalize_obs", action="store_true", default=False, help="normalise both observation streams by their running mean and standard deviation "

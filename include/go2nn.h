@@ -991,6 +991,40 @@ int go2nn_value_norm_apply(float* values, float* returns, int32_t n, const float
 int go2nn_value_norm_update(const double* partials, int32_t rows, double* state, double n, double eps, float* stat32, float* w_last, float* b_last, int32_t K, void* stream);
 int go2nn_value_head_fold(const float* w, const float* b, int32_t K, const float* stat32, float* w_out, float* b_out, void* stream);
 
+/* ---- the temporal action-smoothness loss of PPO on env-block mini-batches (go2_rl_gym_amd/rsl_rl/algorithms/ppo.py, `algorithm.smooth_loss_coef`; csrc/go2nn_smooth_loss.h).
+ * ADDED WITHIN ABI 7: five new entry points and one struct, nothing existing changes, GO2NN_ABI_VERSION stays 7.
+ * A mini-batch in block layout is blocks x T x n rows, row r = b T n + t n + j: all T steps of n environments (blocks = 2: followed by their mirror images).  For t < T - 1,
+ * with the pair weights w[t, j] in {0, 1} (0: an episode boundary between steps t and t + 1 of env j):
+ *   e[b, t, j, :] = w[t, j] (mu[b, t, j, :] - mu[b, t + 1, j, :])           mu = y_a W_mu^T + b_mu (the fp32 dot products of go2nn_ppo_heads)
+ *   L = coef / (blocks (T - 1) n A) sum e^2                                 (a fixed denominator: masked pairs add 0)
+ *   g[b, t, j, :] = 2 coef / (blocks (T - 1) n A) (e[b, t, j, :] - e[b, t - 1, j, :]),   e[., -1] = e[., T - 1] = 0          (both rows of a pair receive gradient)
+ * go2nn_smooth_loss: two plain launches (capturable) behind go2nn_ppo_heads (and go2nn_mirror_loss) on the same stream — the pass, then one block that adds the workgroups'
+ * fp64 sums of e^2 and leaves L, rounded once, in the first partial row —: (g W_mu) * ELU'(y_a) (ELU' from the output: y > 0 ? 1 : y + 1) is ADDED to gz_a, and `partials`
+ * receives go2nn_smooth_loss_rows(blocks, T, n, A, K) rows of go2nn_smooth_loss_cols(A, K) columns whose column sums (go2nn_sum_rows) are
+ *   [ L, 0, 0, 0 | dW_mu [A, K] | gb_a [K] = the column sums of what was added to gz_a | db_mu [A] ]
+ * Fixed summation order, no atomics: two launches give the same bits.  GO2NN_EINVAL, with nothing written, for a null struct or pointer, blocks outside [1, 2], T < 2, n < 1,
+ * A outside [1, 16], K not a multiple of 4 in [4, 256], blocks T n K >= 2^31, a coefficient that is negative or not finite.
+ * go2nn_smooth_loss_set_segments: the number of time segments the device pass splits T into (csrc/go2nn_smooth_loss.h; 0, the default: its own choice); a measurement
+ * hook — go2nn_smooth_loss_rows follows it, the results agree to rounding of the partial sums.  The host build accepts and ignores it.
+ * go2nn_smooth_indices: the env-block mini-batches.  With pi = go2_shuffle_index(., N, ...) of include/go2sim_shuffle.h under (key_state[0], key_state[1]) and n = N / nmb,
+ *   out[i T n + t n + j] = t N + pi(i n + j)          the int64 index list go2sim_shuffle_gather takes as `indices` (rows of the [T, N] rollout)
+ *   w  [i T n + t n + j] = t < T - 1 && dones[t N + pi(i n + j)] == 0          (uint8; dones: the storage's [T, N] uint8 tensor, time-outs included)
+ * and key_state[1] += 1 by a one-lane second launch, so a replayed graph draws a new permutation every time.  GO2NN_EINVAL, with nothing written, for a null pointer,
+ * nmb < 1, T < 2, N < 1, N not a multiple of nmb, T N >= 2^31. */
+typedef struct Go2nnSmoothLoss {
+  const float* y_a;            /* [blocks*T*n, K] */
+  const float *w_mu, *b_mu;    /* [A, K], [A] */
+  const uint8_t* w;            /* [T*n] pair weights of this mini-batch (row T-1 is 0) */
+  float* gz_a;                 /* [blocks*T*n, K]: ADDED to */
+  float* partials;             /* go2nn_smooth_loss_rows x go2nn_smooth_loss_cols: [L,0,0,0 | dW_mu | gb_a | db_mu] */
+  int32_t blocks, T, n, A, K; float coef;
+} Go2nnSmoothLoss;
+int32_t go2nn_smooth_loss_rows(int32_t blocks, int32_t T, int32_t n, int32_t A, int32_t K);
+int32_t go2nn_smooth_loss_cols(int32_t A, int32_t K);
+int go2nn_smooth_loss_set_segments(int32_t segments);
+int go2nn_smooth_loss(const Go2nnSmoothLoss* a, void* stream);
+int go2nn_smooth_indices(int64_t* out, uint8_t* w, const uint8_t* dones, int32_t nmb, int32_t T, int32_t N, uint32_t* key_state, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
