@@ -67,6 +67,40 @@ GO2NN_ASYM_NUM, GO2NN_ASYM_PAIR0 = len(ASYM_ROWS), ASYM_ROWS.index("act_sq_l")
 ASYM_OUT = ("n",) + ASYM_ROWS[1:] + tuple("%s_%s" % (p, k) for p in ASYM_PAIRS for k in ("imb", "imb_n"))
 GO2NN_ASYM_OUT_IMB0, GO2NN_ASYM_OUT_NUM = GO2NN_ASYM_NUM, len(ASYM_OUT)
 ASYM_FIELDS = ("commands", "dof_state", "torques", "contact_forces", "reset_buf")
+# the evaluator's action and torque spectra (GO2NN_SPECTRUM_* of include/go2nn.h): the trace [1 + 25 T, N] — the step row, then per counted step the actions and the torques
+# of the 12 slots (joints in kind order) and the reset flag —, the table [2 + 12 K, N], K = W / 2 + 1 — used, skipped, then sum P and sum M per (signal, kind, bin) —, the
+# reduce's output "n" + the table's rows; and the buffers of Go2nnSpectrumIn in the struct's order
+SPECTRUM_FIELDS = ("actions", "torques", "reset_buf")
+SPECTRUM_SIGNALS, SPECTRUM_KINDS = ("action", "torque"), ("hip", "thigh", "calf")
+GO2NN_SPECTRUM_MIN_WINDOW, GO2NN_SPECTRUM_MAX_WINDOW, GO2NN_SPECTRUM_MAX_STEPS = 8, 256, 1 << 20
+GO2NN_SPECTRUM_CHANNELS, GO2NN_SPECTRUM_CH_ACTION0, GO2NN_SPECTRUM_CH_TORQUE0, GO2NN_SPECTRUM_CH_RESET = 25, 0, 12, 24
+GO2NN_SPECTRUM_USED, GO2NN_SPECTRUM_SKIPPED, GO2NN_SPECTRUM_BIN0 = 0, 1, 2
+
+
+def spectrum_bins(W):
+    return W // 2 + 1
+
+
+def spectrum_trace_rows(T):
+    return 1 + GO2NN_SPECTRUM_CHANNELS * T
+
+
+def spectrum_rows(W):
+    """the rows of the per-robot table; go2nn_spectrum_reduce's output has one more column in front (the group's robots)"""
+    return GO2NN_SPECTRUM_BIN0 + 12 * spectrum_bins(W)
+
+
+def spectrum_row(W, what, signal, kind, k=0):
+    """the table row of bin k of `what` ("P" or "M") of SPECTRUM_SIGNALS[signal] x SPECTRUM_KINDS[kind]"""
+    K = spectrum_bins(W)
+    return GO2NN_SPECTRUM_BIN0 + (6 * K if what == "M" else 0) + (signal * 3 + kind) * K + k
+
+
+def spectrum_twiddle(W):
+    """float64 [W, 2]: (cos, sin)(2 pi n / W), what go2nn_spectrum_welch reads its rotations and its Hann weights from"""
+    import numpy as np
+    a = 2.0 * np.pi * np.arange(W, dtype=np.float64) / float(W)
+    return np.ascontiguousarray(np.stack([np.cos(a), np.sin(a)], 1))
 # the evaluator's command maneuvers: the rows of the table [GO2NN_MANEUVER_NUM, N] in the order of the enum GO2NN_MANEUVER_* of include/go2nn.h (per-env state first, then
 # the accumulators go2nn_maneuver_reduce sums; its output columns are those plus "n"), and the buffers of Go2nnManeuverIn in the struct's order
 MANEUVER_ROWS = ("step", "open", "ok_run", "is_settled", "is_fell", "peak_tilt", "switches", "switch_falls", "settled", "settle_steps", "win_steps", "win_lin_err",
@@ -172,6 +206,10 @@ class Go2nnAsymIn(C.Structure):          # (within ABI 7)
                                                              ("foot_side", C.c_int32 * 4), ("joint_side", C.c_int32 * 12), ("joint_kind", C.c_int32 * 12),
                                                              ("action_perm", C.c_int16 * 12), ("action_sign", C.c_float * 12), ("contact_threshold", C.c_float),
                                                              ("pad_", C.c_int32)]
+
+
+class Go2nnSpectrumIn(C.Structure):          # (within ABI 7)
+    _fields_ = [(k, Go2nnEvalField) for k in SPECTRUM_FIELDS] + [("joint_of_slot", C.c_int32 * 12)]
 
 
 def gait_row(foot, name):
@@ -437,6 +475,10 @@ def bind(path):
     lib.go2nn_asym_begin.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
     lib.go2nn_asym_accumulate.argtypes = [C.POINTER(Go2nnAsymIn), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
     lib.go2nn_asym_reduce.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.go2nn_spectrum_begin.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]          # (within ABI 7) the evaluator's action and torque spectra
+    lib.go2nn_spectrum_record.argtypes = [C.POINTER(Go2nnSpectrumIn), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
+    lib.go2nn_spectrum_welch.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.go2nn_spectrum_reduce.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
     lib.go2nn_eval_bootstrap_check.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]          # (within ABI 7) the cells' member lists, in host memory
     lib.go2nn_eval_bootstrap.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p]
     for fam in ("robust", "maneuver", "gait", "asym"):          # (within ABI 7) the same replicates of every scoring family's reduce table

@@ -133,3 +133,4 @@ if __name__ == "__main__":
     print(kernel_resources())
     print(build_nn(force=True))
     print(kernel_resources(NN_OUT, match="go2nn_mlp_kernel"))
+    print(kernel_resources(NN_OUT, match="spectrum_welch_kernel"))

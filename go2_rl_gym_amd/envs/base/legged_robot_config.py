@@ -318,6 +318,10 @@ class LeggedRobotCfgPPO(BaseConfig):
         blackbox_seconds = 2.0  # [s] length of every robot's ring; memory = num_envs x steps x 448 bytes (1024 x 100: 46 MB)
         blackbox_max_bytes = 512 * 1024 * 1024  # a black box larger than this is refused
         asymmetry = False       # True (--asymmetry): also run the policy on the mirror image of every observation and report how far it is from equivariant (equivariance_rmse, per joint kind, relative, max) and, on steps whose command has vy = yaw = 0, how unequally the robot loads its left and right legs (action, torque, power, contact: left share and per-robot imbalance; utils/evaluator.py ASYM_KEYS); an add-on like `gait`, it works next to every mode above; feed-forward and CTS policies
+        spectrum = False        # True (--spectrum): keep every robot's actions and torques of the counted steps on the device and report their Welch spectra per group: the share of the power at and above `spectrum_cutoff_hz`, the power's centroid, CAPS's frequency-weighted amplitude and the non-DC variance, per signal and joint kind (utils/evaluator.py SPECTRUM_KEYS); an add-on like `gait`, it works next to every mode above
+        spectrum_window = 64    # [policy steps] Welch window length W: even, 8 <= W <= 256; hop W / 2, bin width fs / W (50 Hz / 64 = 0.78 Hz)
+        spectrum_cutoff_hz = 10.0  # [Hz] where "high frequency" begins for <signal>_hf_share: inside (0, fs / 2]
+        spectrum_max_bytes = 512 << 20  # the trace of steps x num_envs x 25 floats (500 x 1024: 51 MB) is refused above this
         bootstrap = 0           # B > 0 (--ci [B]): after the reduce, redraw every cell's robots with replacement B times on the device (go2nn_eval_bootstrap) and give every reported figure of RESULT_KEYS a percentile interval ("ci": {metric: [lo, hi]}, utils/evaluator.py CI_KEYS); the same replicates of two checkpoints are paired (utils/evaluator.py compare); 0: nothing is loaded, allocated or launched
         bootstrap_seed = 2718   # the Philox seed of the redraws: the same seed, the same robots in replicate b of every evaluation
         confidence = 0.95       # the intervals' level: the (1 - confidence) / 2 and (1 + confidence) / 2 quantiles of the replicates
@@ -419,6 +423,10 @@ class LeggedRobotCfgCTS(BaseConfig):
         blackbox_seconds = 2.0  # [s] length of every robot's ring; memory = num_envs x steps x 448 bytes (1024 x 100: 46 MB)
         blackbox_max_bytes = 512 * 1024 * 1024  # a black box larger than this is refused
         asymmetry = False       # True (--asymmetry): also run the policy on the mirror image of every observation and report how far it is from equivariant (equivariance_rmse, per joint kind, relative, max) and, on steps whose command has vy = yaw = 0, how unequally the robot loads its left and right legs (action, torque, power, contact: left share and per-robot imbalance; utils/evaluator.py ASYM_KEYS); an add-on like `gait`, it works next to every mode above; feed-forward and CTS policies
+        spectrum = False        # True (--spectrum): keep every robot's actions and torques of the counted steps on the device and report their Welch spectra per group: the share of the power at and above `spectrum_cutoff_hz`, the power's centroid, CAPS's frequency-weighted amplitude and the non-DC variance, per signal and joint kind (utils/evaluator.py SPECTRUM_KEYS); an add-on like `gait`, it works next to every mode above
+        spectrum_window = 64    # [policy steps] Welch window length W: even, 8 <= W <= 256; hop W / 2, bin width fs / W (50 Hz / 64 = 0.78 Hz)
+        spectrum_cutoff_hz = 10.0  # [Hz] where "high frequency" begins for <signal>_hf_share: inside (0, fs / 2]
+        spectrum_max_bytes = 512 << 20  # the trace of steps x num_envs x 25 floats (500 x 1024: 51 MB) is refused above this
         bootstrap = 0           # B > 0 (--ci [B]): after the reduce, redraw every cell's robots with replacement B times on the device (go2nn_eval_bootstrap) and give every reported figure of RESULT_KEYS a percentile interval ("ci": {metric: [lo, hi]}, utils/evaluator.py CI_KEYS); the same replicates of two checkpoints are paired (utils/evaluator.py compare); 0: nothing is loaded, allocated or launched
         bootstrap_seed = 2718   # the Philox seed of the redraws: the same seed, the same robots in replicate b of every evaluation
         confidence = 0.95       # the intervals' level: the (1 - confidence) / 2 and (1 + confidence) / 2 quantiles of the replicates

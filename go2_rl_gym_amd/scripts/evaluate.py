@@ -19,6 +19,11 @@ feet drag least.
 --asymmetry also scores left-right asymmetry (utils/evaluator.py ASYM_KEYS), next to any of the modes above; --metric then also takes equivariance_rmse (and /hip, /thigh,
 /calf), equivariance_rel, equivariance_max and imbalance/action, /torque, /power, /contact — all lower is better —, so --all_checkpoints --asymmetry --metric
 equivariance_rmse compares a --symmetry run with a plain one.  left_share/* says WHICH side carries more and has no better direction: it is refused as a metric.
+--spectrum also scores how fast the joints are driven (utils/evaluator.py SPECTRUM_KEYS: Welch spectra of every robot's actions and torques), next to any of the modes
+above; --metric then also takes action_hf_share, action_centroid_hz, action_smoothness, action_power and their torque_ twins (and a per-kind figure, action_hf_share/calf) —
+all lower is better —, so --all_checkpoints --spectrum --metric action_hf_share compares a --smooth_loss run with a plain one.  The figures have no bootstrap replicates:
+--ci next to --spectrum leaves every interval as it is, and --ci --metric <a spectrum figure> is refused before anything runs.  The mean power spectra per cell go to
+eval_results/spectrum_<checkpoint number>.npz (utils/recorder.py read_spectrum).
 --record N also records N robots of every (terrain x scenario) group and writes eval_results/trace_<checkpoint number>.npz into the run's directory.
 --blackbox [N] also keeps the last seconds before every robot's first fall (utils/recorder.py FallRecorder), prints per cell with falls how many robots fell and when,
 and writes those of N fallen robots per cell (default 2) to eval_results/falls_<checkpoint number>.npz; read_falls and fall_summary read it back.
@@ -40,8 +45,9 @@ from pathlib import Path
 
 from go2_rl_gym_amd.envs import *  # noqa: F401,F403
 from go2_rl_gym_amd.utils import get_args
-from go2_rl_gym_amd.utils.evaluator import (ASYM_KEYS, CI_KEYS, DIAGONAL_PAIRS, GAIT_FOOT_KEYS, GAIT_KEYS, MANEUVER_KEYS, ROBUST_KEYS, PolicyEvaluator, compare, format_table, interval,
-                                            replicate_metrics, results_dict)
+from go2_rl_gym_amd.utils.evaluator import (ASYM_KEYS, CI_KEYS, DIAGONAL_PAIRS, GAIT_FOOT_KEYS, GAIT_KEYS, MANEUVER_KEYS, ROBUST_KEYS, SPECTRUM_COUNT_KEYS, SPECTRUM_KEYS, PolicyEvaluator,
+                                            compare, format_table, interval, replicate_metrics, results_dict)
+from go2_rl_gym_amd._nn import SPECTRUM_KINDS
 from go2_rl_gym_amd.utils.helpers import _checkpoint_number, get_load_path
 from go2_rl_gym_amd.utils.task_registry import ROOT_DIR, task_registry
 
@@ -56,6 +62,11 @@ def higher_is_better(metric):
 
 def is_foot_metric(metric):
     return "/" in metric and metric.split("/", 1)[0] in GAIT_FOOT_KEYS and metric.split("/", 1)[1] in FEET
+
+
+def is_spectrum_metric(metric):
+    """a pooled spectrum figure, or one of a joint kind ("torque_centroid_hz/calf")"""
+    return metric in SPECTRUM_KEYS or ("/" in metric and metric.split("/", 1)[0] in SPECTRUM_KEYS and metric.split("/", 1)[1] in SPECTRUM_KINDS)
 
 
 def _own_flags(argv):
@@ -79,12 +90,18 @@ def check_metric(metric):
     if metric.startswith("left_share/"):
         raise ValueError("--metric %s: a left share says which side carries more (0.5 is balanced) and has no better direction; rank by imbalance/%s instead"
                          % (metric, metric.split("/", 1)[1]))
+    if metric in SPECTRUM_COUNT_KEYS:
+        raise ValueError("--metric %s: how many windows the spectra were taken over (and the share skipped for a reset) says how much was analysed, not how the policy moves; "
+                         "rank by one of %s" % (metric, ", ".join(SPECTRUM_KEYS)))
 
 
 def check_ci_metric(metric, args):
     """--ci [--ci_all] --metric: refused before anything runs unless the metric will have replicates — with a message that says why"""
     if metric in CI_KEYS:
         return
+    if is_spectrum_metric(metric):
+        raise ValueError("--ci --metric %s: the spectrum figures have no replicates (a robot's table is made by one Welch pass after the run and is not resampled, with or "
+                         "without --ci_all); rank by it without --ci" % metric)
     if not getattr(args, "ci_all", False):
         raise ValueError("--ci --metric %s: the bootstrap resamples the figures %s; the modes' own figures, the gait and the asymmetry sections have no replicates "
                          "without --ci_all" % (metric, ", ".join(CI_KEYS)))
@@ -106,7 +123,7 @@ def check_ci_metric(metric, args):
 def metric_value(row, metric):
     """a checkpoint row's overall `metric`: the scores' own; with --gait a per-foot gait figure (the pooled ones are in `overall`, the per-foot ones in the gait section's);
     with --asymmetry one of the asymmetry figures (kept in their own section: they leave `overall` alone)"""
-    for section in ("gait", "asymmetry"):
+    for section in ("gait", "asymmetry", "spectrum"):
         if metric not in row["overall"] and metric in row.get(section, {}).get("overall", {}):
             return row[section]["overall"][metric]
     return row["overall"][metric]
@@ -188,6 +205,10 @@ def evaluate(argv=None, log_root="default", env_kwargs=None, evaluator_kwargs=No
             rows[-1]["gait"] = {"overall": res["gait"]["overall"], "groups": res["gait"]["groups"]}
         if res.get("asymmetry") is not None:
             rows[-1]["asymmetry"] = {"overall": res["asymmetry"]["overall"], "groups": res["asymmetry"]["groups"]}
+        if res.get("spectrum") is not None:
+            from go2_rl_gym_amd.utils.recorder import write_spectrum
+            rows[-1]["spectrum"] = {"overall": res["spectrum"]["overall"], "groups": res["spectrum"]["groups"]}
+            print("spectrum: %s" % write_spectrum(os.path.join(str(p.parent), "eval_results", "spectrum_%s.npz" % _checkpoint_number(p)), res["spectrum_psd"]))
         if res.get("ladder_summary") is not None:
             rows[-1]["ladder_summary"] = res["ladder_summary"]
             import yaml

@@ -87,6 +87,18 @@ the robots of each robot's own |L - R| / (L + R).  ASYM_KEYS are pooled ratios o
 res["asymmetry"] only — res["overall"] and every other result are those of the flag-off run.  The mirrored forward shares the weights and nothing else with act(); a
 recurrent policy is refused (its mirrored stream needs a twin hidden state).  With `asymmetry = False` nothing of this is loaded, allocated or launched.
 
+How fast the joints are driven: with `evaluation.spectrum` (--spectrum) every robot's 12 actions and 12 torques after the step, and its reset flag, are kept for the counted
+steps — one more plain launch per step, behind the recorders' slot and inside the captured chunk, into a device trace with its own step counter,
+    { ..., go2sim_step, ..., go2nn_eval_accumulate, ..., go2nn_spectrum_record }
+(csrc/go2nn_spectrum.h; steps x num_envs x 25 floats, refused above `spectrum_max_bytes`) — and after the last step ONE go2nn_spectrum_welch, outside any capture, makes every
+robot's Welch spectra of them (the estimator is in include/go2nn.h: windows of `spectrum_window` steps, hop W / 2, a window with a reset frame skipped, mean removed, periodic
+Hann, density scaling; the joints pooled by kind) and one go2nn_spectrum_reduce sums the table over the finest cells the mode has.  An add-on like `gait`: it splits
+nothing and works next to every mode.  SPECTRUM_KEYS, per signal and (`/hip`, `/thigh`, `/calf`) per joint kind, over the bins k >= 1 at f_k = k fs / W: `hf_share` = the
+power at f_k >= `spectrum_cutoff_hz` over the power, `centroid_hz` = sum f_k P_k / sum P_k, `smoothness` = CAPS's 2 / (n fs) sum f_k M_k on the mean amplitude spectrum
+(n = W / 2), `power` = (fs / W) sum of the mean P_k: the mean non-DC variance per joint; `spectrum_windows` and `spectrum_skipped_share` next to them.  Pooled ratios of the
+cells' sums, NaN where nothing was counted; res["overall"] gains the eight pooled figures.  They have no bootstrap replicates (`bootstrap_all` leaves the family out).
+With `spectrum = False` nothing of this is loaded, allocated or launched.
+
 How sure a figure is: with `evaluation.bootstrap = B > 0` (--ci [B]) ONE more launch after go2nn_eval_reduce, on the same accumulators and the same cells, redraws every
 cell's robots with replacement B times (go2nn_eval_bootstrap: csrc/go2nn_bootstrap.h, the rule in include/go2nn.h; Philox seed `bootstrap_seed`) and one more device ->
 host copy brings the [B, cells, 12] fp64 table of resampled reduce rows: res["bootstrap"] = {"replicates", "seed", "confidence", "table", "overall" ([B, 12]: the overall
@@ -120,6 +132,8 @@ from .._nn import (EVAL_FIELDS, EVAL_METRICS, GO2NN_EVAL_NUM, GO2NN_RNN_GRU, GO2
                    MANEUVER_FIELDS, MANEUVER_OUT, Go2nnEvalIn, Go2nnFwdJob, Go2nnLadderIn, Go2nnManeuverIn, Go2nnManeuverSpec, Go2nnMlpIO, Go2nnRnnCellJob, Go2nnRobustIn,
                    Go2nnRobustSpec, PackedMlp, GAIT_FIELDS, GAIT_OUT_FOOT, GO2NN_GAIT_NUM, GO2NN_GAIT_OUT_DIAGONAL, GO2NN_GAIT_OUT_NUM, GO2NN_GAIT_OUT_SUPPORT0, Go2nnGaitIn,
                    gait_out_col, ASYM_FIELDS, ASYM_OUT, ASYM_PAIRS, GO2NN_ASYM_NUM, GO2NN_ASYM_OUT_NUM, Go2nnAsymIn, GO2NN_SENSOR_MAX_DELAY, GO2NN_SENSOR_MAX_SPECS, GO2_OBS_KINDS, SENSOR_KINDS, Go2nnSensorIn, Go2nnSensorSpec)
+from .._nn import (GO2NN_SPECTRUM_MAX_STEPS, GO2NN_SPECTRUM_MAX_WINDOW, GO2NN_SPECTRUM_MIN_WINDOW, GO2NN_SPECTRUM_SKIPPED, GO2NN_SPECTRUM_USED, SPECTRUM_FIELDS, SPECTRUM_KINDS,
+                   SPECTRUM_SIGNALS, Go2nnSpectrumIn, spectrum_bins, spectrum_row, spectrum_rows, spectrum_trace_rows, spectrum_twiddle)
 from .._nn import mirror_rows
 from .helpers import class_to_dict
 
@@ -154,6 +168,11 @@ DIAGONAL_PAIRS = (("FL", "RR"), ("FR", "RL"))
 ASYM_LOADS = ("action", "torque", "power", "contact")          # in the order of ASYM_PAIRS (act_sq, torque_sq, power, contact)
 ASYM_EQ_KEYS = ("equivariance_rmse", "equivariance_rmse/hip", "equivariance_rmse/thigh", "equivariance_rmse/calf", "equivariance_rel", "equivariance_max")
 ASYM_KEYS = ASYM_EQ_KEYS + ("sym_steps_share",) + tuple("left_share/" + x for x in ASYM_LOADS) + tuple("imbalance/" + x for x in ASYM_LOADS)
+# pooled over a partition's robots, per signal ("action_<key>", "torque_<key>") and per joint kind ("<signal>_<key>/<kind>"): the share of the power at and above the
+# cut-off, the power's centroid, CAPS's frequency-weighted mean amplitude, the mean non-DC variance per joint; then the windows analysed and the share skipped for a reset
+SPECTRUM_FIGURES = ("hf_share", "centroid_hz", "smoothness", "power")
+SPECTRUM_KEYS = tuple("%s_%s" % (s, k) for s in SPECTRUM_SIGNALS for k in SPECTRUM_FIGURES)
+SPECTRUM_COUNT_KEYS = ("spectrum_windows", "spectrum_skipped_share")
 # with `bootstrap_all`: what the printed table's interval block shows of each family
 BOOTSTRAP_HEADLINES = (("robust", ("push_falls", "recovered", "recovery_time_s")), ("maneuver", ("switch_falls", "settled", "settle_time_s")),
                        ("ladder", ("cleared", "mean_level_cleared")), ("gait", ("slip_speed", "trot_share", "swing_clearance")), ("asym", ("equivariance_rmse", "imbalance/torque")))
@@ -181,11 +200,14 @@ class _ScoreTable:
     """One per-env score table `table` [rows, N]: begun once per evaluation (go2nn_<name>_begin), advanced once per step (go2nn_<name>_accumulate; robust and maneuver also
     go2nn_<name>_apply before the simulator steps) and reduced once into `out` [cells, cols] (go2nn_<name>_reduce).  make_in: -> the kernels' input struct on the current
     simulator;  args: the tensors a step's launches take between the input and the table (the specs and the env -> spec map);  reduce_args: what the reduce takes in front
-    of `out`.  The evaluator's attributes stay the owners of every tensor"""
+    of `out`.  The spectrum's step is go2nn_spectrum_record into a trace and its table is made by one go2nn_spectrum_welch after the last step: `state` is what
+    go2nn_<name>_begin starts (the table itself, or that trace, which carries the step counter), begin_args what it takes behind the start step, and resampled says whether
+    the family has a go2nn_<name>_bootstrap (`bootstrap_all`).  The evaluator's attributes stay the owners of every tensor"""
 
-    def __init__(self, name, make_in, table, out, args=(), reduce_args=()):
+    def __init__(self, name, make_in, table, out, args=(), reduce_args=(), state=None, begin_args=(), resampled=True):
         self.name, self.make_in, self.table, self.out, self.reduce_args = name, make_in, table, out, tuple(reduce_args)
         self.args = tuple(C.c_void_p(t.data_ptr()) for t in args)
+        self.state, self.begin_args, self.resampled = (table if state is None else state), tuple(begin_args), bool(resampled)
 
 
 def replicate_metrics(rows):
@@ -586,7 +608,7 @@ class PolicyEvaluator:
         N = self.num_envs
         self.acc = torch.zeros(GO2NN_EVAL_NUM, N, device=self.device)
         self.out = torch.zeros(self.num_cells, GO2NN_EVAL_NUM + 2, dtype=torch.float64, device=self.device)
-        self.tables = []          # the active _ScoreTable records in begin / reduce order: robust, ladder, maneuver, gait, asym
+        self.tables = []          # the active _ScoreTable records in begin / reduce order: robust, ladder, maneuver, gait, asym, spectrum
         if self.perturbations is not None:
             self._build_robust()
         if self.sensors is not None:
@@ -603,6 +625,9 @@ class PolicyEvaluator:
         self.asymmetry = bool(_get(evaluation, "asymmetry", False))
         if self.asymmetry:
             self._build_asymmetry()
+        self.spectrum = bool(_get(evaluation, "spectrum", False))
+        if self.spectrum:
+            self._build_spectrum()
         self.dof_limits = self.env.dof_pos_limits.contiguous().clone()
         self._policy, self._policy_of = None, None
         self.recorder = None
@@ -961,13 +986,17 @@ class PolicyEvaluator:
             raise ValueError("evaluation.blackbox: %d robots x %d steps x %d bytes per frame = %d bytes, more than evaluation.blackbox_max_bytes = %d; shorten "
                              "evaluation.blackbox_seconds or lower evaluation.num_envs" % (self.num_envs, T, GO2NN_TRACE_WIDTH * 4, need, cap))
         self.fall_recorder = FallRecorder(self.env, T, nn_lib=self.nn)
+        self.cell_names = self._cell_names()
+
+    def _cell_names(self):
+        """what a cell of the finest partition is called, in cell order"""
         if self.ladder:
             names = ["%s/level_%d/%s" % (t, lv, s[0]) for t in self.terrain_names for lv in self.levels for s in self.scenarios]
         else:
             axis = self.axis_names if self.axis_key in ("perturbations", "sensors") else [None]          # (a maneuver is the cell's scenario itself)
             names = ["%s/%s" % (t, s[0]) + ("/" + p if p is not None else "") for t in self.terrain_names for s in self.scenarios for p in axis]
         assert len(names) == self.num_cells == self.T * self.S * self.L * self.P
-        self.cell_names = names
+        return names
 
     def _build_bootstrap(self):
         """the bootstrap's device side: the cells' member lists (CSR, env indices ascending within a cell; checked on the host, the launch cannot report a bad index) and
@@ -980,7 +1009,7 @@ class PolicyEvaluator:
         need, cap = B * self.num_cells * cols * 8, int(_get(self.ev, "bootstrap_max_bytes", 256 << 20))
         self.bootstrap_all = bool(_get(self.ev, "bootstrap_all", False))
         if self.bootstrap_all:          # the cap holds the SUM of all tables; the refusal names each table's share, before anything is allocated
-            share = [("eval", cols)] + [(t.name, int(t.out.shape[1])) for t in self.tables]
+            share = [("eval", cols)] + [(t.name, int(t.out.shape[1])) for t in self.tables if t.resampled]
             total = sum(B * self.num_cells * c * 8 for _, c in share)
             if total > cap or any(B * self.num_cells * c >= 2 ** 31 for _, c in share):
                 raise ValueError("evaluation.bootstrap_all: %d replicates x %d cells x 8 bytes x (%s) = %d bytes, more than evaluation.bootstrap_max_bytes = %d (or a table "
@@ -997,7 +1026,53 @@ class PolicyEvaluator:
         self.cell_start, self.cell_envs = torch.from_numpy(self.cell_start_host).to(self.device), torch.from_numpy(self.cell_envs_host).to(self.device)
         self.boot_out = torch.zeros(B, self.num_cells, cols, dtype=torch.float64, device=self.device)
         if self.bootstrap_all:          # one more [B, cells, cols] table per active scoring family, in the families' reduce order
-            self.boot_outs = {t.name: torch.zeros(B, self.num_cells, int(t.out.shape[1]), dtype=torch.float64, device=self.device) for t in self.tables}
+            self.boot_outs = {t.name: torch.zeros(B, self.num_cells, int(t.out.shape[1]), dtype=torch.float64, device=self.device) for t in self.tables if t.resampled}
+
+    def _build_spectrum(self):
+        """the spectrum scorer's device side: the trace of the counted steps (refused before it is allocated when larger than `spectrum_max_bytes`), the twiddle table, the
+        per-robot table and the reduce output per cell"""
+        from .symmetry import joint_kinds
+        ev = self.ev
+        W = _get(ev, "spectrum_window", 64)
+        if isinstance(W, bool) or not isinstance(W, (int, np.integer)) or W % 2 or not GO2NN_SPECTRUM_MIN_WINDOW <= W <= GO2NN_SPECTRUM_MAX_WINDOW:
+            raise ValueError("evaluation.spectrum_window: an even number of policy steps in [%d, %d], got %r" % (GO2NN_SPECTRUM_MIN_WINDOW, GO2NN_SPECTRUM_MAX_WINDOW, W))
+        self.spectrum_window, self.spectrum_fs = int(W), 1.0 / self.dt
+        try:
+            cutoff = float(_get(ev, "spectrum_cutoff_hz", 10.0))
+        except (TypeError, ValueError):
+            cutoff = float("nan")
+        if not (math.isfinite(cutoff) and 0.0 < cutoff <= 0.5 * self.spectrum_fs):
+            raise ValueError("evaluation.spectrum_cutoff_hz: a frequency in (0, fs / 2 = %g] Hz, got %r" % (0.5 * self.spectrum_fs, _get(ev, "spectrum_cutoff_hz")))
+        self.spectrum_cutoff = cutoff
+        cap = _get(ev, "spectrum_max_bytes", 512 << 20)
+        if isinstance(cap, bool) or not isinstance(cap, (int, np.integer)) or cap < 1:
+            raise ValueError("evaluation.spectrum_max_bytes: a number of bytes >= 1, got %r" % (cap,))
+        N, T = self.num_envs, self.steps
+        need = spectrum_trace_rows(T) * N * 4
+        if need > int(cap) or T > GO2NN_SPECTRUM_MAX_STEPS:
+            raise ValueError("evaluation.spectrum: the trace of %d counted steps x %d robots x 25 floats = %d bytes, more than evaluation.spectrum_max_bytes = %d (or more than "
+                             "2^20 steps); lower evaluation.num_envs or evaluation.seconds" % (T, N, need, int(cap)))
+        kinds = [int(k) for k in joint_kinds()]
+        self.spectrum_slots = [j for kind in range(len(SPECTRUM_KINDS)) for j in range(12) if kinds[j] == kind]          # hips, thighs, calves: four joints each
+        if len(self.spectrum_slots) != 12 or any(kinds.count(k) != 4 for k in range(3)) or self.env.num_actions != 12:
+            raise ValueError("evaluation.spectrum: 12 joints, four of each kind (utils/symmetry.py joint_kinds), got %r" % (kinds,))
+        self.strace = torch.zeros(spectrum_trace_rows(T), N, device=self.device)
+        self.stwiddle = torch.from_numpy(spectrum_twiddle(self.spectrum_window)).to(self.device)
+        self.stable = torch.zeros(spectrum_rows(self.spectrum_window), N, device=self.device)
+        self.sout = torch.zeros(self.num_cells, 1 + spectrum_rows(self.spectrum_window), dtype=torch.float64, device=self.device)
+        self.tables.append(_ScoreTable("spectrum", self._spectrum_in, self.stable, self.sout, reduce_args=(self.spectrum_window,), state=self.strace, begin_args=(T,),
+                                       resampled=False))
+
+    def _spectrum_in(self):
+        """the record kernel's view of the simulator's buffers (as _eval_in) and the joints in slot order"""
+        a = _field_views(Go2nnSpectrumIn(), self.env._buf, SPECTRUM_FIELDS)
+        a.joint_of_slot[:] = self.spectrum_slots
+        return a
+
+    def _spectrum_welch(self):
+        """the per-robot table from the trace of the counted steps: one launch, after the last step and outside any capture"""
+        self._check(self.nn.go2nn_spectrum_welch(C.c_void_p(self.strace.data_ptr()), self.num_envs, self.steps, self.spectrum_window, self.spectrum_fs,
+                                                 C.c_void_p(self.stwiddle.data_ptr()), C.c_void_p(self.stable.data_ptr()), self._stream()), "go2nn_spectrum_welch")
 
     def _keep_fallen(self, fell):
         """of the fallen robots, per cell of the finest partition the mode reports, the `blackbox` lowest env indices"""
@@ -1108,6 +1183,8 @@ class PolicyEvaluator:
         if run.asym is not None:
             self._table_launch("accumulate", *run.asym, C.c_void_p(actions.data_ptr()), C.c_void_p(mirrored.data_ptr()))
             self.asym_last = (actions, mirrored)          # (what a step_callback of a test reads next to asym_obs)
+        if run.spectrum is not None:          # this step's actions, torques and reset flags into the trace, behind the trace's own step counter
+            self._check(self.nn.go2nn_spectrum_record(C.byref(run.spectrum[1]), C.c_void_p(self.strace.data_ptr()), self.num_envs, self.steps, self._stream()), "go2nn_spectrum_record")
         if self.recorder is not None:
             self.recorder.record()
         if self.fall_recorder is not None:
@@ -1166,6 +1243,9 @@ class PolicyEvaluator:
         gains GAIT_KEYS.
         With `evaluation.asymmetry` also "asymmetry": the same tree as "gait" ("overall", "groups" and the mode's own keys), every leaf with ASYM_KEYS and "n_envs";
         "asymmetry_table" (go2nn_asym_reduce's raw output per cell), "asymmetry_cells" and "asymmetry_contact_threshold".  "overall" gains nothing.
+        With `evaluation.spectrum` also "spectrum": the same tree as "gait", every leaf with SPECTRUM_KEYS, "<key>/<kind>" for the three joint kinds, SPECTRUM_COUNT_KEYS and
+        "n_envs"; "spectrum_table" (go2nn_spectrum_reduce's raw output per cell), "spectrum_cells", "spectrum_settings" {"window", "cutoff_hz", "fs"} and "spectrum_psd"
+        (what eval_results/spectrum_<it>.npz holds: "freqs" [K], the mean power spectrum "psd" [cells, 2, 3, K], the cell, signal and kind names); "overall" gains SPECTRUM_KEYS.
         With `evaluation.record` also "trace": TrajectoryRecorder.fetch() of the counted steps plus "group_of_robot" (index into terrain_names x scenarios, terrain-major,
         per tracked robot), "terrain_names" and "scenarios".
         With `evaluation.blackbox` also "falls": FallRecorder.fetch() of the kept fallen robots plus the labels a trace gets, "cell_names", "cell_of_robot",
@@ -1204,11 +1284,11 @@ class PolicyEvaluator:
             pairs = [(t, t.make_in()) for t in self.tables]
             by = {t.name: (t, tin) for t, tin in pairs}
             run = types.SimpleNamespace(ein=self._eval_in(), sin=sin, tables=pairs, maneuver=by.get("maneuver"), applied=by.get("maneuver") or by.get("robust"),
-                                        scored=[by[n] for n in ("robust", "ladder", "gait") if n in by], asym=by.get("asym"), jobs=None, hist_m=None)
+                                        scored=[by[n] for n in ("robust", "ladder", "gait") if n in by], asym=by.get("asym"), spectrum=by.get("spectrum"), jobs=None, hist_m=None)
             if run.asym is not None:
                 run.jobs, run.hist_m = self._asym_jobs(pol, env.obs_buf if sin is None else self.delivered)
             for t, _ in pairs:
-                self._check(getattr(self.nn, "go2nn_%s_begin" % t.name)(C.c_void_p(t.table.data_ptr()), self.num_envs, -self.warmup_steps, self._stream()), "go2nn_%s_begin" % t.name)
+                self._check(getattr(self.nn, "go2nn_%s_begin" % t.name)(C.c_void_p(t.state.data_ptr()), self.num_envs, -self.warmup_steps, *t.begin_args, self._stream()), "go2nn_%s_begin" % t.name)
             if self.fall_recorder is not None:          # as above; NOT cleared at the warm-up boundary: a ring's history runs through it
                 self.fall_recorder.bind(env)
                 self.fall_recorder.begin(-self.warmup_steps)
@@ -1226,15 +1306,17 @@ class PolicyEvaluator:
                             "go2nn_eval_bootstrap")
             host, bhost = {}, {}
             boot_all = self.bootstrap > 0 and self.bootstrap_all
+            if run.spectrum is not None:
+                self._spectrum_welch()
             for t, _ in pairs:
                 self._check(getattr(self.nn, "go2nn_%s_reduce" % t.name)(C.c_void_p(t.table.data_ptr()), C.c_void_p(self.group.data_ptr()), self.num_envs, self.num_cells,
                                                                          *t.reduce_args, C.c_void_p(t.out.data_ptr()), self._stream()), "go2nn_%s_reduce" % t.name)
-                if boot_all:          # the family's reduce rows of the SAME redrawn robots (outside any capture, as go2nn_eval_bootstrap above)
+                if boot_all and t.resampled:          # the family's reduce rows of the SAME redrawn robots (outside any capture, as go2nn_eval_bootstrap above)
                     self._check(getattr(self.nn, "go2nn_%s_bootstrap" % t.name)(C.c_void_p(t.table.data_ptr()), C.c_void_p(self.cell_start.data_ptr()), C.c_void_p(self.cell_envs.data_ptr()),
                                                                                 self.num_envs, self.num_cells, self.bootstrap, self.bootstrap_seed, *t.reduce_args,
                                                                                 C.c_void_p(self.boot_outs[t.name].data_ptr()), self._stream()), "go2nn_%s_bootstrap" % t.name)
                 host[t.name] = t.out.cpu().numpy().copy()
-                if boot_all:
+                if boot_all and t.resampled:
                     bhost[t.name] = self.boot_outs[t.name].cpu().numpy().copy()
             if run.asym is not None:
                 self.asym_last = None
@@ -1251,6 +1333,8 @@ class PolicyEvaluator:
             self._gait_results(res, host["gait"])
         if "asym" in host:
             self._asym_results(res, host["asym"])
+        if "spectrum" in host:
+            self._spectrum_results(res, host["spectrum"])
         if btable is not None and self.bootstrap_all:
             self._bootstrap_all_results(res, btable, bhost)
         if trace is not None:
@@ -1393,6 +1477,46 @@ class PolicyEvaluator:
         res["overall"] is left as it is: with the flag on every other result is that of the flag-off run"""
         asym, axes = self._addon_tree(acells, self._asym_row, self._asym_pool)
         res.update(asymmetry=asym, asymmetry_table=acells, asymmetry_cells=axes, asymmetry_contact_threshold=self.asym_threshold)
+
+    def _spectrum_row(self, r):
+        """one row of go2nn_spectrum_reduce, or a sum of rows -> SPECTRUM_KEYS pooled over the three joint kinds and per kind ("<key>/<kind>"), SPECTRUM_COUNT_KEYS and
+        n_envs: ratios of the sums, NaN where nothing was counted (no used window, or no power to take a share of).  Bins k >= 1 only: the DC bin holds what the Hann
+        window leaves of the removed mean"""
+        r = np.asarray(r, np.float64)
+        W, fs, K = self.spectrum_window, self.spectrum_fs, spectrum_bins(self.spectrum_window)
+        per = lambda x, n: float(x) / float(n) if n > 0 else float("nan")
+        f = np.arange(1, K, dtype=np.float64) * (fs / W)
+        high = f >= self.spectrum_cutoff
+        used, skipped = r[1 + GO2NN_SPECTRUM_USED], r[1 + GO2NN_SPECTRUM_SKIPPED]
+        d = {}
+        for si, sig in enumerate(SPECTRUM_SIGNALS):
+            P = np.stack([r[1 + spectrum_row(W, "P", si, ki, 1):1 + spectrum_row(W, "P", si, ki, 0) + K] for ki in range(len(SPECTRUM_KINDS))])
+            M = np.stack([r[1 + spectrum_row(W, "M", si, ki, 1):1 + spectrum_row(W, "M", si, ki, 0) + K] for ki in range(len(SPECTRUM_KINDS))])
+            for name, p, m, joints in [("", P.sum(0), M.sum(0), 12.0)] + [("/" + kind, P[ki], M[ki], 4.0) for ki, kind in enumerate(SPECTRUM_KINDS)]:
+                total, n = float(p.sum()), joints * used          # n: the (window, joint) pairs the sums run over
+                d["%s_hf_share%s" % (sig, name)] = per(p[high].sum(), total)
+                d["%s_centroid_hz%s" % (sig, name)] = per(float(np.dot(f, p)), total)
+                d["%s_smoothness%s" % (sig, name)] = per(2.0 / ((W // 2) * fs) * float(np.dot(f, m)), n)
+                d["%s_power%s" % (sig, name)] = per((fs / W) * total, n)
+        d["spectrum_windows"] = int(used)
+        d["spectrum_skipped_share"] = per(skipped, used + skipped)
+        d["n_envs"] = int(r[0])
+        return d
+
+    def _spectrum_results(self, res, scells):
+        """scells: go2nn_spectrum_reduce's table per cell of the active mode -> res["spectrum"]: the cells' rows summed in fp64 for every partition the mode reports;
+        res["overall"] gains the pooled figures SPECTRUM_KEYS"""
+        spec, axes = self._addon_tree(scells, self._spectrum_row)
+        res["overall"].update({k: spec["overall"][k] for k in SPECTRUM_KEYS})
+        W, K = self.spectrum_window, spectrum_bins(self.spectrum_window)
+        used = scells[:, 1 + GO2NN_SPECTRUM_USED][:, None, None, None]
+        first = 1 + spectrum_row(W, "P", 0, 0)
+        psd = scells[:, first:first + 6 * K].reshape(-1, len(SPECTRUM_SIGNALS), len(SPECTRUM_KINDS), K)
+        psd = np.divide(psd, 4.0 * used, out=np.full(psd.shape, np.nan), where=used > 0)          # the mean over the used windows and a kind's 4 joints
+        settings = {"window": W, "cutoff_hz": self.spectrum_cutoff, "fs": self.spectrum_fs}
+        res.update(spectrum=spec, spectrum_table=scells, spectrum_cells=axes, spectrum_settings=settings,
+                   spectrum_psd=dict(settings, freqs=np.arange(K, dtype=np.float64) * (self.spectrum_fs / W), psd=psd, cell_names=self._cell_names(),
+                                     signals=list(SPECTRUM_SIGNALS), kinds=list(SPECTRUM_KINDS)))
 
     def _bootstrap_results(self, res, bcells):
         """bcells: go2nn_eval_bootstrap's table [B, cells, 12] -> "ci" in every leaf dict _row() made, and res["bootstrap"].  A partition's replicate rows are the sums of
@@ -1586,6 +1710,11 @@ def scalars(res):
         for t, per in res["asymmetry"]["groups"].items():
             for s, d in per.items():
                 out += [("Eval/asymmetry/%s/%s/%s" % (t, s, k), d[k]) for k in ASYM_KEYS]
+    if res.get("spectrum") is not None:          # 'Eval/spectrum/<key>' overall (pooled and per joint kind) and 'Eval/spectrum/<terrain>/<scenario>/<key>' per group
+        out += [("Eval/spectrum/" + k, v) for k, v in res["spectrum"]["overall"].items() if k not in ("n_envs", "ci")]
+        for t, per in res["spectrum"]["groups"].items():
+            for s, d in per.items():
+                out += [("Eval/spectrum/%s/%s/%s" % (t, s, k), d[k]) for k in SPECTRUM_KEYS]
     if res.get("falls") is not None:          # with the black box: how many robots fell on a counted step
         out.append(("Eval/falls/robots_fell", res["falls"]["fell_total"]))
     if res.get("bootstrap") is not None:          # with the bootstrap: 'Eval/ci_low/<metric>' and 'Eval/ci_high/<metric>', the overall figures only
@@ -1623,6 +1752,8 @@ def results_dict(res, it=None):
     if res.get("asymmetry") is not None:          # as the gait section: every partition the mode reports
         d["asymmetry"] = plain(res["asymmetry"])
         d["asymmetry_contact_threshold"] = float(res["asymmetry_contact_threshold"])
+    if res.get("spectrum") is not None:          # as the gait section; the estimator's settings next to the tree
+        d["spectrum"] = dict(plain(res["spectrum"]), **{k: (int(v) if k == "window" else float(v)) for k, v in res["spectrum_settings"].items()})
     if res.get("bootstrap") is not None:          # how the "ci" entries of the leaves above were made
         d["bootstrap"] = {k: res["bootstrap"][k] for k in ("replicates", "seed", "confidence")}
     return d
@@ -1670,6 +1801,12 @@ def format_table(res):
         rows = [(t, s, d) for t, per in res["asymmetry"]["groups"].items() for s, d in per.items()] + [("all", "all", res["asymmetry"]["overall"])]
         for t, s, d in rows:
             lines.append("%-16s %-14s " % (t, s) + " ".join("%18.3e" % d[c] if c.startswith("equivariance") else "%18.4f" % d[c] for c in cols))
+    if res.get("spectrum") is not None:          # one more block: the pooled spectrum figures per group
+        cols = SPECTRUM_KEYS + SPECTRUM_COUNT_KEYS
+        lines += ["", "%-16s %-14s " % ("terrain", "spectrum") + " ".join("%22s" % c for c in cols)]
+        rows = [(t, s, d) for t, per in res["spectrum"]["groups"].items() for s, d in per.items()] + [("all", "all", res["spectrum"]["overall"])]
+        for t, s, d in rows:
+            lines.append("%-16s %-14s " % (t, s) + " ".join("%22.4g" % d[c] for c in cols))
     if res.get("falls") is not None:          # one more block: per cell with falls, how many robots fell and the medians over the kept ones (NaN: no frame before the fall)
         from .recorder import fall_summary
         falls = res["falls"]
@@ -1709,4 +1846,7 @@ def write_results(log_dir, it, res):
     if res.get("falls") is not None:
         from .recorder import write_falls
         write_falls(os.path.join(path, "falls_%s.npz" % it), res["falls"])
+    if res.get("spectrum_psd") is not None:
+        from .recorder import write_spectrum
+        write_spectrum(os.path.join(path, "spectrum_%s.npz" % it), res["spectrum_psd"])
     return out

@@ -93,7 +93,7 @@ _RUNNER_OVERRIDES = ("max_iterations", "experiment_name", "run_name", "load_run"
 def update_cfg_from_args(env_cfg, cfg_train, args):
     """Command-line overrides onto the config objects (legged_gym/utils/helpers.py update_cfg_from_args): --num_envs onto the env config;
     --seed, --resume and the runner fields above onto the train config; the RoboGauge switches when the train config has that section (parsed and ignored: the service is
-    out of scope), --symmetry onto algorithm.symmetry, --diagnostics onto algorithm.diagnostics, --normalize_obs onto runner.empirical_normalization, --normalize_value onto algorithm.normalize_value, and next to them --evaluate / --eval_interval / --record / --robust / --ladder / --maneuvers / --sensors / --gait / --blackbox / --asymmetry / --ci / --ci_all onto the `evaluation` section."""
+    out of scope), --symmetry onto algorithm.symmetry, --diagnostics onto algorithm.diagnostics, --normalize_obs onto runner.empirical_normalization, --normalize_value onto algorithm.normalize_value, and next to them --evaluate / --eval_interval / --record / --robust / --ladder / --maneuvers / --sensors / --gait / --spectrum / --blackbox / --asymmetry / --ci / --ci_all onto the `evaluation` section."""
     if env_cfg is not None and args.num_envs is not None:
         env_cfg.env.num_envs = args.num_envs
     if cfg_train is None:
@@ -146,6 +146,8 @@ def update_cfg_from_args(env_cfg, cfg_train, args):
             ev.sensors = [[n, dict(f)] for n, f in DEFAULT_SENSORS]
         if getattr(args, "gait", False):
             ev.gait = True
+        if getattr(args, "spectrum", False):
+            ev.spectrum = True
         if getattr(args, "blackbox", None) is not None:
             ev.blackbox = args.blackbox
         if getattr(args, "asymmetry", False):
@@ -186,6 +188,8 @@ def get_args(argv=None):
                    "robot does): evaluation.sensors = utils/evaluator.py DEFAULT_SENSORS")
     p.add_argument("--gait", action="store_true", default=False, help="score how the robots walk too (duty factor, stride frequency, slip, swing clearance, support pattern; works "
                    "next to every mode above): evaluation.gait = True")
+    p.add_argument("--spectrum", action="store_true", default=False, help="score how fast the joints are driven too: Welch spectra of every robot's actions and torques (high-"
+                   "frequency share, centroid, CAPS smoothness, power; works next to every mode above): evaluation.spectrum = True")
     p.add_argument("--blackbox", type=int, nargs="?", const=2, help="keep the last seconds before every evaluated robot's first fall and write, per reported cell, those of N "
                    "fallen robots (default 2) to eval_results/falls_<it>.npz (works next to every mode above): evaluation.blackbox = N")
     p.add_argument("--asymmetry", action="store_true", default=False, help="score left-right asymmetry too: how far the policy is from mirror-equivariant on the states it "

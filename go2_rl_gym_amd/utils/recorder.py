@@ -378,3 +378,18 @@ def read_trace(path):
                 out[k] = v.item() if v.ndim == 0 else v
     out["gait"] = gait
     return out
+
+
+def write_spectrum(path, spectrum):
+    """one .npz of the evaluator's mean power spectra (res["spectrum_psd"]): `freqs` [K] in Hz, `psd` [cells, 2, 3, K] — per cell of the active mode, signal and joint kind
+    the mean over the used windows and the kind's 4 joints, NaN for a cell without a used window —, the names `cell_names`, `signals`, `kinds`, and the estimator's
+    `window`, `cutoff_hz` and `fs`"""
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    np.savez(path, **{k: np.asarray(v) for k, v in spectrum.items()})
+    return path
+
+
+def read_spectrum(path):
+    """-> what write_spectrum was given (numbers as Python numbers, name lists as lists)"""
+    with np.load(path, allow_pickle=False) as z:
+        return {k: (z[k].tolist() if z[k].dtype.kind == "U" else z[k].item() if z[k].ndim == 0 else z[k]) for k in z.files}

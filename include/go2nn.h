@@ -1025,6 +1025,54 @@ int go2nn_smooth_loss_set_segments(int32_t segments);
 int go2nn_smooth_loss(const Go2nnSmoothLoss* a, void* stream);
 int go2nn_smooth_indices(int64_t* out, uint8_t* w, const uint8_t* dones, int32_t nmb, int32_t T, int32_t N, uint32_t* key_state, void* stream);
 
+/* ---- the evaluator's action and torque spectra: how fast are the joints of every evaluated robot being driven (go2_rl_gym_amd/utils/evaluator.py, `evaluation.spectrum`;
+ * csrc/go2nn_spectrum.h).
+ * ADDED WITHIN ABI 7: four new entry points and one struct, nothing existing changes, GO2NN_ABI_VERSION stays 7.
+ * A spectrum evaluation step is { ..., go2sim_step, go2nn_eval_accumulate, ..., go2nn_spectrum_record }: one more plain launch per step (capturable; one lane per robot, no
+ * atomics), then ONE go2nn_spectrum_welch after the last step and one go2nn_spectrum_reduce.
+ * THE ESTIMATOR, ONCE: Welch's method on the T counted steps, per robot.  24 signals: the 12 entries of the simulator's `actions` and the 12 of `torques` AFTER the step,
+ * sampled at the policy rate fs = 1 / (sim dt x decimation).  Windows of W samples (even, 8 <= W <= 256), hop W / 2: window w covers the counted frames
+ * [w W / 2, w W / 2 + W); a tail shorter than W is dropped; the positions do not depend on what the robot does.  A window is SKIPPED (and counted as such) when any of its
+ * frames has reset_buf set: that frame shows the post-reset pose, and nothing is analysed across an episode boundary.  Per used window and signal x[0 .. W):
+ *   y[n] = (x[n] - mean(x)) hann[n],   hann[n] = 0.5 - 0.5 cos(2 pi n / W)   (periodic),   X_k = sum_n y[n] exp(-2 pi i k n / W),   k = 0 .. W / 2
+ *   P_k = c_k |X_k|^2 / (fs sum hann^2)        c_k = 2 except c_0 = c_{W/2} = 1          (scipy.signal.welch: window "hann", detrend "constant", scaling "density")
+ *   M_k = c_k |X_k| / sum hann                 (the amplitude of a sinusoid on bin k)
+ * in fp64 (sum hann = W / 2, sum hann^2 = 3 W / 8).  The 12 joints are pooled by KIND — slots 0 .. 3 the hips, 4 .. 7 the thighs, 8 .. 11 the calves; joint_of_slot names
+ * the joint of every slot (utils/symmetry.py joint_kinds()) — and each window's sum over a kind's 4 joints is rounded once to fp32 and added to the robot's table column.
+ * The trace: fp32 [GO2NN_SPECTRUM_TRACE_ROWS(T), N], row-major by row, column e = robot e: the STEP row, then per counted step s the GO2NN_SPECTRUM_CHANNELS rows
+ * 1 + s 25 + channel — the action of slot 0 .. 11, the torque of slot 0 .. 11, the reset flag as 0.f / 1.f.  T x N x 25 x 4 bytes: the caller caps it.
+ * The table: fp32 [GO2NN_SPECTRUM_ROWS(W), N], column e = robot e: USED (windows), SKIPPED (windows), then with K = W / 2 + 1 the row BIN0 + (signal 3 + kind) K + k =
+ * sum P_k and the row BIN0 + 6 K + (signal 3 + kind) K + k = sum M_k over the used windows and the kind's 4 joints (signal 0 action, 1 torque; kind 0 hip, 1 thigh, 2 calf).
+ * go2nn_spectrum_begin: trace = 0, then STEP[e] = start for every e (the evaluator passes -warmup_steps).
+ * go2nn_spectrum_record (AFTER the step), per robot, with s = STEP[e]: STEP[e] = s + 1; if 0 <= s < T the 25 floats of step s are written — bit-exact copies of the fields.
+ * go2nn_spectrum_welch: the table of every robot from its trace, overwritten (not added to).  twiddle: fp64 [W, 2] = (cos, sin)(2 pi n / W) in the trace's memory space.
+ *   No atomics, fixed summation order: two launches give the same bits, and the host build gives the device's.
+ * go2nn_spectrum_reduce: out [G, GO2NN_SPECTRUM_OUT_NUM(W)] (fp64), per group g: column 0 its robots, column 1 + r the fp64 sum of table row r (go2nn_eval_reduce's order).
+ * GO2NN_EINVAL, with nothing written: null pointers, N < 1, T outside [1, GO2NN_SPECTRUM_MAX_STEPS], W odd or outside [8, 256], fs not finite and above 0, an env stride < 1,
+ * a component stride (actions, torques) < 1, a joint_of_slot that is no permutation of 0 .. 11, G outside 1 .. 65535. */
+#define GO2NN_SPECTRUM_MIN_WINDOW 8
+#define GO2NN_SPECTRUM_MAX_WINDOW 256
+#define GO2NN_SPECTRUM_MAX_STEPS 1048576
+#define GO2NN_SPECTRUM_CHANNELS 25
+enum { GO2NN_SPECTRUM_CH_ACTION0 = 0, GO2NN_SPECTRUM_CH_TORQUE0 = 12, GO2NN_SPECTRUM_CH_RESET = 24 };
+#define GO2NN_SPECTRUM_TRACE_STEP 0
+#define GO2NN_SPECTRUM_TRACE_ROWS(T) (1 + GO2NN_SPECTRUM_CHANNELS * (T))
+enum { GO2NN_SPECTRUM_USED = 0, GO2NN_SPECTRUM_SKIPPED, GO2NN_SPECTRUM_BIN0 };
+#define GO2NN_SPECTRUM_BINS(W) ((W) / 2 + 1)
+#define GO2NN_SPECTRUM_ROWS(W) (GO2NN_SPECTRUM_BIN0 + 12 * GO2NN_SPECTRUM_BINS(W))
+#define GO2NN_SPECTRUM_OUT_N 0
+#define GO2NN_SPECTRUM_OUT_ROW0 1
+#define GO2NN_SPECTRUM_OUT_NUM(W) (GO2NN_SPECTRUM_OUT_ROW0 + GO2NN_SPECTRUM_ROWS(W))
+/* The buffers as (pointer, env stride, component stride) in ELEMENTS like Go2nnEvalIn's: actions and torques [N, 12], reset_buf uint8 (comp_stride unused, may be 0). */
+typedef struct Go2nnSpectrumIn {
+  Go2nnEvalField actions, torques, reset_buf;
+  int32_t joint_of_slot[12];
+} Go2nnSpectrumIn;
+int go2nn_spectrum_begin(float* trace, int32_t N, int32_t start, int32_t T, void* stream);
+int go2nn_spectrum_record(const Go2nnSpectrumIn* in, float* trace, int32_t N, int32_t T, void* stream);
+int go2nn_spectrum_welch(const float* trace, int32_t N, int32_t T, int32_t W, double fs, const double* twiddle, float* table, void* stream);
+int go2nn_spectrum_reduce(const float* table, const int32_t* group, int32_t N, int32_t G, int32_t W, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

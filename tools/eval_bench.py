@@ -1,6 +1,6 @@
 """What one policy evaluation costs (utils/evaluator.py), and what the metric kernel saves over torch expressions.
 
-    python tools/eval_bench.py [--task go2_flat] [--reps 3] [--robust] [--ladder] [--maneuvers] [--sensors] [--blackbox] [--asymmetry] [--ci] [--ci_all] [--out profiles/eval_bench.json]
+    python tools/eval_bench.py [--task go2_flat] [--reps 3] [--robust] [--ladder] [--maneuvers] [--sensors] [--blackbox] [--asymmetry] [--ci] [--ci_all] [--spectrum] [--out profiles/eval_bench.json]
 
 Measures, on cuda:0, with the task's default `evaluation` section (1024 robots, 1 s + 10 s):
   * wall time of evaluate() run eagerly and with the captured chunk of steps replayed (simulator re-creation, capture and the final host copy included: it is what
@@ -28,6 +28,10 @@ evaluation.bootstrap_all, alternating, the difference split into launches, copie
 runs each (at least five) in this one session — best, median, spread, every run and the difference of the medians —, and go2nn_eval_bootstrap alone per back-to-back call
 on the evaluation's own accumulators at the plain cells, at --robust's cells and at seven times as many (--robust on a terrain task), each next to the same resampling
 written in numpy on the host with the copy of the accumulators it would need.
+--spectrum: a measurement of its own, written to profiles/spectrum_bench.json: evaluate() run eagerly with evaluation.spectrum off and on, alternating, --reps runs each
+(at least five) in this one session — best, median, spread, every run and the difference of the medians —, go2nn_spectrum_record per back-to-back call, go2nn_spectrum_welch
+per back-to-back launch on the evaluation's own trace, a device-to-device copy of the trace's bytes for scale, and the Welch kernel's registers, LDS and scratch from the
+code object's notes.
 Writes one JSON file and prints it."""
 import argparse
 import ctypes as C
@@ -399,6 +403,74 @@ def bootstrap_all_main(a):
         e.close()
 
 
+def spectrum_main(a):
+    """--spectrum: what `evaluation.spectrum` costs one evaluation, next to the same evaluation without it in the same session (alternating runs), and its launches alone
+    -> profiles/spectrum_bench.json"""
+    from go2_rl_gym_amd import build
+    env_cfg, train_cfg = task_registry.get_cfgs(a.task)
+    ev_cfg = class_to_dict(train_cfg.evaluation)
+    make = lambda on: PolicyEvaluator(env_cfg, dict(ev_cfg, spectrum=on), task_class=task_registry.get_task_class(a.task), device="cuda:0")
+    evs = {"off": make(False), "on": make(True)}
+    from go2_rl_gym_amd.rsl_rl.modules import ActorCritic
+    torch.manual_seed(0)
+    ac = ActorCritic(45, 263, 12, **{k: v for k, v in class_to_dict(train_cfg.policy).items() if k in ("actor_hidden_dims", "critic_hidden_dims", "activation", "init_noise_std")}).to("cuda:0")
+    res = {k: ev.evaluate(ac, use_graph=False) for k, ev in evs.items()}
+    assert res["off"]["table"].tobytes() == res["on"]["table"].tobytes() and "spectrum" not in res["off"]
+    ev = evs["on"]
+    N, T, W, st = ev.num_envs, ev.steps, ev.spectrum_window, ev._stream()
+    entry = {"task": a.task, "device": torch.cuda.get_device_name(0), "num_envs": N, "steps": ev.warmup_steps + T, "counted_steps": T, "window": W, "fs": ev.spectrum_fs,
+             "trace_bytes": int(ev.strace.numel() * 4), "table_bytes": int(ev.stable.numel() * 4), "cells": ev.num_cells,
+             "overall": {k: v for k, v in res["on"]["spectrum"]["overall"].items() if "/" not in k}}
+    entry["registers"] = {name: {k: r[k] for k in ("kernel", "vgpr_count", "sgpr_count", "scratch_bytes_per_lane", "lds_bytes_per_workgroup")}
+                          for name, r in (("welch", build.kernel_resources(build.NN_OUT, match="spectrum_welch_kernel")),
+                                          ("record", build.kernel_resources(build.NN_OUT, match="SpectrumRecord"))) if r}
+    entry["welch_dynamic_lds_bytes"] = 8 * (2 * W + 24 * W + 24)
+    # the per-step launch: 200 back-to-back calls on the evaluation's own buffers (the trace's counter is past T: the launch's early return is NOT what is timed — begin first)
+    sin = ev._spectrum_in()
+    begin = lambda: ev.nn.go2nn_spectrum_begin(C.c_void_p(ev.strace.data_ptr()), N, 0, T, st)
+    rec = lambda: ev.nn.go2nn_spectrum_record(C.byref(sin), C.c_void_p(ev.strace.data_ptr()), N, T, st)
+    keep = ev.strace.clone()
+    assert begin() == 0 and rec() == 0
+    timed(rec, 20)
+    assert begin() == 0
+    dev_us, wall_us = timed(rec, 200)          # steps 0 .. 199 < T: every call writes its 25 rows
+    entry["record"] = {"device_us_per_launch_back_to_back": dev_us, "host_us_per_call": wall_us}
+    begin_us = timed(begin, 20)[0]
+    entry["begin"] = {"device_us_per_launch_back_to_back": begin_us}
+    ev.strace.copy_(keep)
+    # the Welch launch on the evaluation's own trace, and a device-to-device copy of the trace's bytes for scale
+    timed(ev._spectrum_welch, 3)
+    dev_us, wall_us = timed(ev._spectrum_welch, 20)
+    entry["welch"] = {"device_us_per_launch_back_to_back": dev_us, "host_us_per_call": wall_us}
+    other = torch.empty_like(ev.strace)
+    copy = lambda: other.copy_(ev.strace)
+    timed(copy, 3)
+    entry["trace_copy_device_to_device"] = {"device_us_per_copy": timed(copy, 20)[0]}
+    group = C.c_void_p(ev.group.data_ptr())
+    red = lambda: ev.nn.go2nn_spectrum_reduce(C.c_void_p(ev.stable.data_ptr()), group, N, ev.num_cells, W, C.c_void_p(ev.sout.data_ptr()), st)
+    timed(red, 3)
+    entry["reduce"] = {"device_us_per_launch_back_to_back": timed(red, 20)[0]}
+    if not a.kernel_only:
+        walls = {k: [] for k in evs}
+        for _ in range(max(a.reps, 5)):          # alternating, in this one session
+            for k, e in evs.items():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                e.evaluate(ac, use_graph=False)
+                walls[k].append((time.perf_counter() - t0) * 1e3)
+        entry["evaluate_wall_ms_eager"] = {k: {"best": min(w), "median": statistics.median(w), "spread": max(w) - min(w), "all": w} for k, w in walls.items()}
+        entry["evaluate_wall_ms_eager"]["on_minus_off_median"] = statistics.median(walls["on"]) - statistics.median(walls["off"])
+        if os.path.exists(a.out):          # sections of the file this tool does not measure (merged by hand; their "about" says from what) stay
+            with open(a.out) as f:
+                entry.update({k: v for k, v in json.load(f).items() if k in ("bench_py_env_steps_per_s",)})
+        os.makedirs(os.path.dirname(a.out), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(entry, f, indent=1)
+    print(json.dumps(entry))
+    for e in evs.values():
+        e.close()
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--task", default="go2_flat")
@@ -412,9 +484,12 @@ def main():
     p.add_argument("--asymmetry", action="store_true")
     p.add_argument("--ci", action="store_true")
     p.add_argument("--ci_all", action="store_true")
+    p.add_argument("--spectrum", action="store_true")
     p.add_argument("--out", default=None)
     a = p.parse_args()
-    a.out = a.out or os.path.join(ROOT, "profiles", "bootstrap_all_bench.json" if a.ci_all else "bootstrap_bench.json" if a.ci else "asymmetry_bench.json" if a.asymmetry else "blackbox_bench.json" if a.blackbox else "eval_bench.json")
+    a.out = a.out or os.path.join(ROOT, "profiles", "spectrum_bench.json" if a.spectrum else "bootstrap_all_bench.json" if a.ci_all else "bootstrap_bench.json" if a.ci else "asymmetry_bench.json" if a.asymmetry else "blackbox_bench.json" if a.blackbox else "eval_bench.json")
+    if a.spectrum:
+        return spectrum_main(a)
     if a.ci_all:
         return bootstrap_all_main(a)
     if a.ci:
