@@ -75,6 +75,31 @@ SPECTRUM_SIGNALS, SPECTRUM_KINDS = ("action", "torque"), ("hip", "thigh", "calf"
 GO2NN_SPECTRUM_MIN_WINDOW, GO2NN_SPECTRUM_MAX_WINDOW, GO2NN_SPECTRUM_MAX_STEPS = 8, 256, 1 << 20
 GO2NN_SPECTRUM_CHANNELS, GO2NN_SPECTRUM_CH_ACTION0, GO2NN_SPECTRUM_CH_TORQUE0, GO2NN_SPECTRUM_CH_RESET = 25, 0, 12, 24
 GO2NN_SPECTRUM_USED, GO2NN_SPECTRUM_SKIPPED, GO2NN_SPECTRUM_BIN0 = 0, 1, 2
+# the evaluator's actuator loads (GO2NN_ACTUATOR_* of include/go2nn.h): the per-robot rows of the table [GO2NN_ACTUATOR_NUM, N], the rows of one joint and of one foot, each in
+# the order of its enum; the table is the robot rows, then ACTUATOR_JOINT_ROWS per joint, then ACTUATOR_FOOT_ROWS per foot; go2nn_actuator_reduce's output is "n", "n_used",
+# then every table row but "step"; and the buffers of Go2nnActuatorIn in the struct's order
+ACTUATOR_ENV_ROWS = ("step", "used", "dist")
+ACTUATOR_JOINT_ROWS = ("tau_sq", "tau_peak", "tau_sat", "vel_peak", "vel_sat", "work_pos", "work_neg", "margin_min")
+ACTUATOR_FOOT_ROWS = ("fz_peak", "fz_sum", "fz_frames")
+GO2NN_ACTUATOR_JOINT0 = len(ACTUATOR_ENV_ROWS)
+GO2NN_ACTUATOR_FOOT0 = GO2NN_ACTUATOR_JOINT0 + 12 * len(ACTUATOR_JOINT_ROWS)
+GO2NN_ACTUATOR_NUM = GO2NN_ACTUATOR_FOOT0 + 4 * len(ACTUATOR_FOOT_ROWS)
+GO2NN_ACTUATOR_OUT_N, GO2NN_ACTUATOR_OUT_N_USED, GO2NN_ACTUATOR_OUT_ROW0, GO2NN_ACTUATOR_OUT_NUM = 0, 1, 2, GO2NN_ACTUATOR_NUM + 1
+ACTUATOR_FIELDS = ("dof_state", "torques", "contact_forces", "root_states", "reset_buf")
+
+
+def actuator_row(name, index=None):
+    """the table row of `name`: of ACTUATOR_ENV_ROWS, or of ACTUATOR_JOINT_ROWS for joint `index` (DOF order), or of ACTUATOR_FOOT_ROWS for foot `index` (foot_body order)"""
+    if name in ACTUATOR_ENV_ROWS:
+        return ACTUATOR_ENV_ROWS.index(name)
+    if name in ACTUATOR_JOINT_ROWS:
+        return GO2NN_ACTUATOR_JOINT0 + index * len(ACTUATOR_JOINT_ROWS) + ACTUATOR_JOINT_ROWS.index(name)
+    return GO2NN_ACTUATOR_FOOT0 + index * len(ACTUATOR_FOOT_ROWS) + ACTUATOR_FOOT_ROWS.index(name)
+
+
+def actuator_out_col(name, index=None):
+    """the column of `name` in go2nn_actuator_reduce's output: "n", "n_used", or a table row's (actuator_row's arguments)"""
+    return {"n": GO2NN_ACTUATOR_OUT_N, "n_used": GO2NN_ACTUATOR_OUT_N_USED}[name] if name in ("n", "n_used") else GO2NN_ACTUATOR_OUT_ROW0 + actuator_row(name, index) - 1
 
 
 def spectrum_bins(W):
@@ -210,6 +235,12 @@ class Go2nnAsymIn(C.Structure):          # (within ABI 7)
 
 class Go2nnSpectrumIn(C.Structure):          # (within ABI 7)
     _fields_ = [(k, Go2nnEvalField) for k in SPECTRUM_FIELDS] + [("joint_of_slot", C.c_int32 * 12)]
+
+
+class Go2nnActuatorIn(C.Structure):          # (within ABI 7)
+    _fields_ = [(k, Go2nnEvalField) for k in ACTUATOR_FIELDS] + [("dof_vel_offset", C.c_int32), ("contact_body_stride", C.c_int32), ("foot_body", C.c_int32 * 4),
+                                                                 ("pos_lo", C.c_float * 12), ("pos_hi", C.c_float * 12), ("tau_sat_thr", C.c_float * 12),
+                                                                 ("vel_sat_thr", C.c_float * 12), ("contact_threshold", C.c_float), ("pad_", C.c_int32)]
 
 
 def gait_row(foot, name):
@@ -481,7 +512,10 @@ def bind(path):
     lib.go2nn_spectrum_reduce.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
     lib.go2nn_eval_bootstrap_check.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]          # (within ABI 7) the cells' member lists, in host memory
     lib.go2nn_eval_bootstrap.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p]
-    for fam in ("robust", "maneuver", "gait", "asym"):          # (within ABI 7) the same replicates of every scoring family's reduce table
+    lib.go2nn_actuator_begin.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]          # (within ABI 7) the evaluator's actuator loads
+    lib.go2nn_actuator_accumulate.argtypes = [C.POINTER(Go2nnActuatorIn), C.c_void_p, C.c_int32, C.c_void_p]
+    lib.go2nn_actuator_reduce.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+    for fam in ("robust", "maneuver", "gait", "asym", "actuator"):          # (within ABI 7) the same replicates of every scoring family's reduce table
         getattr(lib, "go2nn_%s_bootstrap" % fam).argtypes = lib.go2nn_eval_bootstrap.argtypes
     lib.go2nn_ladder_bootstrap.argtypes = lib.go2nn_eval_bootstrap.argtypes[:7] + [C.c_float, C.c_void_p, C.c_void_p]
     lib.go2nn_maneuver_check_specs.argtypes = [C.c_void_p, C.c_int32]

@@ -1267,3 +1267,4 @@ int go2nn_moe_mix_forward(const float* logits, const float* outs, const float* b
 #include "go2nn_value_norm.h"   // (within ABI 7) value normalisation: the critic predicts returns in units of their running std; one launch behind GAE, one merge per iteration
 #include "go2nn_smooth_loss.h"  // (within ABI 7) the temporal action-smoothness loss of PPO on env-block mini-batches: one pass that walks t, and the mini-batch index list
 #include "go2nn_spectrum.h"     // (within ABI 7) the evaluator's action and torque spectra: a per-step trace of every robot, one Welch pass per evaluation, per-group sums
+#include "go2nn_actuator.h"     // (within ABI 7) the evaluator's actuator loads: per-joint torque, speed, work and limit margin of every robot, foot forces, per-group sums

@@ -322,6 +322,8 @@ class LeggedRobotCfgPPO(BaseConfig):
         spectrum_window = 64    # [policy steps] Welch window length W: even, 8 <= W <= 256; hop W / 2, bin width fs / W (50 Hz / 64 = 0.78 Hz)
         spectrum_cutoff_hz = 10.0  # [Hz] where "high frequency" begins for <signal>_hf_share: inside (0, fs / 2]
         spectrum_max_bytes = 512 << 20  # the trace of steps x num_envs x 25 floats (500 x 1024: 51 MB) is refused above this
+        actuators = False       # True (--actuators): follow every robot's joints and feet on the device and report per joint, per joint kind and over all joints RMS and peak torque, the share of samples at or above `actuators_saturation` x the torque / speed limit, mechanical power, the margin to the soft position limits, the foot forces and the positive work per metre (utils/evaluator.py ACTUATOR_KEYS); an add-on like `gait`, it works next to every mode above
+        actuators_saturation = 0.95  # a torque (joint speed) sample counts as saturated at or above this share of the joint's nominal limit: finite, in (0, 1]
         bootstrap = 0           # B > 0 (--ci [B]): after the reduce, redraw every cell's robots with replacement B times on the device (go2nn_eval_bootstrap) and give every reported figure of RESULT_KEYS a percentile interval ("ci": {metric: [lo, hi]}, utils/evaluator.py CI_KEYS); the same replicates of two checkpoints are paired (utils/evaluator.py compare); 0: nothing is loaded, allocated or launched
         bootstrap_seed = 2718   # the Philox seed of the redraws: the same seed, the same robots in replicate b of every evaluation
         confidence = 0.95       # the intervals' level: the (1 - confidence) / 2 and (1 + confidence) / 2 quantiles of the replicates
@@ -427,6 +429,8 @@ class LeggedRobotCfgCTS(BaseConfig):
         spectrum_window = 64    # [policy steps] Welch window length W: even, 8 <= W <= 256; hop W / 2, bin width fs / W (50 Hz / 64 = 0.78 Hz)
         spectrum_cutoff_hz = 10.0  # [Hz] where "high frequency" begins for <signal>_hf_share: inside (0, fs / 2]
         spectrum_max_bytes = 512 << 20  # the trace of steps x num_envs x 25 floats (500 x 1024: 51 MB) is refused above this
+        actuators = False       # True (--actuators): follow every robot's joints and feet on the device and report per joint, per joint kind and over all joints RMS and peak torque, the share of samples at or above `actuators_saturation` x the torque / speed limit, mechanical power, the margin to the soft position limits, the foot forces and the positive work per metre (utils/evaluator.py ACTUATOR_KEYS); an add-on like `gait`, it works next to every mode above
+        actuators_saturation = 0.95  # a torque (joint speed) sample counts as saturated at or above this share of the joint's nominal limit: finite, in (0, 1]
         bootstrap = 0           # B > 0 (--ci [B]): after the reduce, redraw every cell's robots with replacement B times on the device (go2nn_eval_bootstrap) and give every reported figure of RESULT_KEYS a percentile interval ("ci": {metric: [lo, hi]}, utils/evaluator.py CI_KEYS); the same replicates of two checkpoints are paired (utils/evaluator.py compare); 0: nothing is loaded, allocated or launched
         bootstrap_seed = 2718   # the Philox seed of the redraws: the same seed, the same robots in replicate b of every evaluation
         confidence = 0.95       # the intervals' level: the (1 - confidence) / 2 and (1 + confidence) / 2 quantiles of the replicates

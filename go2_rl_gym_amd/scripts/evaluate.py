@@ -24,6 +24,12 @@ above; --metric then also takes action_hf_share, action_centroid_hz, action_smoo
 all lower is better —, so --all_checkpoints --spectrum --metric action_hf_share compares a --smooth_loss run with a plain one.  The figures have no bootstrap replicates:
 --ci next to --spectrum leaves every interval as it is, and --ci --metric <a spectrum figure> is refused before anything runs.  The mean power spectra per cell go to
 eval_results/spectrum_<checkpoint number>.npz (utils/recorder.py read_spectrum).
+--actuators also scores what the policy does to the motors and the legs (utils/evaluator.py ACTUATOR_KEYS), next to any of the modes above; --metric then also takes
+torque_rms, torque_rms_share, torque_peak, torque_saturation, joint_speed_peak, joint_speed_saturation, positive_power, negative_power, grf_peak, grf_stance_mean and
+energy_per_m — all lower is better — and limit_margin (higher is better), each also per joint kind and per joint (torque_saturation/calf, torque_rms/FL_thigh; a foot figure
+per foot, grf_peak/RR), ranked in its pooled figure's direction, so --all_checkpoints --actuators --metric torque_saturation names the checkpoint that leans least on the
+torque limit.  The extremes torque_peak_max, joint_speed_peak_max, grf_peak_max (lower is better) and limit_margin_min (higher) rank without --ci and are refused with it: a
+bootstrap of an extreme is not one.  A key given without --actuators is refused before anything runs.
 --record N also records N robots of every (terrain x scenario) group and writes eval_results/trace_<checkpoint number>.npz into the run's directory.
 --blackbox [N] also keeps the last seconds before every robot's first fall (utils/recorder.py FallRecorder), prints per cell with falls how many robots fell and when,
 and writes those of N fallen robots per cell (default 2) to eval_results/falls_<checkpoint number>.npz; read_falls and fall_summary read it back.
@@ -45,19 +51,21 @@ from pathlib import Path
 
 from go2_rl_gym_amd.envs import *  # noqa: F401,F403
 from go2_rl_gym_amd.utils import get_args
-from go2_rl_gym_amd.utils.evaluator import (ASYM_KEYS, CI_KEYS, DIAGONAL_PAIRS, GAIT_FOOT_KEYS, GAIT_KEYS, MANEUVER_KEYS, ROBUST_KEYS, SPECTRUM_COUNT_KEYS, SPECTRUM_KEYS, PolicyEvaluator,
+from go2_rl_gym_amd.utils.evaluator import (ACTUATOR_EXTREME_KEYS, ACTUATOR_FOOT_KEYS, ACTUATOR_KEYS, ACTUATOR_KINDS, ASYM_KEYS, CI_KEYS, DIAGONAL_PAIRS, GAIT_FOOT_KEYS, GAIT_KEYS, MANEUVER_KEYS, ROBUST_KEYS, SPECTRUM_COUNT_KEYS, SPECTRUM_KEYS, PolicyEvaluator,
                                             compare, format_table, interval, replicate_metrics, results_dict)
 from go2_rl_gym_amd._nn import SPECTRUM_KINDS
 from go2_rl_gym_amd.utils.helpers import _checkpoint_number, get_load_path
 from go2_rl_gym_amd.utils.task_registry import ROOT_DIR, task_registry
 
-HIGHER_IS_BETTER = ("survival", "speed_along_cmd", "recovered", "mean_level_cleared", "cleared", "settled", "trot_share", "swing_clearance")
+HIGHER_IS_BETTER = ("survival", "speed_along_cmd", "recovered", "mean_level_cleared", "cleared", "settled", "trot_share", "swing_clearance", "limit_margin", "limit_margin_min")
+LEGS = ("FL", "FR", "RL", "RR")
+ACTUATOR_JOINTS = tuple("%s_%s" % (leg, kind) for leg in LEGS for kind in ACTUATOR_KINDS)          # what the actuator scorer names its per-joint keys after ("<key>/<joint>")
 FEET = tuple(leg for pair in DIAGONAL_PAIRS for leg in pair)          # the feet the gait scorer names its per-foot keys after ("<key>/<foot>")
 
 
 def higher_is_better(metric):
     """a per-foot gait figure ("swing_clearance/FL") has the direction of its pooled figure"""
-    return metric in HIGHER_IS_BETTER or (is_foot_metric(metric) and metric.split("/", 1)[0] in HIGHER_IS_BETTER)
+    return metric in HIGHER_IS_BETTER or ((is_foot_metric(metric) or is_actuator_metric(metric)) and metric.split("/", 1)[0] in HIGHER_IS_BETTER)
 
 
 def is_foot_metric(metric):
@@ -67,6 +75,20 @@ def is_foot_metric(metric):
 def is_spectrum_metric(metric):
     """a pooled spectrum figure, or one of a joint kind ("torque_centroid_hz/calf")"""
     return metric in SPECTRUM_KEYS or ("/" in metric and metric.split("/", 1)[0] in SPECTRUM_KEYS and metric.split("/", 1)[1] in SPECTRUM_KINDS)
+
+
+def is_actuator_metric(metric):
+    """an actuator figure or extreme: over all joints / feet, of a joint kind or a joint ("torque_rms/FL_hip"), of a foot ("grf_peak/RR"); energy_per_m has no pools.
+    The joints and feet are the Go2's (LEGS x ACTUATOR_KINDS), known here before a simulator exists so that a key can be refused before anything runs; the evaluator names
+    its keys after env.dof_names and env.body_names, and for a robot named otherwise the pooled and per-kind keys rank and a per-joint key is refused here"""
+    key, _, pool = metric.partition("/")
+    if key not in ACTUATOR_KEYS + ACTUATOR_EXTREME_KEYS:
+        return False
+    if not pool:
+        return "/" not in metric
+    if key == "energy_per_m":
+        return False
+    return pool in LEGS if key in ACTUATOR_FOOT_KEYS + ("grf_peak_max",) else pool in ACTUATOR_KINDS + ACTUATOR_JOINTS
 
 
 def _own_flags(argv):
@@ -95,10 +117,19 @@ def check_metric(metric):
                          "rank by one of %s" % (metric, ", ".join(SPECTRUM_KEYS)))
 
 
+def check_flag_metric(metric, args):
+    """a figure whose flag is not on is refused before anything runs"""
+    if is_actuator_metric(metric) and not getattr(args, "actuators", False):
+        raise ValueError("--metric %s: the figure is scored under --actuators, which is not on" % metric)
+
+
 def check_ci_metric(metric, args):
     """--ci [--ci_all] --metric: refused before anything runs unless the metric will have replicates — with a message that says why"""
     if metric in CI_KEYS:
         return
+    if is_actuator_metric(metric) and metric.split("/", 1)[0] in ACTUATOR_EXTREME_KEYS:
+        raise ValueError("--ci --metric %s: an extreme over the robots has no bootstrap interval — a bootstrap of an extreme is not one (a resampling can only lose the "
+                         "largest value); rank by it without --ci, or by %s" % (metric, metric.replace("_max", "").replace("_min", "")))
     if is_spectrum_metric(metric):
         raise ValueError("--ci --metric %s: the spectrum figures have no replicates (a robot's table is made by one Welch pass after the run and is not resampled, with or "
                          "without --ci_all); rank by it without --ci" % metric)
@@ -108,6 +139,10 @@ def check_ci_metric(metric, args):
     if metric in ("pushes", "switches", "n_envs"):
         raise ValueError("--ci_all --metric %s: an integer count of the design, the same in every resampling of a cell's robots up to which robots were drawn; it gets no "
                          "interval and ranks nothing" % metric)
+    if is_actuator_metric(metric):          # (every one that is left has replicates under --ci_all)
+        if not getattr(args, "actuators", False):
+            raise ValueError("--ci_all --metric %s: the figure is scored under --actuators, which is not on" % metric)
+        return
     if metric == "equivariance_max":
         raise ValueError("--ci_all --metric equivariance_max: a maximum over the robots has no bootstrap interval (a resampling can only lose the largest value); rank by "
                          "equivariance_rmse")
@@ -123,7 +158,7 @@ def check_ci_metric(metric, args):
 def metric_value(row, metric):
     """a checkpoint row's overall `metric`: the scores' own; with --gait a per-foot gait figure (the pooled ones are in `overall`, the per-foot ones in the gait section's);
     with --asymmetry one of the asymmetry figures (kept in their own section: they leave `overall` alone)"""
-    for section in ("gait", "asymmetry", "spectrum"):
+    for section in ("gait", "asymmetry", "spectrum", "actuators"):
         if metric not in row["overall"] and metric in row.get(section, {}).get("overall", {}):
             return row[section]["overall"][metric]
     return row["overall"][metric]
@@ -167,6 +202,7 @@ def evaluate(argv=None, log_root="default", env_kwargs=None, evaluator_kwargs=No
     own, rest = _own_flags(list(sys.argv[1:] if argv is None else argv))
     check_metric(own["metric"])
     args = get_args(rest)
+    check_flag_metric(own["metric"], args)
     if args.ci is not None:          # refused before anything runs: the comparison needs the metric's replicates
         check_ci_metric(own["metric"], args)
     env_cfg, train_cfg = task_registry.get_cfgs(name=args.task)
@@ -205,6 +241,8 @@ def evaluate(argv=None, log_root="default", env_kwargs=None, evaluator_kwargs=No
             rows[-1]["gait"] = {"overall": res["gait"]["overall"], "groups": res["gait"]["groups"]}
         if res.get("asymmetry") is not None:
             rows[-1]["asymmetry"] = {"overall": res["asymmetry"]["overall"], "groups": res["asymmetry"]["groups"]}
+        if res.get("actuators") is not None:
+            rows[-1]["actuators"] = {"overall": res["actuators"]["overall"], "groups": res["actuators"]["groups"]}
         if res.get("spectrum") is not None:
             from go2_rl_gym_amd.utils.recorder import write_spectrum
             rows[-1]["spectrum"] = {"overall": res["spectrum"]["overall"], "groups": res["spectrum"]["groups"]}

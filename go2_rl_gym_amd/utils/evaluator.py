@@ -99,6 +99,22 @@ power at f_k >= `spectrum_cutoff_hz` over the power, `centroid_hz` = sum f_k P_k
 cells' sums, NaN where nothing was counted; res["overall"] gains the eight pooled figures.  They have no bootstrap replicates (`bootstrap_all` leaves the family out).
 With `spectrum = False` nothing of this is loaded, allocated or launched.
 
+What the policy does to the motors and the legs: with `evaluation.actuators` (--actuators) every robot's joints and feet are followed too — an add-on like `gait`: it splits
+nothing and works in the plain evaluation and next to every mode and add-on.  A step gains ONE launch behind the gait scorer's slot, inside the captured chunk,
+    { ..., go2sim_step, ..., go2nn_eval_accumulate, ..., go2nn_actuator_accumulate }
+(csrc/go2nn_actuator.h; the rule is in include/go2nn.h: frames with reset_buf set are not used, as in gait) and the end one go2nn_actuator_reduce over the finest cells the
+mode has.  The limits are the simulator's nominal `torque_limits` and `dof_vel_limits` and the soft position limits the reward uses; a sample counts as saturated at or above
+`actuators_saturation` x the limit (an exact fp32 comparison against a threshold formed once on the host); a foot is in contact above `gait_contact_threshold`.  ACTUATOR_KEYS
+are pooled over a partition's robots — over all joints, per joint kind (`<key>/hip`, `/thigh`, `/calf`) and per joint (`<key>/FL_hip` ...), NaN where nothing was counted:
+`torque_rms` [N m] (what motor heating goes with), `torque_rms_share` (each joint's tau^2 in units of its limit^2), `torque_peak` and `joint_speed_peak` (the mean over the
+robots of each robot's own largest sample), `torque_saturation` and `joint_speed_saturation` (share of samples), `positive_power` and `negative_power` [W] (mean of
+max(+-tau qd, 0) per step, summed over the pool's joints), `limit_margin` [rad] (the mean over robots of each robot's own smallest distance to a position limit; negative past
+it; higher is better); per foot (`<key>/FL` ...) and over the feet `grf_peak` [N] (mean over robots, and feet, of each one's largest vertical force) and `grf_stance_mean`
+(mean force over the contact frames); per partition `energy_per_m` [J/m] (positive mechanical work / distance the root travelled in the plane; NaN below 1 mm per used
+robot, as for `stand`).  ACTUATOR_EXTREME_KEYS — `torque_peak_max`, `joint_speed_peak_max`, `grf_peak_max`, `limit_margin_min`, with the same pools — are the exact max / min
+over a partition's robots, from one more device -> host copy of the table's USED, peak and margin rows; they get no bootstrap interval.  The figures live in
+res["actuators"] only: res["overall"] and every other result are those of the flag-off run.  With `actuators = False` nothing of this is loaded, allocated or launched.
+
 How sure a figure is: with `evaluation.bootstrap = B > 0` (--ci [B]) ONE more launch after go2nn_eval_reduce, on the same accumulators and the same cells, redraws every
 cell's robots with replacement B times (go2nn_eval_bootstrap: csrc/go2nn_bootstrap.h, the rule in include/go2nn.h; Philox seed `bootstrap_seed`) and one more device ->
 host copy brings the [B, cells, 12] fp64 table of resampled reduce rows: res["bootstrap"] = {"replicates", "seed", "confidence", "table", "overall" ([B, 12]: the overall
@@ -110,7 +126,7 @@ cell.  An evaluation is deterministic per robot index, so the same replicates of
 active scoring family (go2nn_<family>_bootstrap, after the family's reduce, outside any captured graph) redraws the SAME robots — the draws depend on (b, g, k, seed) only —
 on the family's table, res["bootstrap"] gains "tables": {family: [B, cells, cols]} and "metrics": {figure: float64 [B]} (the overall replicates of every figure that has an
 interval, the asymmetry's among them), and every leaf that reports a family's figures gains them in its "ci" — the leaves of res["gait"] and res["asymmetry"] too, the gait's
-with the per-foot keys; res["ladder_summary"][t] gains "ci" for level_cleared and mean_level_cleared from the replicate `cleared` curves.  The replicate figures are the row
+with the per-foot keys, the actuators' with every pool's keys but the extremes; res["ladder_summary"][t] gains "ci" for level_cleared and mean_level_cleared from the replicate `cleared` curves.  The replicate figures are the row
 functions' vectorised twins (robust_replicates, ... below: the same IEEE operations on every replicate row and leaf at once); integer counts (pushes, switches, n_envs) and
 equivariance_max (a bootstrap of a maximum is not one) get no interval; `bootstrap_max_bytes` then caps the sum of all tables.  An add-on like `gait`: it reads only the accumulators and the cell
 assignment and works next to every mode; the table is refused above `bootstrap_max_bytes`; with bootstrap = 0 nothing is loaded, allocated or launched.
@@ -134,6 +150,7 @@ from .._nn import (EVAL_FIELDS, EVAL_METRICS, GO2NN_EVAL_NUM, GO2NN_RNN_GRU, GO2
                    gait_out_col, ASYM_FIELDS, ASYM_OUT, ASYM_PAIRS, GO2NN_ASYM_NUM, GO2NN_ASYM_OUT_NUM, Go2nnAsymIn, GO2NN_SENSOR_MAX_DELAY, GO2NN_SENSOR_MAX_SPECS, GO2_OBS_KINDS, SENSOR_KINDS, Go2nnSensorIn, Go2nnSensorSpec)
 from .._nn import (GO2NN_SPECTRUM_MAX_STEPS, GO2NN_SPECTRUM_MAX_WINDOW, GO2NN_SPECTRUM_MIN_WINDOW, GO2NN_SPECTRUM_SKIPPED, GO2NN_SPECTRUM_USED, SPECTRUM_FIELDS, SPECTRUM_KINDS,
                    SPECTRUM_SIGNALS, Go2nnSpectrumIn, spectrum_bins, spectrum_row, spectrum_rows, spectrum_trace_rows, spectrum_twiddle)
+from .._nn import (ACTUATOR_FIELDS, ACTUATOR_FOOT_ROWS, ACTUATOR_JOINT_ROWS, GO2NN_ACTUATOR_NUM, GO2NN_ACTUATOR_OUT_NUM, Go2nnActuatorIn, actuator_out_col, actuator_row)
 from .._nn import mirror_rows
 from .helpers import class_to_dict
 
@@ -173,9 +190,24 @@ ASYM_KEYS = ASYM_EQ_KEYS + ("sym_steps_share",) + tuple("left_share/" + x for x 
 SPECTRUM_FIGURES = ("hf_share", "centroid_hz", "smoothness", "power")
 SPECTRUM_KEYS = tuple("%s_%s" % (s, k) for s in SPECTRUM_SIGNALS for k in SPECTRUM_FIGURES)
 SPECTRUM_COUNT_KEYS = ("spectrum_windows", "spectrum_skipped_share")
+# pooled over a partition's robots, over all joints, per joint kind ("<key>/hip", "/thigh", "/calf") and per joint ("<key>/FL_hip" ...): RMS torque [N m] and the same in units
+# of each joint's limit, the mean over robots of each robot's own peak torque / speed, the share of samples at or above `actuators_saturation` x the limit, the mean positive
+# and negative mechanical power [W] summed over the pool's joints, the mean over robots of each robot's own smallest distance to a soft position limit [rad]; per foot
+# ("<key>/FL" ...) and over the feet the mean of each robot's own largest vertical foot force [N] and the mean force over the contact frames; per partition the positive
+# mechanical work per metre travelled [J/m]; and the extremes over a partition's robots, which are exact maxima / minima and have no bootstrap interval
+ACTUATOR_JOINT_KEYS = ("torque_rms", "torque_rms_share", "torque_peak", "torque_saturation", "joint_speed_peak", "joint_speed_saturation", "positive_power", "negative_power",
+                       "limit_margin")
+ACTUATOR_FOOT_KEYS = ("grf_peak", "grf_stance_mean")
+ACTUATOR_KEYS = ACTUATOR_JOINT_KEYS + ACTUATOR_FOOT_KEYS + ("energy_per_m",)
+ACTUATOR_EXTREME_KEYS = ("torque_peak_max", "joint_speed_peak_max", "grf_peak_max", "limit_margin_min")
+ACTUATOR_KINDS = ("hip", "thigh", "calf")
+# the rows of the per-robot table behind the extremes, as one device -> host copy brings them: USED (a robot without a used frame has none), then the maxima, then the minima
+ACTUATOR_MAX_ROWS = [actuator_row(k, j) for k in ("tau_peak", "vel_peak") for j in range(12)] + [actuator_row("fz_peak", f) for f in range(4)]
+ACTUATOR_MIN_ROWS = [actuator_row("margin_min", j) for j in range(12)]
 # with `bootstrap_all`: what the printed table's interval block shows of each family
 BOOTSTRAP_HEADLINES = (("robust", ("push_falls", "recovered", "recovery_time_s")), ("maneuver", ("switch_falls", "settled", "settle_time_s")),
-                       ("ladder", ("cleared", "mean_level_cleared")), ("gait", ("slip_speed", "trot_share", "swing_clearance")), ("asym", ("equivariance_rmse", "imbalance/torque")))
+                       ("ladder", ("cleared", "mean_level_cleared")), ("gait", ("slip_speed", "trot_share", "swing_clearance")), ("asym", ("equivariance_rmse", "imbalance/torque")),
+                       ("actuator", ("torque_rms_share", "torque_saturation", "energy_per_m")))
 MAX_CHUNK = 50
 # The accumulate kernel runs AFTER the env step, when the simulator has already rolled its action history (last_actions = this step's actions): the previous step's
 # actions — the kernel's `last_actions` input — are then in the simulator's last_last_actions buffer.
@@ -310,6 +342,47 @@ def asym_replicates(rows):
     for x, p in zip(ASYM_LOADS, ASYM_PAIRS):
         d["imbalance/" + x] = _per(v[p + "_imb"], v[p + "_imb_n"])
     return d
+
+
+def actuator_figures(rows, dt, joint_names, foot_names, torque_limits):
+    """rows: float64 [..., GO2NN_ACTUATOR_OUT_NUM (+ the extremes)], go2nn_actuator_reduce's row per leaf (and per replicate) -> {key: float64 [...]} for ACTUATOR_KEYS
+    over every pool; NaN where nothing was counted.  The ONE statement of the figures: PolicyEvaluator._actuator_row is this on a single row, so replicate b's figure is
+    the row function of replicate row b bit for bit.  A pool's sums run over its joints (feet) in DOF (foot_body) order"""
+    r = np.asarray(rows, np.float64)
+    col = lambda name, i=None: r[..., actuator_out_col(name, i)]
+    n_used, used, dist = col("n_used"), col("used"), col("dist")
+
+    def total(name, members, scale=None):
+        acc = np.zeros(used.shape)
+        for i in members:
+            acc = acc + (col(name, i) if scale is None else col(name, i) / scale[i])
+        return acc
+    kind_of = [next((k for k in ACTUATOR_KINDS if k in n), None) for n in joint_names]
+    pools = [("", list(range(12)))] + [("/" + k, [j for j in range(12) if kind_of[j] == k]) for k in ACTUATOR_KINDS] + [("/" + n, [j]) for j, n in enumerate(joint_names)]
+    limit_sq = [float(t) * float(t) for t in torque_limits]
+    d = {}
+    for name, js in pools:
+        nj = float(len(js))
+        d["torque_rms" + name] = np.sqrt(_per(total("tau_sq", js), nj * used))
+        d["torque_rms_share" + name] = np.sqrt(_per(total("tau_sq", js, limit_sq), nj * used))
+        d["torque_peak" + name] = _per(total("tau_peak", js), nj * n_used)
+        d["torque_saturation" + name] = _per(total("tau_sat", js), nj * used)
+        d["joint_speed_peak" + name] = _per(total("vel_peak", js), nj * n_used)
+        d["joint_speed_saturation" + name] = _per(total("vel_sat", js), nj * used)
+        d["positive_power" + name] = _per(total("work_pos", js), used)
+        d["negative_power" + name] = _per(total("work_neg", js), used)
+        d["limit_margin" + name] = _per(total("margin_min", js), nj * n_used)
+    for name, fs in [("", list(range(4)))] + [("/" + n, [f]) for f, n in enumerate(foot_names)]:
+        d["grf_peak" + name] = _per(total("fz_peak", fs), float(len(fs)) * n_used)
+        d["grf_stance_mean" + name] = _per(total("fz_sum", fs), total("fz_frames", fs))
+    moved = dist * dt >= 1e-3 * n_used          # below a millimetre per used robot (`stand`) a cost per metre says nothing
+    d["energy_per_m"] = _per(total("work_pos", list(range(12))), np.where(moved, dist, 0.0))          # (dt cancels: joules per metre)
+    return d
+
+
+def actuator_replicates(rows, dt, joint_names, foot_names, torque_limits):
+    """the bootstrappable actuator figures of replicate rows [B, leaves, cols]: all but the extremes (a bootstrap of an extreme is not one)"""
+    return actuator_figures(rows, dt, joint_names, foot_names, torque_limits)
 
 
 def interval_columns(mat, confidence):
@@ -608,7 +681,7 @@ class PolicyEvaluator:
         N = self.num_envs
         self.acc = torch.zeros(GO2NN_EVAL_NUM, N, device=self.device)
         self.out = torch.zeros(self.num_cells, GO2NN_EVAL_NUM + 2, dtype=torch.float64, device=self.device)
-        self.tables = []          # the active _ScoreTable records in begin / reduce order: robust, ladder, maneuver, gait, asym, spectrum
+        self.tables = []          # the active _ScoreTable records in begin / reduce order: robust, ladder, maneuver, gait, asym, spectrum, actuator
         if self.perturbations is not None:
             self._build_robust()
         if self.sensors is not None:
@@ -620,7 +693,8 @@ class PolicyEvaluator:
         self.gait = bool(_get(evaluation, "gait", False))
         if self.gait:
             self._build_gait()
-        if self.axis_key is not None or self.gait:
+        self.actuators = bool(_get(evaluation, "actuators", False))
+        if self.axis_key is not None or self.gait or self.actuators:
             self._warn_small_cells()
         self.asymmetry = bool(_get(evaluation, "asymmetry", False))
         if self.asymmetry:
@@ -629,6 +703,8 @@ class PolicyEvaluator:
         if self.spectrum:
             self._build_spectrum()
         self.dof_limits = self.env.dof_pos_limits.contiguous().clone()
+        if self.actuators:
+            self._build_actuators()
         self._policy, self._policy_of = None, None
         self.recorder = None
         per_group = int(_get(evaluation, "record", 0) or 0)
@@ -823,7 +899,8 @@ class PolicyEvaluator:
         sizes = np.bincount(self.cell_host, minlength=self.num_cells)
         if sizes.min() < 4:
             axes = " x ".join(self.cell_axes) + (" condition" if self.axis_key == "sensors" else "")
-            what = "cells have fewer than 4 robots (smallest: %d)" if self.axis_key is not None else "groups have fewer than 4 robots (smallest: %d) for the gait figures"
+            pooled = " and ".join(n for n, on in (("gait", self.gait), ("actuator", self.actuators)) if on)
+            what = "cells have fewer than 4 robots (smallest: %d)" if self.axis_key is not None else "groups have fewer than 4 robots (smallest: %d) for the " + pooled + " figures"
             print("[go2_rl_gym_amd] evaluation: %d of %d (%s) %s; raise evaluation.num_envs" % (int((sizes < 4).sum()), self.num_cells, axes, what % int(sizes.min())))
 
     def _cell_views(self, cells, pool=np.sum):
@@ -1063,6 +1140,49 @@ class PolicyEvaluator:
         self.tables.append(_ScoreTable("spectrum", self._spectrum_in, self.stable, self.sout, reduce_args=(self.spectrum_window,), state=self.strace, begin_args=(T,),
                                        resampled=False))
 
+    def _build_actuators(self):
+        """the actuator scorer's device side: the per-robot table, the reduce output per cell, the limits and the two saturation thresholds as the kernel compares them
+        (fp32 products formed once, here), the joints and feet by NAME, and the rows the extremes are read from"""
+        env, ev = self.env, self.ev
+        raw = _get(ev, "actuators_saturation", 0.95)
+        try:
+            sat = float(raw)
+        except (TypeError, ValueError):
+            sat = float("nan")
+        if isinstance(raw, bool) or not (math.isfinite(sat) and 0.0 < sat <= 1.0):
+            raise ValueError("evaluation.actuators_saturation: the share of a joint's torque / speed limit from which a sample counts as saturated, finite and in (0, 1], got %r" % (raw,))
+        self.act_saturation = sat
+        self.act_threshold = float(_get(ev, "gait_contact_threshold", 1.0))
+        if not (math.isfinite(self.act_threshold) and self.act_threshold >= 0.0):
+            raise ValueError("evaluation.gait_contact_threshold: a finite force >= 0 [N], got %r" % (_get(ev, "gait_contact_threshold"),))
+        host = lambda t: t.detach().cpu().numpy().astype(np.float32)
+        self.act_torque_limits, self.act_vel_limits, pos = host(env.torque_limits), host(env.dof_vel_limits), host(self.dof_limits)
+        if self.act_torque_limits.shape != (12,) or self.act_vel_limits.shape != (12,) or pos.shape != (12, 2) or env.num_actions != 12:
+            raise ValueError("evaluation.actuators: the kernel scores 12 joints, got torque limits %s, speed limits %s, position limits %s"
+                             % (self.act_torque_limits.shape, self.act_vel_limits.shape, pos.shape))
+        self.act_pos_lo, self.act_pos_hi = pos[:, 0].copy(), pos[:, 1].copy()
+        self.act_tau_thr, self.act_vel_thr = np.float32(sat) * self.act_torque_limits, np.float32(sat) * self.act_vel_limits
+        self.joint_names = [str(n).replace("_joint", "") for n in env.dof_names]
+        if len(self.joint_names) != 12 or any(sum(k in n for k in ACTUATOR_KINDS) != 1 for n in self.joint_names) or len(set(self.joint_names)) != 12:
+            raise ValueError("evaluation.actuators: the joints %r do not name one hip, thigh or calf each" % (self.joint_names,))
+        self.act_feet = [int(i) for i in env.feet_indices.tolist()]
+        if len(self.act_feet) != 4:
+            raise ValueError("evaluation.actuators: four feet are needed, got bodies %r" % (self.act_feet,))
+        self.act_foot_names = [str(env.body_names[i]).replace("_foot", "") for i in self.act_feet]
+        self.act_table = torch.zeros(GO2NN_ACTUATOR_NUM, self.num_envs, device=self.device)
+        self.act_out = torch.zeros(self.num_cells, GO2NN_ACTUATOR_OUT_NUM, dtype=torch.float64, device=self.device)
+        self.act_extreme_rows = torch.tensor([actuator_row("used")] + ACTUATOR_MAX_ROWS + ACTUATOR_MIN_ROWS, dtype=torch.long, device=self.device)
+        self.tables.append(_ScoreTable("actuator", self._actuator_in, self.act_table, self.act_out))
+
+    def _actuator_in(self):
+        """the actuator kernel's view of the simulator's buffers (as _asym_in) and its limits, by value"""
+        b = self.env._buf
+        a, d = _field_views(Go2nnActuatorIn(), b, ACTUATOR_FIELDS, last=True), b["dof_state"]
+        a.dof_state.comp_stride, a.dof_vel_offset, a.contact_body_stride = d.stride(1), d.stride(2), b["contact_forces"].stride(1)
+        a.foot_body[:], a.contact_threshold = self.act_feet, self.act_threshold
+        a.pos_lo[:], a.pos_hi[:], a.tau_sat_thr[:], a.vel_sat_thr[:] = self.act_pos_lo.tolist(), self.act_pos_hi.tolist(), self.act_tau_thr.tolist(), self.act_vel_thr.tolist()
+        return a
+
     def _spectrum_in(self):
         """the record kernel's view of the simulator's buffers (as _eval_in) and the joints in slot order"""
         a = _field_views(Go2nnSpectrumIn(), self.env._buf, SPECTRUM_FIELDS)
@@ -1246,6 +1366,9 @@ class PolicyEvaluator:
         With `evaluation.spectrum` also "spectrum": the same tree as "gait", every leaf with SPECTRUM_KEYS, "<key>/<kind>" for the three joint kinds, SPECTRUM_COUNT_KEYS and
         "n_envs"; "spectrum_table" (go2nn_spectrum_reduce's raw output per cell), "spectrum_cells", "spectrum_settings" {"window", "cutoff_hz", "fs"} and "spectrum_psd"
         (what eval_results/spectrum_<it>.npz holds: "freqs" [K], the mean power spectrum "psd" [cells, 2, 3, K], the cell, signal and kind names); "overall" gains SPECTRUM_KEYS.
+        With `evaluation.actuators` also "actuators": the same tree as "gait", every leaf with ACTUATOR_KEYS and ACTUATOR_EXTREME_KEYS over all joints / feet, per joint kind,
+        per joint and per foot, and "n_envs"; "actuator_table" (go2nn_actuator_reduce's raw output per cell), "actuator_extremes" (per cell the 28 maxima and 12 minima
+        behind the extremes; -inf / +inf for a cell without a used robot), "actuator_cells" and "actuator_settings" (the limits, the thresholds, the names).  "overall" gains nothing.
         With `evaluation.record` also "trace": TrajectoryRecorder.fetch() of the counted steps plus "group_of_robot" (index into terrain_names x scenarios, terrain-major,
         per tracked robot), "terrain_names" and "scenarios".
         With `evaluation.blackbox` also "falls": FallRecorder.fetch() of the kept fallen robots plus the labels a trace gets, "cell_names", "cell_of_robot",
@@ -1284,7 +1407,7 @@ class PolicyEvaluator:
             pairs = [(t, t.make_in()) for t in self.tables]
             by = {t.name: (t, tin) for t, tin in pairs}
             run = types.SimpleNamespace(ein=self._eval_in(), sin=sin, tables=pairs, maneuver=by.get("maneuver"), applied=by.get("maneuver") or by.get("robust"),
-                                        scored=[by[n] for n in ("robust", "ladder", "gait") if n in by], asym=by.get("asym"), spectrum=by.get("spectrum"), jobs=None, hist_m=None)
+                                        scored=[by[n] for n in ("robust", "ladder", "gait", "actuator") if n in by], asym=by.get("asym"), spectrum=by.get("spectrum"), jobs=None, hist_m=None)
             if run.asym is not None:
                 run.jobs, run.hist_m = self._asym_jobs(pol, env.obs_buf if sin is None else self.delivered)
             for t, _ in pairs:
@@ -1320,6 +1443,8 @@ class PolicyEvaluator:
                     bhost[t.name] = self.boot_outs[t.name].cpu().numpy().copy()
             if run.asym is not None:
                 self.asym_last = None
+            # the actuators' extremes: ONE more device -> host copy, of the USED row and the 28 + 12 peak and margin rows of every robot
+            extremes = self.act_table.index_select(0, self.act_extreme_rows).cpu().numpy() if "actuator" in by else None
             table = self.out.cpu().numpy().copy()          # the device -> host copy (and synchronisation) of an evaluation
             btable = self.boot_out.cpu().numpy().copy() if self.bootstrap > 0 else None
             trace = self.recorder.fetch() if self.recorder is not None else None
@@ -1335,6 +1460,8 @@ class PolicyEvaluator:
             self._asym_results(res, host["asym"])
         if "spectrum" in host:
             self._spectrum_results(res, host["spectrum"])
+        if "actuator" in host:
+            self._actuator_results(res, host["actuator"], extremes)
         if btable is not None and self.bootstrap_all:
             self._bootstrap_all_results(res, btable, bhost)
         if trace is not None:
@@ -1518,6 +1645,64 @@ class PolicyEvaluator:
                    spectrum_psd=dict(settings, freqs=np.arange(K, dtype=np.float64) * (self.spectrum_fs / W), psd=psd, cell_names=self._cell_names(),
                                      signals=list(SPECTRUM_SIGNALS), kinds=list(SPECTRUM_KINDS)))
 
+    @staticmethod
+    def _actuator_pool(rows, axis=0):
+        """stacked actuator rows [reduce columns | maxima | minima] -> the row of their union along `axis` (not the last): sums, the max of the maxima, the min of the minima"""
+        rows = np.asarray(rows, np.float64)
+        out, a, b = rows.sum(axis), GO2NN_ACTUATOR_OUT_NUM, GO2NN_ACTUATOR_OUT_NUM + len(ACTUATOR_MAX_ROWS)
+        out[..., a:b] = rows[..., a:b].max(axis)
+        out[..., b:] = rows[..., b:].min(axis)
+        return out
+
+    def _actuator_rows(self, rows):
+        """rows [L, cols]: L rows of go2nn_actuator_reduce, or pooled ones -> L dicts: ACTUATOR_KEYS over all joints / feet, per joint kind, per joint and per foot, and
+        n_envs — actuator_figures of all rows at once (numpy's elementwise IEEE operations: a row's figures do not depend on its neighbours); rows that carry the extremes
+        behind the reduce columns (_actuator_pool) also give ACTUATOR_EXTREME_KEYS, NaN without a used robot"""
+        rows = np.asarray(rows, np.float64)
+        d = actuator_figures(rows[:, :GO2NN_ACTUATOR_OUT_NUM], self.dt, self.joint_names, self.act_foot_names, self.act_torque_limits)
+        if rows.shape[1] > GO2NN_ACTUATOR_OUT_NUM:
+            x = rows[:, GO2NN_ACTUATOR_OUT_NUM:]
+            x = np.where(np.isfinite(x), x, np.nan)          # (-inf / +inf: no robot of the partition has a used frame — then none of its entries is finite)
+            tau, vel, fz, margin = x[:, 0:12], x[:, 12:24], x[:, 24:28], x[:, 28:40]
+            kind_of = [next(k for k in ACTUATOR_KINDS if k in n) for n in self.joint_names]
+            pools = [("", list(range(12)))] + [("/" + k, [j for j in range(12) if kind_of[j] == k]) for k in ACTUATOR_KINDS] + [("/" + n, [j]) for j, n in enumerate(self.joint_names)]
+            for name, js in pools:
+                d["torque_peak_max" + name], d["joint_speed_peak_max" + name], d["limit_margin_min" + name] = tau[:, js].max(1), vel[:, js].max(1), margin[:, js].min(1)
+            for name, fs in [("", list(range(4)))] + [("/" + n, [f]) for f, n in enumerate(self.act_foot_names)]:
+                d["grf_peak_max" + name] = fz[:, fs].max(1)
+        keys, cols = list(d), [v.tolist() for v in d.values()]
+        return [dict(zip(keys, vals), n_envs=int(n)) for vals, n in zip(zip(*cols), rows[:, 0])]
+
+    def _actuator_row(self, r):
+        """one row of go2nn_actuator_reduce, or a pooled one -> its figures (_actuator_rows)"""
+        return self._actuator_rows(np.asarray(r, np.float64)[None])[0]
+
+    def _actuator_results(self, res, acells, extremes):
+        """acells: go2nn_actuator_reduce's table per cell of the active mode;  extremes [1 + 28 + 12, N]: the USED, peak and margin rows of every robot -> res["actuators"]:
+        the cells' rows pooled for every partition the mode reports — sums in fp64, the extremes as the exact max / min over the partition's robots that have a used frame.
+        res["overall"] is left as it is: with the flag on every other result is that of the flag-off run"""
+        n_max = len(ACTUATOR_MAX_ROWS)
+        ext = np.concatenate([np.full((self.num_cells, n_max), -np.inf), np.full((self.num_cells, len(ACTUATOR_MIN_ROWS)), np.inf)], 1)
+        used = extremes[0] > 0
+        for c in range(self.num_cells):
+            ids = np.nonzero((self.cell_host == c) & used)[0]
+            if len(ids):
+                ext[c, :n_max], ext[c, n_max:] = extremes[1:1 + n_max][:, ids].max(1), extremes[1 + n_max:][:, ids].min(1)
+        # the pooled row of every leaf first, then the figures of all leaves in one vectorised pass (a leaf has some 200 of them)
+        tree, axes = self._addon_tree(np.concatenate([acells, ext], 1), lambda r: np.array(r, np.float64), self._actuator_pool)
+        leaves = []
+
+        def walk(node, visit):
+            return {k: walk(v, visit) for k, v in node.items()} if isinstance(node, dict) else visit(node)
+        walk(tree, leaves.append)
+        figures = iter(self._actuator_rows(np.stack(leaves)))
+        tree = walk(tree, lambda _: next(figures))
+        settings = {"saturation": self.act_saturation, "contact_threshold": self.act_threshold, "joint_names": list(self.joint_names), "foot_names": list(self.act_foot_names),
+                    "torque_limits": [float(x) for x in self.act_torque_limits], "joint_speed_limits": [float(x) for x in self.act_vel_limits],
+                    "position_limits": [[float(a), float(b)] for a, b in zip(self.act_pos_lo, self.act_pos_hi)],
+                    "torque_saturation_thresholds": [float(x) for x in self.act_tau_thr], "joint_speed_saturation_thresholds": [float(x) for x in self.act_vel_thr]}
+        res.update(actuators=tree, actuator_table=acells, actuator_extremes=ext, actuator_cells=axes, actuator_settings=settings)
+
     def _bootstrap_results(self, res, bcells):
         """bcells: go2nn_eval_bootstrap's table [B, cells, 12] -> "ci" in every leaf dict _row() made, and res["bootstrap"].  A partition's replicate rows are the sums of
         its cells' replicate rows: _cell_views, which gives _results its reshapes and sums, one axis further in"""
@@ -1599,10 +1784,11 @@ class PolicyEvaluator:
         conf, bs, dt = self.confidence, res["bootstrap"], self.dt
         metrics = dict(replicate_metrics(bs["overall"]))
         twins = {"robust": lambda r: robust_replicates(r, dt), "maneuver": lambda r: maneuver_replicates(r, dt), "ladder": lambda r: ladder_replicates(r, dt),
-                 "gait": lambda r: gait_replicates(r, dt, self.foot_names), "asym": asym_replicates}
+                 "gait": lambda r: gait_replicates(r, dt, self.foot_names), "asym": asym_replicates,
+                 "actuator": lambda r: actuator_replicates(r, dt, self.joint_names, self.act_foot_names, self.act_torque_limits)}
         for name, table in bhost.items():
-            if name in ("gait", "asym"):
-                root = res["gait" if name == "gait" else "asymmetry"]
+            if name in ("gait", "asym", "actuator"):
+                root = res[{"gait": "gait", "asym": "asymmetry", "actuator": "actuators"}[name]]
                 leaves = self._addon_replicates(table, self._asym_pool if name == "asym" else np.sum)
             else:
                 root, leaves = res, self._mode_replicates(res, name, table)
@@ -1715,6 +1901,11 @@ def scalars(res):
         for t, per in res["spectrum"]["groups"].items():
             for s, d in per.items():
                 out += [("Eval/spectrum/%s/%s/%s" % (t, s, k), d[k]) for k in SPECTRUM_KEYS]
+    if res.get("actuators") is not None:          # 'Eval/actuators/<key>' overall (every pool) and 'Eval/actuators/<terrain>/<scenario>/<key>' per group (over all joints / feet)
+        out += [("Eval/actuators/" + k, v) for k, v in res["actuators"]["overall"].items() if k not in ("n_envs", "ci")]
+        for t, per in res["actuators"]["groups"].items():
+            for s, d in per.items():
+                out += [("Eval/actuators/%s/%s/%s" % (t, s, k), d[k]) for k in ACTUATOR_KEYS + ACTUATOR_EXTREME_KEYS]
     if res.get("falls") is not None:          # with the black box: how many robots fell on a counted step
         out.append(("Eval/falls/robots_fell", res["falls"]["fell_total"]))
     if res.get("bootstrap") is not None:          # with the bootstrap: 'Eval/ci_low/<metric>' and 'Eval/ci_high/<metric>', the overall figures only
@@ -1726,6 +1917,8 @@ def scalars(res):
                     out += [("Eval/ci_low/" + k, lo), ("Eval/ci_high/" + k, hi)]
             for k, (lo, hi) in ((res.get("asymmetry") or {}).get("overall", {}).get("ci") or {}).items():
                 out += [("Eval/asymmetry/ci_low/" + k, lo), ("Eval/asymmetry/ci_high/" + k, hi)]
+            for k, (lo, hi) in ((res.get("actuators") or {}).get("overall", {}).get("ci") or {}).items():
+                out += [("Eval/actuators/ci_low/" + k, lo), ("Eval/actuators/ci_high/" + k, hi)]
     return out
 
 
@@ -1754,6 +1947,8 @@ def results_dict(res, it=None):
         d["asymmetry_contact_threshold"] = float(res["asymmetry_contact_threshold"])
     if res.get("spectrum") is not None:          # as the gait section; the estimator's settings next to the tree
         d["spectrum"] = dict(plain(res["spectrum"]), **{k: (int(v) if k == "window" else float(v)) for k, v in res["spectrum_settings"].items()})
+    if res.get("actuators") is not None:          # as the gait section; the limits and the saturation share next to the tree
+        d["actuators"] = dict(plain(res["actuators"]), settings=dict(res["actuator_settings"]))
     if res.get("bootstrap") is not None:          # how the "ci" entries of the leaves above were made
         d["bootstrap"] = {k: res["bootstrap"][k] for k in ("replicates", "seed", "confidence")}
     return d
@@ -1807,6 +2002,12 @@ def format_table(res):
         rows = [(t, s, d) for t, per in res["spectrum"]["groups"].items() for s, d in per.items()] + [("all", "all", res["spectrum"]["overall"])]
         for t, s, d in rows:
             lines.append("%-16s %-14s " % (t, s) + " ".join("%22.4g" % d[c] for c in cols))
+    if res.get("actuators") is not None:          # one more block: per joint kind the torque, speed and margin figures, then the foot forces and the work per metre
+        cols = tuple("%s/%s" % (k, kind) for kind in ACTUATOR_KINDS for k in ("torque_rms", "torque_peak", "torque_saturation", "joint_speed_peak", "limit_margin")) + ("grf_peak", "energy_per_m")
+        lines += ["", "%-16s %-14s " % ("terrain", "actuators") + " ".join("%23s" % c for c in cols)]
+        rows = [(t, s, d) for t, per in res["actuators"]["groups"].items() for s, d in per.items()] + [("all", "all", res["actuators"]["overall"])]
+        for t, s, d in rows:
+            lines.append("%-16s %-14s " % (t, s) + " ".join("%23.4f" % d[c] for c in cols))
     if res.get("falls") is not None:          # one more block: per cell with falls, how many robots fell and the medians over the kept ones (NaN: no frame before the fall)
         from .recorder import fall_summary
         falls = res["falls"]
@@ -1825,8 +2026,9 @@ def format_table(res):
         lines += ["", "%-36s " % head + " ".join("%34s" % c for c in cols)]
         lines.append("%-36s " % "all" + " ".join("%34s" % ("%.4f [%.4f, %.4f]" % ((res["overall"][c],) + tuple(res["overall"]["ci"][c]))) for c in cols))
         if "tables" in bs:          # with `bootstrap_all`: the active families' headline figures
-            cells = [(c, res["overall"]) for fam, cs in BOOTSTRAP_HEADLINES for c in cs if fam in bs["tables"] and fam != "asym"]
+            cells = [(c, res["overall"]) for fam, cs in BOOTSTRAP_HEADLINES for c in cs if fam in bs["tables"] and fam not in ("asym", "actuator")]
             cells += [(c, res["asymmetry"]["overall"]) for fam, cs in BOOTSTRAP_HEADLINES for c in cs if fam == "asym" and fam in bs["tables"]]
+            cells += [(c, res["actuators"]["overall"]) for fam, cs in BOOTSTRAP_HEADLINES for c in cs if fam == "actuator" and fam in bs["tables"]]
             if cells:
                 lines += ["%-36s " % "" + " ".join("%34s" % c for c, _ in cells)]
                 lines.append("%-36s " % "all" + " ".join("%34s" % ("%.4g [%.4g, %.4g]" % ((d[c],) + tuple(d["ci"][c]))) for c, d in cells))

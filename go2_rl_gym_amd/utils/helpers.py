@@ -93,7 +93,7 @@ _RUNNER_OVERRIDES = ("max_iterations", "experiment_name", "run_name", "load_run"
 def update_cfg_from_args(env_cfg, cfg_train, args):
     """Command-line overrides onto the config objects (legged_gym/utils/helpers.py update_cfg_from_args): --num_envs onto the env config;
     --seed, --resume and the runner fields above onto the train config; the RoboGauge switches when the train config has that section (parsed and ignored: the service is
-    out of scope), --symmetry onto algorithm.symmetry, --diagnostics onto algorithm.diagnostics, --normalize_obs onto runner.empirical_normalization, --normalize_value onto algorithm.normalize_value, and next to them --evaluate / --eval_interval / --record / --robust / --ladder / --maneuvers / --sensors / --gait / --spectrum / --blackbox / --asymmetry / --ci / --ci_all onto the `evaluation` section."""
+    out of scope), --symmetry onto algorithm.symmetry, --diagnostics onto algorithm.diagnostics, --normalize_obs onto runner.empirical_normalization, --normalize_value onto algorithm.normalize_value, and next to them --evaluate / --eval_interval / --record / --robust / --ladder / --maneuvers / --sensors / --gait / --spectrum / --actuators / --blackbox / --asymmetry / --ci / --ci_all onto the `evaluation` section."""
     if env_cfg is not None and args.num_envs is not None:
         env_cfg.env.num_envs = args.num_envs
     if cfg_train is None:
@@ -148,6 +148,8 @@ def update_cfg_from_args(env_cfg, cfg_train, args):
             ev.gait = True
         if getattr(args, "spectrum", False):
             ev.spectrum = True
+        if getattr(args, "actuators", False):
+            ev.actuators = True
         if getattr(args, "blackbox", None) is not None:
             ev.blackbox = args.blackbox
         if getattr(args, "asymmetry", False):
@@ -190,6 +192,9 @@ def get_args(argv=None):
                    "next to every mode above): evaluation.gait = True")
     p.add_argument("--spectrum", action="store_true", default=False, help="score how fast the joints are driven too: Welch spectra of every robot's actions and torques (high-"
                    "frequency share, centroid, CAPS smoothness, power; works next to every mode above): evaluation.spectrum = True")
+    p.add_argument("--actuators", action="store_true", default=False, help="score what the policy does to the motors and the legs too: per-joint RMS and peak torque, the "
+                   "share of samples at the torque / speed limit, mechanical power, margin to the joint stops, foot forces, energy per metre (works next to every mode "
+                   "above): evaluation.actuators = True")
     p.add_argument("--blackbox", type=int, nargs="?", const=2, help="keep the last seconds before every evaluated robot's first fall and write, per reported cell, those of N "
                    "fallen robots (default 2) to eval_results/falls_<it>.npz (works next to every mode above): evaluation.blackbox = N")
     p.add_argument("--asymmetry", action="store_true", default=False, help="score left-right asymmetry too: how far the policy is from mirror-equivariant on the states it "

@@ -1073,6 +1073,65 @@ int go2nn_spectrum_record(const Go2nnSpectrumIn* in, float* trace, int32_t N, in
 int go2nn_spectrum_welch(const float* trace, int32_t N, int32_t T, int32_t W, double fs, const double* twiddle, float* table, void* stream);
 int go2nn_spectrum_reduce(const float* table, const int32_t* group, int32_t N, int32_t G, int32_t W, double* out, void* stream);
 
+/* ---- the evaluator's actuator loads: what does every evaluated robot do to its motors and its legs (go2_rl_gym_amd/utils/evaluator.py, `evaluation.actuators`;
+ * csrc/go2nn_actuator.h).
+ * ADDED WITHIN ABI 7: four new entry points and one struct, nothing existing changes, GO2NN_ABI_VERSION stays 7.
+ * An actuator evaluation step is { ..., go2sim_step, go2nn_eval_accumulate, ..., go2nn_actuator_accumulate }: one more plain launch per step (capturable; one lane per robot,
+ * the twelve joints and four feet unrolled inside the lane, no LDS, no atomics), one go2nn_actuator_reduce at the end and, for intervals, one go2nn_actuator_bootstrap.
+ * The table: fp32 [GO2NN_ACTUATOR_NUM, N], row-major by row, column e = robot e: the per-robot rows of the first enum below, then GO2NN_ACTUATOR_JOINT_ROWS rows per joint j
+ * (row GO2NN_ACTUATOR_JOINT0 + j * GO2NN_ACTUATOR_JOINT_ROWS + the second enum; j in the simulator's DOF order), then GO2NN_ACTUATOR_FOOT_ROWS rows per foot f (row
+ * GO2NN_ACTUATOR_FOOT0 + f * GO2NN_ACTUATOR_FOOT_ROWS + the third enum; f in foot_body order).  Counts are whole numbers held in fp32 (exact below 2^24).
+ * go2nn_actuator_begin: table = 0, then STEP[e] = start for every e (the evaluator passes -warmup_steps).
+ * go2nn_actuator_accumulate (AFTER the step), per robot, with s = STEP[e]:
+ *   STEP = s + 1.  s < 0: nothing more.  reset_buf set: the frame is not used (the gait rule: it shows the post-reset pose).
+ *   otherwise, with first = (USED == 0):  USED += 1;  DIST += sqrt(vx^2 + vy^2), the root's world planar speed root_states[7:9] (x dt: metres);
+ *   per joint j, with tau = torques[j] (the torque APPLIED in the last substep, after the simulator's clip), q = dof_state[j, 0], qd = dof_state[j, 1]:
+ *     TAU_SQ += tau^2;  TAU_PEAK = max(TAU_PEAK, |tau|);  TAU_SAT += (|tau| >= tau_sat_thr[j]);  VEL_PEAK = max(VEL_PEAK, |qd|);  VEL_SAT += (|qd| >= vel_sat_thr[j]);
+ *     p = tau * qd (one rounded fp32 product):  WORK_POS += max(p, 0);  WORK_NEG += max(-p, 0)          (x dt: joules)
+ *     m = min(q - pos_lo[j], pos_hi[j] - q):  MARGIN_MIN = first ? m : min(MARGIN_MIN, m)                (negative past a limit)
+ *   per foot f, with fz = contact_forces[foot_body[f], z]:  FZ_PEAK = max(FZ_PEAK, fz);  if fz > contact_threshold (strictly, the gait rule): FZ_SUM += fz, FZ_FRAMES += 1.
+ *   The two saturation comparisons are exact fp32 comparisons against thresholds the host forms once (the evaluator: `actuators_saturation` x the nominal limit).
+ * go2nn_actuator_reduce: out [G, GO2NN_ACTUATOR_OUT_NUM] (fp64), per group g: column N its robots, N_USED those with USED > 0, then column GO2NN_ACTUATOR_OUT_ROW0 + r - 1
+ * the fp64 sum of table row r >= 1 (USED, DIST, the 96 joint rows, the 12 foot rows).  EVERY column is a sum: a peak or margin column is the sum over the robots of each
+ * robot's own peak or margin (divide by N_USED for their mean); a robot with USED == 0 holds zeros in every row.  The summation scheme (and the device function) of
+ * go2nn_eval_reduce: fixed order, bit-equal outputs for equal inputs, group ids outside [0, G) ignored, an empty group gives zeros.
+ * go2nn_actuator_bootstrap: go2nn_gait_bootstrap's rule and refusals on this table and these columns (the same draws: replicate (b, g) of every family redraws the same robots). */
+enum { GO2NN_ACTUATOR_STEP = 0, GO2NN_ACTUATOR_USED, GO2NN_ACTUATOR_DIST, GO2NN_ACTUATOR_JOINT0 };
+enum {
+  GO2NN_ACTUATOR_J_TAU_SQ = 0, GO2NN_ACTUATOR_J_TAU_PEAK, GO2NN_ACTUATOR_J_TAU_SAT, GO2NN_ACTUATOR_J_VEL_PEAK, GO2NN_ACTUATOR_J_VEL_SAT, GO2NN_ACTUATOR_J_WORK_POS,
+  GO2NN_ACTUATOR_J_WORK_NEG, GO2NN_ACTUATOR_J_MARGIN_MIN, GO2NN_ACTUATOR_JOINT_ROWS
+};
+#define GO2NN_ACTUATOR_FOOT0 (GO2NN_ACTUATOR_JOINT0 + 12 * GO2NN_ACTUATOR_JOINT_ROWS)
+enum { GO2NN_ACTUATOR_F_FZ_PEAK = 0, GO2NN_ACTUATOR_F_FZ_SUM, GO2NN_ACTUATOR_F_FZ_FRAMES, GO2NN_ACTUATOR_FOOT_ROWS };
+#define GO2NN_ACTUATOR_NUM (GO2NN_ACTUATOR_FOOT0 + 4 * GO2NN_ACTUATOR_FOOT_ROWS)          /* 111 */
+#define GO2NN_ACTUATOR_OUT_N 0
+#define GO2NN_ACTUATOR_OUT_N_USED 1
+#define GO2NN_ACTUATOR_OUT_ROW0 2                                           /* column GO2NN_ACTUATOR_OUT_ROW0 + r - 1 belongs to table row r >= 1 */
+#define GO2NN_ACTUATOR_OUT_NUM (GO2NN_ACTUATOR_OUT_ROW0 + GO2NN_ACTUATOR_NUM - 1)          /* 112 = 7 x 16 = 8 x 14 = 4 x 28: equal column windows exist */
+/* The buffers as (pointer, env stride, component stride) in ELEMENTS like Go2nnAsymIn's: dof_state [N, 12, 2] (dof_vel_offset elements from a joint's position to its
+ * velocity), torques [N, 12], contact_forces [N, bodies, 3] with contact_body_stride between bodies, root_states [N, 13], reset_buf uint8 (comp_stride unused, may be 0).
+ * foot_body names the four foot bodies.  BY VALUE (twelve entries need no device table): pos_lo / pos_hi [rad], the position limits the margin is taken to; tau_sat_thr
+ * [N m] and vel_sat_thr [rad/s], at and above which a sample counts as saturated; contact_threshold in newtons, finite and >= 0.  Nothing but the table is written. */
+typedef struct Go2nnActuatorIn {
+  Go2nnEvalField dof_state, torques, contact_forces, root_states, reset_buf;
+  int32_t dof_vel_offset;
+  int32_t contact_body_stride;
+  int32_t foot_body[4];
+  float pos_lo[12], pos_hi[12];
+  float tau_sat_thr[12], vel_sat_thr[12];
+  float contact_threshold;
+  int32_t pad_;
+} Go2nnActuatorIn;
+/* GO2NN_EINVAL for a null table or N < 1. */
+int go2nn_actuator_begin(float* table, int32_t N, int32_t start, void* stream);
+/* GO2NN_EINVAL, with nothing written, for null pointers, N < 1, an env stride < 1, a component stride (vector fields) < 1, dof_vel_offset or contact_body_stride < 1,
+ * foot_body < 0, a position limit that is not finite or pos_lo > pos_hi, a saturation threshold that is not finite and above 0, a contact_threshold that is negative or
+ * not finite. */
+int go2nn_actuator_accumulate(const Go2nnActuatorIn* in, float* table, int32_t N, void* stream);
+/* GO2NN_EINVAL for null pointers, N < 1, G outside 1 .. 65535. */
+int go2nn_actuator_reduce(const float* table, const int32_t* group, int32_t N, int32_t G, double* out, void* stream);
+int go2nn_actuator_bootstrap(const float* table, const int32_t* cell_start, const int32_t* cell_envs, int32_t N, int32_t G, int32_t B, uint32_t seed, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,6 +1,6 @@
 """What one policy evaluation costs (utils/evaluator.py), and what the metric kernel saves over torch expressions.
 
-    python tools/eval_bench.py [--task go2_flat] [--reps 3] [--robust] [--ladder] [--maneuvers] [--sensors] [--blackbox] [--asymmetry] [--ci] [--ci_all] [--spectrum] [--out profiles/eval_bench.json]
+    python tools/eval_bench.py [--task go2_flat] [--reps 3] [--robust] [--ladder] [--maneuvers] [--sensors] [--blackbox] [--asymmetry] [--ci] [--ci_all] [--spectrum] [--actuators] [--out profiles/eval_bench.json]
 
 Measures, on cuda:0, with the task's default `evaluation` section (1024 robots, 1 s + 10 s):
   * wall time of evaluate() run eagerly and with the captured chunk of steps replayed (simulator re-creation, capture and the final host copy included: it is what
@@ -32,6 +32,10 @@ written in numpy on the host with the copy of the accumulators it would need.
 (at least five) in this one session — best, median, spread, every run and the difference of the medians —, go2nn_spectrum_record per back-to-back call, go2nn_spectrum_welch
 per back-to-back launch on the evaluation's own trace, a device-to-device copy of the trace's bytes for scale, and the Welch kernel's registers, LDS and scratch from the
 code object's notes.
+--actuators: a measurement of its own, written to profiles/actuators_bench.json: evaluate() run eagerly with evaluation.actuators off and on, alternating, --reps runs each
+(at least five) in this one session — best, median, spread, every run and the difference of the medians —, go2nn_actuator_accumulate per back-to-back call next to
+go2nn_gait_accumulate and go2nn_asym_accumulate timed the same way in the same process on the same simulator's buffers, go2nn_actuator_bootstrap next to go2nn_gait_bootstrap
+at 6, 42 and 294 cells (B = 1000), the reduce, the copy of the rows the extremes are read from, and the kernels' registers and scratch from the code object's notes.
 Writes one JSON file and prints it."""
 import argparse
 import ctypes as C
@@ -471,6 +475,101 @@ def spectrum_main(a):
         e.close()
 
 
+def actuator_launches(ev):
+    """ev: an evaluator with actuators, gait and asymmetry on, after an evaluation -> device and host us per back-to-back go2nn_<family>_accumulate call on its own buffers:
+    begin at step 0, 20 calls to warm up, begin again, 200 timed calls — every one a counted step"""
+    N, st, out = ev.num_envs, ev._stream(), {}
+    actions = torch.zeros(N, 12, device=ev.device)
+    for t in ev.tables:
+        if t.name not in ("actuator", "gait", "asym"):
+            continue
+        tin, extra = t.make_in(), ((C.c_void_p(actions.data_ptr()), C.c_void_p(actions.data_ptr())) if t.name == "asym" else ())
+        begin = lambda: getattr(ev.nn, "go2nn_%s_begin" % t.name)(C.c_void_p(t.table.data_ptr()), N, 0, st)
+        acc = lambda: getattr(ev.nn, "go2nn_%s_accumulate" % t.name)(C.byref(tin), *extra, C.c_void_p(t.table.data_ptr()), N, st)
+        keep = t.table.clone()
+        assert begin() == 0 and acc() == 0, ev.nn.go2nn_last_error()
+        timed(acc, 20)
+        assert begin() == 0
+        dev_us, wall_us = timed(acc, 200)
+        t.table.copy_(keep)
+        out[t.name] = {"device_us_per_launch_back_to_back": dev_us, "host_us_per_call": wall_us}
+    return out
+
+
+def actuator_bootstraps(ev, B=1000):
+    """-> device us per back-to-back go2nn_actuator_bootstrap and go2nn_gait_bootstrap launch on the evaluator's own tables at 6, 42 and 294 cells of its robots"""
+    import numpy as np
+    N, st, out, p = ev.num_envs, ev._stream(), {}, lambda t: C.c_void_p(t.data_ptr())
+    for t in ev.tables:
+        if t.name not in ("actuator", "gait"):
+            continue
+        for G in (6, 42, 294):
+            cell = (np.arange(N) % G).astype(np.int32)
+            start, envs = np.concatenate([[0], np.cumsum(np.bincount(cell, minlength=G))]).astype(np.int32), np.argsort(cell, kind="stable").astype(np.int32)
+            s_d, e_d = torch.from_numpy(start).to(ev.device), torch.from_numpy(envs).to(ev.device)
+            res = torch.zeros(B, G, int(t.out.shape[1]), dtype=torch.float64, device=ev.device)
+            fn = lambda: getattr(ev.nn, "go2nn_%s_bootstrap" % t.name)(p(t.table), p(s_d), p(e_d), N, G, B, 2718, p(res), st)
+            assert fn() == 0, ev.nn.go2nn_last_error()
+            timed(fn, 20)
+            out["%s/%d" % (t.name, G)] = {"device_us_per_launch_back_to_back": timed(fn, 200)[0]}
+    return out
+
+
+def actuators_main(a):
+    """--actuators: what `evaluation.actuators` costs one evaluation, next to the same evaluation without it in the same session (alternating runs), and its launches alone
+    next to the gait and asymmetry scorers' -> profiles/actuators_bench.json"""
+    from go2_rl_gym_amd import build
+    env_cfg, train_cfg = task_registry.get_cfgs(a.task)
+    ev_cfg = class_to_dict(train_cfg.evaluation)
+    make = lambda **over: PolicyEvaluator(env_cfg, dict(ev_cfg, **over), task_class=task_registry.get_task_class(a.task), device="cuda:0")
+    evs = {"off": make(actuators=False), "on": make(actuators=True)}
+    from go2_rl_gym_amd.rsl_rl.modules import ActorCritic
+    torch.manual_seed(0)
+    ac = ActorCritic(45, 263, 12, **{k: v for k, v in class_to_dict(train_cfg.policy).items() if k in ("actor_hidden_dims", "critic_hidden_dims", "activation", "init_noise_std")}).to("cuda:0")
+    res = {k: ev.evaluate(ac, use_graph=False) for k, ev in evs.items()}
+    assert res["off"]["table"].tobytes() == res["on"]["table"].tobytes() and "actuators" not in res["off"]
+    ev = evs["on"]
+    N, st = ev.num_envs, ev._stream()
+    entry = {"task": a.task, "device": torch.cuda.get_device_name(0), "num_envs": N, "steps": ev.warmup_steps + ev.steps, "counted_steps": ev.steps, "cells": ev.num_cells,
+             "table_bytes": int(ev.act_table.numel() * 4), "overall": {k: v for k, v in res["on"]["actuators"]["overall"].items() if "/" not in k}}
+    entry["registers"] = {name: {k: r[k] for k in ("kernel", "vgpr_count", "sgpr_count", "scratch_bytes_per_lane", "lds_bytes_per_workgroup")}
+                          for name, r in (("accumulate", build.kernel_resources(build.NN_OUT, match="ActuatorAccumulate")),
+                                          ("reduce", build.kernel_resources(build.NN_OUT, match="eval_reduce_kernelILin1E12ActuatorTerm")),
+                                          ("bootstrap", build.kernel_resources(build.NN_OUT, match="eval_bootstrap_kernelILi112E"))) if r}
+    # the per-step launch next to gait's and the asymmetry's: one evaluator with all three on, so that the three are timed in one process on one simulator's buffers
+    three = make(actuators=True, gait=True, asymmetry=True)
+    three.evaluate(ac, use_graph=False)
+    entry["accumulate"] = actuator_launches(three)
+    entry["bootstrap_B1000"] = actuator_bootstraps(three)
+    three.close()
+    group = C.c_void_p(ev.group.data_ptr())
+    red = lambda: ev.nn.go2nn_actuator_reduce(C.c_void_p(ev.act_table.data_ptr()), group, N, ev.num_cells, C.c_void_p(ev.act_out.data_ptr()), st)
+    timed(red, 3)
+    entry["reduce"] = {"device_us_per_launch_back_to_back": timed(red, 20)[0]}
+    rows = lambda: ev.act_table.index_select(0, ev.act_extreme_rows).cpu()
+    timed(rows, 3)
+    entry["extremes_copy"] = {"rows": int(ev.act_extreme_rows.numel()), "host_us_per_copy": timed(rows, 20)[1]}
+    if not a.kernel_only:
+        walls = {k: [] for k in evs}
+        for _ in range(max(a.reps, 5)):          # alternating, in this one session
+            for k, e in evs.items():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                e.evaluate(ac, use_graph=False)
+                walls[k].append((time.perf_counter() - t0) * 1e3)
+        entry["evaluate_wall_ms_eager"] = {k: {"best": min(w), "median": statistics.median(w), "spread": max(w) - min(w), "all": w} for k, w in walls.items()}
+        entry["evaluate_wall_ms_eager"]["on_minus_off_median"] = statistics.median(walls["on"]) - statistics.median(walls["off"])
+        if os.path.exists(a.out):          # sections of the file this tool does not measure (merged by hand; their "about" says from what) stay
+            with open(a.out) as f:
+                entry.update({k: v for k, v in json.load(f).items() if k in ("variants", "bench_py_env_steps_per_s")})
+        os.makedirs(os.path.dirname(a.out), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(entry, f, indent=1)
+    print(json.dumps(entry))
+    for e in evs.values():
+        e.close()
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--task", default="go2_flat")
@@ -485,9 +584,12 @@ def main():
     p.add_argument("--ci", action="store_true")
     p.add_argument("--ci_all", action="store_true")
     p.add_argument("--spectrum", action="store_true")
+    p.add_argument("--actuators", action="store_true")
     p.add_argument("--out", default=None)
     a = p.parse_args()
-    a.out = a.out or os.path.join(ROOT, "profiles", "spectrum_bench.json" if a.spectrum else "bootstrap_all_bench.json" if a.ci_all else "bootstrap_bench.json" if a.ci else "asymmetry_bench.json" if a.asymmetry else "blackbox_bench.json" if a.blackbox else "eval_bench.json")
+    a.out = a.out or os.path.join(ROOT, "profiles", "actuators_bench.json" if a.actuators else "spectrum_bench.json" if a.spectrum else "bootstrap_all_bench.json" if a.ci_all else "bootstrap_bench.json" if a.ci else "asymmetry_bench.json" if a.asymmetry else "blackbox_bench.json" if a.blackbox else "eval_bench.json")
+    if a.actuators:
+        return actuators_main(a)
     if a.spectrum:
         return spectrum_main(a)
     if a.ci_all:
